@@ -2,7 +2,7 @@
 """Headline benchmark: ns/day (+ pair-interactions/s) of the 100k-atom TIP3P water box (config C3 of
 BASELINE.json / SURVEY.md §8) on N MI355X, one independent replica per GPU (config C4, weak scaling).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
            --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -84,6 +84,40 @@ def time_pair_launches(forces, integ, system, nsteps=TIMING_PASS_STEPS):
     ms, launches = forces.read_timing(system.pos, reset=True)
     forces.enable_timing(system.pos, False)
     return ms, launches
+
+
+DUMP_LIMIT_BYTES = 64 * 2**20  # --dump-outputs: all arrays together
+
+
+def timed_outputs(ekin, epot, temp, system):
+    """What the timed `Integrator.step` call hands its caller — kinetic energy, potential energy and temperature of its
+    last step, per replica — and the state that step leaves in `system` (positions, velocities, forces), on the host."""
+    def host(t):
+        a = t.detach().cpu().numpy()
+        return a if a.dtype in (np.float32, np.float64) else a.astype(np.float32)
+
+    return {"ekin": np.asarray(ekin, dtype=np.float64), "epot": np.asarray(epot, dtype=np.float64),
+            "temperature": np.asarray(temp, dtype=np.float64),
+            "pos": host(system.pos), "vel": host(system.vel), "forces": host(system.forces)}
+
+
+def dump_outputs(path, arrays, limit=DUMP_LIMIT_BYTES):
+    """Write every array as `path/<name>.npy`.  If they exceed `limit` bytes in all, the per-atom arrays ([replicas, atoms,
+    3]) keep a fixed sample of atoms, the same in every run (seeded, sorted), whose indices go to `atom_index.npy` (as
+    float64).  Returns the names written and the number of atoms kept (None: all of them)."""
+    os.makedirs(path, exist_ok=True)
+    per_atom = [k for k, a in arrays.items() if a.ndim == 3]
+    total = sum(a.nbytes + 256 for a in arrays.values())  # (256: room for an .npy header)
+    kept = None
+    if per_atom and total > limit:
+        natoms = arrays[per_atom[0]].shape[1]
+        atom_bytes = sum(arrays[k].nbytes for k in per_atom) / natoms
+        kept = int((limit - 256 - (total - atom_bytes * natoms)) // (atom_bytes + 8))
+        idx = np.sort(np.random.default_rng(0).choice(natoms, size=kept, replace=False))
+        arrays = dict(arrays, **{k: np.ascontiguousarray(arrays[k][:, idx]) for k in per_atom}, atom_index=idx.astype(np.float64))
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+    return sorted(arrays), kept
 
 
 def pmc_traffic(switched=False):
@@ -538,11 +572,12 @@ def cpu_baseline(par, state, box, budget_s=20.0):
     }
 
 
-def c3_leg(forces, integ, system, natoms, steps, fan, pmc=True, switched=False):
+def c3_leg(forces, integ, system, natoms, steps, fan, pmc=True, switched=False, keep_outputs=False):
     """One timed leg on the water box: `integ.step(steps)` between barrier + synchronize on both sides (nothing else in
     the region: no events, no read-backs), then — outside the region — the statistics, the pass that times the dominant
     kernel (time_pair_launches) and the pair count; returns the elapsed time, the observables and the `roofline` /
-    `list` blocks of a bench line."""
+    `list` blocks of a bench line.  keep_outputs: also `outputs`, what the timed call computed (timed_outputs), taken
+    before the timing pass moves the system on."""
     st0 = forces.stats(system.pos)
     replays0 = integ.replays
     fan.barrier()
@@ -553,6 +588,7 @@ def c3_leg(forces, integ, system, natoms, steps, fan, pmc=True, switched=False):
     elapsed = time.perf_counter() - t0  # this rank's K steps are complete (barrier + synchronize in front, synchronize
     fan.barrier()                       # + barrier behind); the job's time is the slowest rank's
     elapsed = fan.max_over_ranks(elapsed)
+    outputs = timed_outputs(ekin, epot, temp, system) if keep_outputs else None
     st1 = forces.stats(system.pos)
     replays = integ.replays - replays0
     obs = fan.gather_observables(ekin, epot, temp)
@@ -627,7 +663,7 @@ def c3_leg(forces, integ, system, natoms, steps, fan, pmc=True, switched=False):
         "capacity_per_atom": int(st2["max_neighbours"]),
         "ncell": list(st2["ncell"]),
     }
-    return {"elapsed": elapsed, "obs": obs, "pairs_in_cutoff": pcut, "roofline": roofline, "list": lst}
+    return {"elapsed": elapsed, "obs": obs, "pairs_in_cutoff": pcut, "roofline": roofline, "list": lst, "outputs": outputs}
 
 
 def main():
@@ -647,12 +683,19 @@ def main():
                     "`config.workload` says so; the default line carries the switched box as `secondary.c3_switch`)")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend (nccl = RCCL; gloo with --dry)")
     ap.add_argument("--dry", action="store_true", help="launcher/collective plumbing only, no GPU work (CPU test)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last of them computed (ekin, epot, temperature; positions, "
+                    "velocities and forces of the box) as DIR/<name>.npy; c3 only, rank 0's replica")
     ap.add_argument("--config", default="c3", choices=["c3", "c5"],
                     help="c3 (default, the headline): 98 304-atom TIP3P box, one replica per GPU; c5: 10^6-atom LJ box, "
                     "spatial domain decomposition for --gpus > 1")
     args = ap.parse_args()
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1:
+        raise SystemExit("--steps must be >= 1")
+    if args.dump_outputs and (args.config != "c3" or args.dry):
+        raise SystemExit("--dump-outputs: the c3 workload on a GPU only")
     if args.gpus > 1 and "RANK" not in os.environ:
         raise SystemExit(self_launch(args))
 
@@ -694,7 +737,9 @@ def main():
     if args.warmup:
         integ.step(args.warmup)
 
-    leg = c3_leg(forces, integ, system, natoms, args.steps, fan, pmc=args.nside == 32, switched=args.switch_dist is not None)
+    leg = c3_leg(forces, integ, system, natoms, args.steps, fan, pmc=args.nside == 32, switched=args.switch_dist is not None,
+                 keep_outputs=bool(args.dump_outputs) and rank == 0)
+    dumped = dump_outputs(args.dump_outputs, leg["outputs"]) if leg["outputs"] is not None else None
     elapsed, obs, pcut = leg["elapsed"], leg["obs"], leg["pairs_in_cutoff"]
     steps_per_s = args.steps / elapsed
     value = ns_per_day(args.steps, elapsed) * world
@@ -730,6 +775,8 @@ def main():
         "list": dict(leg["list"], skin_weights=args.skin_weights),
         "roofline": leg["roofline"],
     }
+    if dumped:
+        out["outputs"] = {"dir": args.dump_outputs, "arrays": dumped[0], "atoms_sampled": dumped[1]}
     if world > 1:
         out["rccl"] = rccl_info(world, args.backend)
     want_cpu = rank == 0 and world == 1 and not args.no_cpu_baseline

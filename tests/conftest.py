@@ -16,16 +16,11 @@ if (os.cpu_count() or 1) > 16:
 
 def pytest_configure(config):
     config.addinivalue_line("markers", "gpu: needs a real MI355X (run with -m gpu via gpurun)")
-    config.addinivalue_line("markers", "needs_reference: needs /root/reference (build container only)")
 
 
 def pytest_collection_modifyitems(config, items):
-    have_ref = os.path.isdir("/root/reference/torchmd")
-    skip_ref = pytest.mark.skip(reason="/root/reference not present (GPU box)")
     have_gpu = None
     for item in items:
-        if "needs_reference" in item.keywords and not have_ref:
-            item.add_marker(skip_ref)
         if "gpu" in item.keywords:
             if have_gpu is None:
                 import torch

@@ -217,8 +217,50 @@ def wrap():
     np.savez_compressed(os.path.join(HERE, "wrap.npz"), **out)
 
 
+def params():
+    """Inputs and outputs of the reader / `Parameters` tests of tests/test_host_logic.py: the reference's own input files
+    (bytes, so that the tests run this repo's readers on them) and what the reference's `Parameters` makes of them —
+    tables, A/B, exclusions.  Case `water_f32` / `water_f64`: the reference's YAML force field on tests/water; the
+    AMBER cases: this repo's `PrmtopForceField` fed to the reference's `Parameters` (its own backend needs parmed)."""
+    from torchmd.forcefields.ff_yaml import YamlForcefield as RefYaml
+
+    out = {}
+
+    def store_file(case, name, path):
+        with open(path, "rb") as fh:
+            out[f"{case}_in_{name}"] = np.frombuffer(fh.read(), dtype=np.uint8)
+
+    def store_par(case, par, ab=False):
+        pack_parameters(par, out, prefix=case + "_")
+        out[case + "_exclusions"] = np.array(sorted(map(tuple, par.get_exclusions())), dtype=np.int64).reshape(-1, 2)
+        if ab:
+            out[case + "_A"], out[case + "_B"] = (x.numpy() for x in par.get_AB())
+
+    d = os.path.join(REF, "tests", "water")
+    mol = tio.read_psf(os.path.join(d, "structure.psf"))
+    terms = ["lj", "bonds", "angles", "electrostatics"]
+    for prec in ("f32", "f64"):
+        case = "water_" + prec
+        store_file(case, "psf", os.path.join(d, "structure.psf"))
+        store_file(case, "yaml", os.path.join(d, "water_forcefield.yaml"))
+        ref = RefParameters(RefYaml(mol, os.path.join(d, "water_forcefield.yaml")), mol, terms, precision=PREC[prec])
+        store_par(case, ref, ab=True)
+    for case, folder in (("ala2", "prod_alanine_dipeptide_amber"), ("thrombin-ligand-amber", "thrombin-ligand-amber"),
+                         ("benzamidine-amber", "benzamidine-amber"), ("ligand-amber", "ligand-amber")):
+        d = os.path.join(REF, "tests", "data", folder)
+        store_file(case, "prmtop", os.path.join(d, "structure.prmtop"))
+        if case == "ala2":
+            store_file(case, "coor", os.path.join(d, "input.coor"))
+            store_file(case, "xsc", os.path.join(d, "input.xsc"))
+        mol, top = tio.read_prmtop(os.path.join(d, "structure.prmtop"))
+        ref = RefParameters(PrmtopForceField(mol, top), mol, ALL_TERMS, precision=torch.float64)
+        store_par(case, ref)
+    np.savez_compressed(os.path.join(HERE, "params.npz"), **out)
+    print("params:", sorted({k.split("_in_")[0] for k in out if "_in_" in k}))
+
+
 if __name__ == "__main__":
     torch.set_num_threads(8)
-    which = sys.argv[1:] or ["water291", "ala2", "thrombin", "wrap"]
+    which = sys.argv[1:] or ["water291", "ala2", "thrombin", "wrap", "params"]
     for w in which:
         globals()[w]()

@@ -1,5 +1,5 @@
 """CPU tests (no GPU): C-ABI surface, host-side logic of the Forces/Integrator mirror, topology
-readers / Parameters against the reference (when /root/reference is present), replica fan-out over
+readers / Parameters against the reference's (stored in tests/golden/params.npz), replica fan-out over
 gloo with world_size 2."""
 
 import ctypes as C
@@ -8,6 +8,7 @@ import os
 import re
 import subprocess
 import sys
+from types import SimpleNamespace
 
 import numpy as np
 import pytest
@@ -237,14 +238,36 @@ def test_replica_fanout_gloo_world2(tmp_path):
 
 
 # ------------------------------------------------------------------------------------------------
-# readers + Parameters vs the reference itself (build container only)
+# readers + Parameters vs the reference's Parameters (tests/golden/params.npz: its input files and what it made of them)
 # ------------------------------------------------------------------------------------------------
-def _ref_modules():
-    sys.path.insert(0, "/root/reference")
-    from torchmd.forcefields.ff_yaml import YamlForcefield
-    from torchmd.parameters import Parameters as RefParameters
+_INPUT_NAMES = {"psf": "structure.psf", "yaml": "water_forcefield.yaml", "prmtop": "structure.prmtop", "coor": "input.coor",
+                "xsc": "input.xsc"}
 
-    return YamlForcefield, RefParameters
+
+def _ref_case(case, tmp_path):
+    """The reference's input files of `case`, written to tmp_path ({kind: path}), and a duck type of the reference's
+    `Parameters` built from them (tests/golden/make_golden.py: params)."""
+    g = load("params")
+    files = {}
+    for kind, name in _INPUT_NAMES.items():
+        key = f"{case}_in_{kind}"
+        if key in g:
+            files[kind] = str(tmp_path / name)
+            with open(files[kind], "wb") as fh:
+                fh.write(g[key].tobytes())
+    assert files, case
+
+    def t(key):
+        return torch.from_numpy(g[f"{case}_{key}"]) if f"{case}_{key}" in g else None
+
+    ref = SimpleNamespace(charges=t("charges"), masses=t("masses"), mapped_atom_types=t("types"),
+                          nonbonded_params={"params": t("nonbonded_params")},
+                          get_AB=lambda: (t("A"), t("B")),
+                          get_exclusions=lambda: [tuple(int(x) for x in row) for row in g[case + "_exclusions"]])
+    for name in ("bond", "angle", "dihedral", "improper", "nonbonded_14"):
+        idx = t(name + "_idx")
+        setattr(ref, name + "_params", None if idx is None else {"idx": idx, "map": t(name + "_map"), "params": t(name + "_params")})
+    return files, ref
 
 
 def _same_table(a, b):
@@ -255,19 +278,16 @@ def _same_table(a, b):
     return ok and torch.equal(a["map"][:, 0], b["map"][:, 0]) and torch.equal(pa, pb)
 
 
-@pytest.mark.needs_reference
 @pytest.mark.parametrize("prec", [torch.float32, torch.float64])
-def test_parameters_match_reference_water(prec):
+def test_parameters_match_reference_water(prec, tmp_path):
     from torchmd_amd import io as tio
     from torchmd_amd.forcefields import YamlForceField
     from torchmd_amd.parameters import Parameters
 
-    RefYaml, RefParameters = _ref_modules()
-    d = "/root/reference/tests/water"
-    mol = tio.read_psf(os.path.join(d, "structure.psf"))
+    files, ref = _ref_case("water_" + ("f32" if prec == torch.float32 else "f64"), tmp_path)
+    mol = tio.read_psf(files["psf"])
     terms = ["lj", "bonds", "angles", "electrostatics"]
-    mine = Parameters(YamlForceField(mol, os.path.join(d, "water_forcefield.yaml")), mol, terms, precision=prec)
-    ref = RefParameters(RefYaml(mol, os.path.join(d, "water_forcefield.yaml")), mol, terms, precision=prec)
+    mine = Parameters(YamlForceField(mol, files["yaml"]), mol, terms, precision=prec)
     assert torch.equal(mine.charges, ref.charges) and torch.equal(mine.masses, ref.masses)
     assert torch.equal(mine.mapped_atom_types, ref.mapped_atom_types)
     assert torch.equal(mine.nonbonded_params["params"], ref.nonbonded_params["params"])
@@ -278,47 +298,39 @@ def test_parameters_match_reference_water(prec):
     assert sorted(map(tuple, mine.get_exclusions())) == sorted(map(tuple, ref.get_exclusions()))
 
 
-@pytest.mark.needs_reference
-def test_parameters_match_reference_ala2():
+def test_parameters_match_reference_ala2(tmp_path):
     from torchmd_amd import io as tio
     from torchmd_amd.forcefields import ForceField, PrmtopForceField
     from torchmd_amd.parameters import Parameters
 
-    _, RefParameters = _ref_modules()
-    d = "/root/reference/tests/data/prod_alanine_dipeptide_amber"
-    mol, top = tio.read_prmtop(os.path.join(d, "structure.prmtop"))
+    files, ref = _ref_case("ala2", tmp_path)
+    mol, top = tio.read_prmtop(files["prmtop"])
     ff = PrmtopForceField(mol, top)
-    assert isinstance(ForceField.create(mol, os.path.join(d, "structure.prmtop")), PrmtopForceField)
+    assert isinstance(ForceField.create(mol, files["prmtop"]), PrmtopForceField)
     terms = ["bonds", "angles", "dihedrals", "impropers", "1-4", "electrostatics", "lj"]
     mine = Parameters(ff, mol, terms, precision=torch.float64)
-    ref = RefParameters(ff, mol, terms, precision=torch.float64)
     for name in ("bond", "angle", "dihedral", "improper", "nonbonded_14"):
         assert _same_table(getattr(mine, name + "_params"), getattr(ref, name + "_params")), name
     assert torch.equal(mine.nonbonded_params["params"], ref.nonbonded_params["params"])
     g = load("ala2")
     assert np.array_equal(mine.charges.numpy(), g["par_charges"])
-    assert np.array_equal(tio.read_namd_coor(os.path.join(d, "input.coor")), g["pos"])
-    assert np.array_equal(tio.read_xsc(os.path.join(d, "input.xsc")), g["box"])
+    assert np.array_equal(tio.read_namd_coor(files["coor"]), g["pos"])
+    assert np.array_equal(tio.read_xsc(files["xsc"]), g["box"])
 
 
-@pytest.mark.needs_reference
 @pytest.mark.parametrize("folder", ["thrombin-ligand-amber", "benzamidine-amber", "ligand-amber"])
-def test_parameters_match_reference_prmtop_fixtures(folder):
+def test_parameters_match_reference_prmtop_fixtures(folder, tmp_path):
     """Own prmtop reader + `PrmtopForceField` + `Parameters` against the reference's `Parameters` fed with
     the same objects, on the reference's AMBER fixtures (protein + ligand complex, two ligands: impropers, many atom types)."""
     from torchmd_amd import io as tio
     from torchmd_amd.forcefields import PrmtopForceField
     from torchmd_amd.parameters import Parameters
 
-    _, RefParameters = _ref_modules()
-    path = os.path.join("/root/reference/tests/data", folder, "structure.prmtop")
-    if not os.path.exists(path):
-        pytest.skip(f"no {path}")
-    mol, top = tio.read_prmtop(path)
+    files, ref = _ref_case(folder, tmp_path)
+    mol, top = tio.read_prmtop(files["prmtop"])
     ff = PrmtopForceField(mol, top)
     terms = ["bonds", "angles", "dihedrals", "impropers", "1-4", "electrostatics", "lj"]
     mine = Parameters(ff, mol, terms, precision=torch.float64)
-    ref = RefParameters(ff, mol, terms, precision=torch.float64)
     for name in ("bond", "angle", "dihedral", "improper", "nonbonded_14"):
         assert _same_table(getattr(mine, name + "_params"), getattr(ref, name + "_params")), name
     assert torch.equal(mine.nonbonded_params["params"], ref.nonbonded_params["params"])
@@ -641,6 +653,35 @@ def test_bench_self_launch_gloo_world2(world):
                          text=True, timeout=300, env=env)
     assert res.returncode == 0, res.stderr[-2000:]
     assert json.loads([ln for ln in res.stdout.splitlines() if ln.startswith("{")][0])["n_gpus"] == 1
+
+
+def test_bench_dump_outputs(tmp_path):
+    """`bench.py --dump-outputs DIR` writes float32 / float64 arrays; beyond the byte limit the per-atom arrays keep a fixed,
+    seeded sample of atoms (the same in every run) with its indices, and the files stay within the limit."""
+    import importlib.util
+
+    spec = importlib.util.spec_from_file_location("bench_for_test", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    rng = np.random.default_rng(3)
+    arrays = {"ekin": np.array([1.5]), "epot": np.array([-2.5]), "temperature": np.array([300.0]),
+              **{k: rng.normal(size=(1, 5000, 3)).astype(np.float32) for k in ("pos", "vel", "forces")}}
+    names, kept = bench.dump_outputs(str(tmp_path / "all"), arrays)
+    assert kept is None and names == sorted(arrays)
+    for k, a in arrays.items():
+        assert np.array_equal(np.load(tmp_path / "all" / f"{k}.npy"), a)
+    limit = 60_000
+    for run in ("a", "b"):
+        names, kept = bench.dump_outputs(str(tmp_path / run), arrays, limit=limit)
+        assert "atom_index" in names and 0 < kept < 5000
+        files = {n: np.load(tmp_path / run / f"{n}.npy") for n in names}
+        assert sum((tmp_path / run / f"{n}.npy").stat().st_size for n in names) <= limit
+        assert all(a.dtype in (np.float32, np.float64) for a in files.values())
+        idx = files["atom_index"].astype(np.int64)
+        assert len(idx) == kept and np.all(np.diff(idx) > 0)
+        assert np.array_equal(files["pos"], arrays["pos"][:, idx]) and np.array_equal(files["ekin"], arrays["ekin"])
+    for n in names:
+        assert np.array_equal(np.load(tmp_path / "a" / f"{n}.npy"), np.load(tmp_path / "b" / f"{n}.npy"))
 
 
 def test_skin_weight_rules():
