@@ -509,9 +509,7 @@ def test_lj_million_atoms_vs_oracle(nside):
     all of their pairs are there) must equal the GPU's within the fp32 bar; (ii) 10^6-atom box only: the in-cutoff
     pair COUNT of the whole box by the oracle's decision arithmetic (pair_geometry + `dist <= cutoff`, fp32, in chunks)
     must equal the GPU's count exactly."""
-    from scipy.spatial import cKDTree
-
-    from oracle import torchmd_oracle as orc
+    from _oracle_sample import periodic_count, periodic_tree, sample_forces
     from torchmd_amd.builders import argon_forcefield, lj_box
     from torchmd_amd.forces import Forces
     from torchmd_amd.integrator import Integrator, maxwell_boltzmann
@@ -534,34 +532,16 @@ def test_lj_million_atoms_vs_oracle(nside):
     assert st["algorithm"] == "celllist" and st["overflow"] == 0 and st["steps_in_pair_launch"] >= 10, st
     p = s.pos.detach().cpu()
     Fg = s.forces.detach().cpu()
-    p64 = p[0].double().numpy()
-    b = np.asarray(box, dtype=np.float64)
-    w = p64 - np.floor(p64 / b) * b
-    w = np.where(w >= b, w - b, w)
-    tree = cKDTree(w, boxsize=b)
-    pick = np.sort(np.random.default_rng(7).choice(n, 20000, replace=False))
-    nb = tree.query_ball_point(w[pick], 9.5, workers=-1)
-    i = np.repeat(pick, [len(x) for x in nb])
-    j = np.concatenate([np.asarray(x, dtype=np.int64) for x in nb])
-    keep = i != j
-    lo, hi = np.minimum(i[keep], j[keep]), np.maximum(i[keep], j[keep])
-    key = np.unique(lo * np.int64(n) + hi)  # pairs between two picked atoms were found twice; sorted (i asc, j asc)
-    pairs = np.stack([key // n, key % n], axis=1)
-    _, Fo, nin = orc.compute(par, p, s.box.cpu(), ["lj"], pairs=pairs, cutoff=9.0)
-    err = (Fg[0, pick] - Fo[0, pick]).abs().max().item()
-    print(f"{n} argon atoms after 12 MD steps: {len(pairs)} candidate pairs touch the 20 000 picked atoms, {nin[0]} inside the "
+    tree = periodic_tree(p[0].double().numpy(), box)
+    pick, Fo, npairs, nin = sample_forces(par, p, s.box.cpu(), ["lj"], 20000, 7, rlist=9.5, tree=tree, cutoff=9.0)
+    err = (Fg[0, pick] - Fo).abs().max().item()
+    print(f"{n} argon atoms after 12 MD steps: {npairs} candidate pairs touch the 20 000 picked atoms, {nin} inside the "
           f"cutoff; max|dF| on the picked atoms = {err:.3e} (max|F| = {Fg[0, pick].abs().max().item():.2f})")
-    assert nin[0] > 600000
+    assert nin > 600000
     assert err < FTOL["f32"]
     if nside == 100:
         n_gpu = f.count_pairs(s.pos, s.box)[0]
-        allp = tree.query_pairs(9.05, output_type="ndarray")
-        pt, bt = p[0], s.box.cpu()[0][torch.eye(3).bool()]
-        total = 0
-        for c in range(0, len(allp), 4_000_000):
-            idx = torch.as_tensor(allp[c: c + 4_000_000].astype(np.int64))
-            d, _, _ = orc.pair_geometry(pt, idx, bt)
-            total += int((d <= 9.0).sum().item())
+        total = periodic_count(p[0], box, 9.0, tree=tree)
         print(f"P_cut of the whole box: oracle {total}, GPU {n_gpu}")
         assert n_gpu == total
     f.close()
