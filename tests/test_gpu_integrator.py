@@ -340,7 +340,7 @@ def test_replica_batched_md_matches_single_replica_runs():
     assert np.abs(pb[0] - pb[2]).max() > 1e-3
 
 
-@pytest.mark.parametrize("case", ["langevin", "nve", "langevin-switch", "nve-boxes", "nve-f64", "nve-thrombin"])
+@pytest.mark.parametrize("case", ["langevin", "nve", "langevin-switch", "nve-boxes", "nve-f64", "nve-thrombin", "nve-boxes-light-full"])
 def test_replicas_of_a_celllist_context_in_one_launch_are_bit_identical(case, monkeypatch):
     """The reference's batch axis on the cell-list path (systems.py:6-18, forces.py:105,116): fp32 contexts with several
     replicas make ONE pair + step launch per MD step for all of them (round 6; every replica keeps its own neighbour state,
@@ -371,6 +371,12 @@ def test_replicas_of_a_celllist_context_in_one_launch_are_bit_identical(case, mo
         n = pos0.shape[0]
         terms = ["bonds", "angles", "dihedrals", "impropers", "1-4", "electrostatics", "lj"]
         R, kw, jitter, vscale = 2, dict(cutoff=9.0, algorithm="celllist"), 0.01, 0.01
+    elif "light-full" in case:  # all five bonded kinds on the light scheme, molecules across 64-atom blocks and box faces
+        import _bonded_systems as B
+
+        s = B.light_full(B.LARGE)
+        par, pos0, box0, n, terms = s.par(dt), s.pos, s.box, s.natoms, B.ALL_TERMS
+        R, kw, jitter, vscale = 3, dict(cutoff=9.0, rfa=True), 0.02, 0.01
     else:
         mol, pos0, box0 = tip3p_box(12, seed=3)
         n = mol.numAtoms
@@ -744,7 +750,7 @@ def test_fused_launch_timeout_falls_back_to_the_integrator_kernel(monkeypatch):
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("case", ["water_langevin", "water_nve", "water_two_replicas", "lj_langevin", "water_counter_wraps",
-                                  "water_32_lanes", "water_64_lanes", "thrombin"])
+                                  "water_32_lanes", "water_64_lanes", "thrombin", "light_full"])
 def test_step_blocks_of_the_pair_launch_are_bit_identical(case, monkeypatch):
     """Interior steps of tmdhip_md_run on the lean fp32 pair kernel are made by the pair launch itself ("step blocks"
     behind the pair blocks wait for the pair waves of their atoms: FusedStep in csrc/engine.h, pair_fast_f32.hip) instead of by an
@@ -774,6 +780,12 @@ def test_step_blocks_of_the_pair_launch_are_bit_identical(case, monkeypatch):
         pos, box = np.asarray(g["pos"], dtype=np.float64), np.zeros(3)
         terms = ["bonds", "angles", "dihedrals", "impropers", "1-4", "electrostatics", "lj"]
         kw = dict(cutoff=9.0)
+    elif case == "light_full":  # all five bonded kinds on the light scheme, molecules across 64-atom step blocks
+        import _bonded_systems as B
+
+        s = B.light_full(B.LARGE)
+        par, pos, box, terms = s.par(dt), s.pos, s.box, B.ALL_TERMS
+        kw = dict(cutoff=9.0, rfa=True)
     elif case.startswith("water"):
         mol, pos, box = tip3p_box(14, seed=4)  # 8 232 atoms
         terms = ["lj", "electrostatics", "bonds", "angles"]
@@ -785,7 +797,7 @@ def test_step_blocks_of_the_pair_launch_are_bit_identical(case, monkeypatch):
         par = Parameters(argon_forcefield(mol), mol, terms, precision=dt)
         kw = dict(cutoff=9.0)
     gamma = None if case == "water_nve" else 1.0
-    lanes = {"water_32_lanes": "32", "water_64_lanes": "64", "thrombin": "64"}.get(case, "8" if case.startswith("water") else "4")
+    lanes = {"water_32_lanes": "32", "water_64_lanes": "64", "thrombin": "64", "light_full": "16"}.get(case, "8" if case.startswith("water") else "4")
     monkeypatch.setenv("TMDHIP_LPA", lanes)  # (32 / 64: what mid-size boxes get; 8 and 16 pair blocks per step block)
     torch.manual_seed(3)
     vel0 = maxwell_boltzmann(par.masses, 300.0, nrep)
@@ -824,7 +836,7 @@ def test_step_blocks_of_the_pair_launch_are_bit_identical(case, monkeypatch):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("case", ["water_langevin", "water_nve", "lj_langevin", "thrombin"])
+@pytest.mark.parametrize("case", ["water_langevin", "water_nve", "lj_langevin", "thrombin", "light_full"])
 def test_final_step_of_a_call_in_the_pair_launch(case, monkeypatch):
     """The LAST step of a step() call (reference integrator.py:116-125: forces, second half kick, then the energies and
     the kinetic energy the call returns) is made by the last pair launch itself: FINAL step blocks (csrc/md_step.h) apply
@@ -846,6 +858,12 @@ def test_final_step_of_a_call_in_the_pair_launch(case, monkeypatch):
         pos, box = np.asarray(g["pos"], dtype=np.float64), np.zeros(3)
         terms = ["bonds", "angles", "dihedrals", "impropers", "1-4", "electrostatics", "lj"]
         kw = dict(cutoff=9.0)
+    elif case == "light_full":  # all five bonded kinds on the light scheme, molecules across 64-atom step blocks
+        import _bonded_systems as B
+
+        s = B.light_full(B.LARGE)
+        par, pos, box, terms = s.par(dt), s.pos, s.box, B.ALL_TERMS
+        kw = dict(cutoff=9.0, rfa=True)
     elif case.startswith("water"):
         mol, pos, box = tip3p_box(14, seed=4)  # 8 232 atoms
         terms = ["lj", "electrostatics", "bonds", "angles"]
@@ -857,7 +875,7 @@ def test_final_step_of_a_call_in_the_pair_launch(case, monkeypatch):
         par = Parameters(argon_forcefield(mol), mol, terms, precision=dt)
         kw = dict(cutoff=9.0)
     gamma = None if case == "water_nve" else 1.0
-    monkeypatch.setenv("TMDHIP_LPA", "64" if case == "thrombin" else ("8" if case.startswith("water") else "4"))
+    monkeypatch.setenv("TMDHIP_LPA", "64" if case == "thrombin" else ("8" if case.startswith("water") else ("16" if case == "light_full" else "4")))
     torch.manual_seed(3)
     vel0 = maxwell_boltzmann(par.masses, 300.0, 1)
 

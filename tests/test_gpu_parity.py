@@ -1254,8 +1254,9 @@ def test_plain_evaluations_leave_the_rebuild_chain_out_and_recover(monkeypatch):
         assert torch.equal(Fa, Fc), k
 
 
-@pytest.mark.parametrize("kw", [dict(cutoff=9.0, rfa=True), dict(cutoff=9.0, rfa=True, switch_dist=7.5), dict(cutoff=8.0)],
-                         ids=["rf", "rf-switch", "coulomb"])
+@pytest.mark.parametrize("kw", [dict(cutoff=9.0, rfa=True), dict(cutoff=9.0, rfa=True, switch_dist=7.5), dict(cutoff=8.0),
+                                dict(cutoff=9.0, rfa=True, system="light-full")],
+                         ids=["rf", "rf-switch", "coulomb", "rf-light-full"])
 def test_plain_evaluation_with_the_bonded_terms_in_the_pair_launch(kw, monkeypatch):
     """`compute()` with energies on a cell-list context with a light topology (round 6, `tmdhip_compute`): the ENERGY variant of the
     lean pair launch carries evaluation-only step blocks that add the bonded force of their atoms and leave the bonded energies,
@@ -1267,9 +1268,17 @@ def test_plain_evaluation_with_the_bonded_terms_in_the_pair_launch(kw, monkeypat
     from torchmd_amd.parameters import Parameters
 
     dev = _dev()
-    mol, pos, box = tip3p_box(14, seed=31)  # 8 232 atoms
-    terms = ["lj", "electrostatics", "bonds", "angles"]
-    par = Parameters(water_forcefield(mol), mol, terms, precision=torch.float32)
+    kw = dict(kw)
+    if kw.pop("system", None) == "light-full":  # all five bonded kinds, up to 8 records per atom (tests/_bonded_systems.py)
+        import _bonded_systems as B
+
+        s = B.light_full(B.LARGE).rounded(torch.float32)
+        pos, box, terms = s.pos, s.box, B.ALL_TERMS
+        par = s.par(torch.float32)
+    else:
+        mol, pos, box = tip3p_box(14, seed=31)  # 8 232 atoms
+        terms = ["lj", "electrostatics", "bonds", "angles"]
+        par = Parameters(water_forcefield(mol), mol, terms, precision=torch.float32)
     rng = np.random.default_rng(4)
     seq = [pos, pos + rng.normal(scale=0.02, size=pos.shape), pos + rng.normal(scale=0.04, size=pos.shape)]
     b = box_tensor(box, 1, torch.float32, dev)
