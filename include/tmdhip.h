@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define TMDHIP_ABI_VERSION 8
+#define TMDHIP_ABI_VERSION 9
 
 /* dtype */
 #define TMDHIP_F32 0
@@ -140,6 +140,8 @@ typedef struct tmdhip_stats {
   int64_t final_steps_in_pair_launch; /* tmdhip_md_run calls whose LAST step (final kick, bonded + kinetic energies) was made by the
                                        * step blocks of the last pair launch (ABI 8; whole context) */
   int64_t batched_launches;     /* pair + step launches that served several replicas of a cell-list context at once (ABI 8; whole context) */
+  int64_t pme_evaluations;      /* reciprocal-space (PME) evaluations of this replica (ABI 9)                  */
+  int64_t pme_bytes;            /* device memory held by the context's PME buffers and FFT plans (ABI 9)      */
 } tmdhip_stats;
 
 int tmdhip_abi_version(void);
@@ -149,6 +151,22 @@ const char *tmdhip_last_error(void);
 int tmdhip_create(tmdhip_ctx **out, const tmdhip_nonbonded_desc *desc);
 int tmdhip_set_bonded(tmdhip_ctx *ctx, const tmdhip_bonded_desc *desc);
 void tmdhip_destroy(tmdhip_ctx *ctx);
+
+/* Smooth particle-mesh Ewald electrostatics (Essmann et al. 1995) for periodic boxes (ABI 9).  With `enable` the
+ * electrostatics term of every evaluation becomes the Ewald sum: real space erfc(beta r)/r within the cutoff (pair
+ * kernels), reciprocal space on an nx x ny x nz grid with order-`order` cardinal B-splines (pme.hip), the excluded-pair
+ * correction -k q_i q_j erf(beta r)/r, the self term -k beta/sqrt(pi) sum q^2 and the neutralising background
+ * -k pi Q^2 / (2 V beta^2).  Needs a cutoff, no reaction field, the electrostatics term, order 4..6, grid edges >= order
+ * and a non-zero box at compute time.  Creates the FFT plans (rocFFT compiles kernels here, not in the evaluations);
+ * synchronises the device.  enable = 0 releases every PME buffer.  Domain decomposition refuses PME contexts. */
+typedef struct tmdhip_pme_desc {
+  int32_t struct_size; /* = sizeof(tmdhip_pme_desc) */
+  int32_t enable;
+  double beta;         /* Ewald splitting parameter, 1/Angstrom */
+  int32_t grid[3];     /* FFT grid points per box edge */
+  int32_t order;       /* B-spline order (4..6) */
+} tmdhip_pme_desc;
+int tmdhip_set_pme(tmdhip_ctx *ctx, const tmdhip_pme_desc *desc);
 
 /* Nonbonded block of Forces.compute (forces.py:260-319) for one replica: minimum-image distances
  * (360-372), `dist <= cutoff` filter (76-81), LJ (+switch) / Coulomb / reaction field / repulsion

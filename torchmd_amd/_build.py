@@ -22,7 +22,7 @@ LIBDIR = os.path.join(PKG, "lib")
 OBJDIR = os.path.join(LIBDIR, "obj")
 LIBPATH = os.path.join(LIBDIR, "libtmdhip.so")
 SOURCES = ["context.hip", "list_build.hip", "pair_generic.hip", "pair_fast_f32.hip", "pair_fast_f32_batch.hip", "pair_lean_f64.hip", "md_loop.hip",
-           "bonded.hip", "integrator.hip", "domain.hip", "dd_migrate.hip"]
+           "bonded.hip", "integrator.hip", "domain.hip", "dd_migrate.hip", "pme.hip"]
 HEADERS = ["common.h", "pair_math.h", "rng.h", "bonded_math.h", "engine.h", "md_step.h", "pair_fast_kernel.h", "dd_comm.h",
            os.path.join("..", "..", "include", "tmdhip.h")]
 ARCH = "gfx950"
@@ -34,6 +34,16 @@ def _hipcc():
         if cand and os.path.exists(cand):
             return cand
     raise RuntimeError("hipcc not found (set HIPCC or install ROCm)")
+
+
+def _fft_link_flags(hipcc):
+    """hipFFT (PME, pme.hip) from the ROCm installation hipcc belongs to, found at run time through an rpath.  (A process
+    that has imported torch first already holds torch's own copy under the same soname; the loader then reuses it.)"""
+    rocm = os.path.dirname(os.path.dirname(os.path.realpath(hipcc)))
+    libdir = os.path.join(rocm, "lib")
+    if not os.path.exists(os.path.join(libdir, "libhipfft.so")):
+        libdir = "/opt/rocm/lib"
+    return [f"-L{libdir}", "-lhipfft", f"-Wl,-rpath,{libdir}"]
 
 
 def _newest_header() -> float:
@@ -86,7 +96,7 @@ def build_library(force: bool = False, verbose: bool = False, extra_flags=(), ou
                 warn = f.result()
                 if verbose and warn.strip():
                     print(warn, file=sys.stderr)
-    cmd = [hipcc, f"--offload-arch={ARCH}", "-fPIC", "-shared", *objs, "-o", target + ".tmp"]
+    cmd = [hipcc, f"--offload-arch={ARCH}", "-fPIC", "-shared", *objs, *_fft_link_flags(hipcc), "-o", target + ".tmp"]
     if verbose:
         print(" ".join(cmd), flush=True)
     res = subprocess.run(cmd, capture_output=True, text=True)

@@ -13,7 +13,7 @@ PKG = os.path.dirname(os.path.abspath(__file__))
 # TMDHIP_LIB: developer knob for A/B runs of differently built libraries (kernel experiments)
 LIBPATH = os.environ.get("TMDHIP_LIB") or os.path.join(PKG, "lib", "libtmdhip.so")
 
-ABI_VERSION = 8
+ABI_VERSION = 9
 F32, F64 = 0, 1
 TERM_LJ, TERM_ELECTROSTATICS, TERM_REPULSION, TERM_REPULSIONCG = 1, 2, 4, 8
 E_LJ, E_ELECTROSTATICS, E_REPULSION, E_REPULSIONCG, E_BONDS, E_ANGLES, E_DIHEDRALS, E_IMPROPERS = range(8)
@@ -202,6 +202,18 @@ class Stats(C.Structure):
         ("fused_step_timeouts", C.c_int64),
         ("final_steps_in_pair_launch", C.c_int64),
         ("batched_launches", C.c_int64),
+        ("pme_evaluations", C.c_int64),
+        ("pme_bytes", C.c_int64),
+    ]
+
+
+class PmeDesc(C.Structure):
+    _fields_ = [
+        ("struct_size", C.c_int32),
+        ("enable", C.c_int32),
+        ("beta", C.c_double),
+        ("grid", C.c_int32 * 3),
+        ("order", C.c_int32),
     ]
 
 
@@ -212,6 +224,7 @@ SIGNATURES = {
     "tmdhip_create": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(NonbondedDesc)]),
     "tmdhip_set_bonded": (C.c_int, [C.c_void_p, C.POINTER(BondedDesc)]),
     "tmdhip_destroy": (None, [C.c_void_p]),
+    "tmdhip_set_pme": (C.c_int, [C.c_void_p, C.POINTER(PmeDesc)]),
     "tmdhip_compute_nonbonded": (
         C.c_int,
         [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_double), C.c_void_p, C.c_void_p, C.c_int, C.c_void_p],

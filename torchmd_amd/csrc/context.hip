@@ -577,6 +577,7 @@ void tmdhip_destroy(tmdhip_ctx *ctx) {
   ctx->sync_e.release();
   ctx->obs_ke.release();
   tmd::bonded_release(ctx);
+  tmd::pme_release(ctx);
   delete ctx;
 }
 
@@ -594,9 +595,14 @@ int tmdhip_compute_nonbonded(tmdhip_ctx *ctx, int replica, const void *pos_dev, 
     const size_t esz = ctx->real_size, stride = (size_t)ctx->d.natoms * 3 * esz;
     if (nrep > 1 && ctx->algorithm == TMDHIP_ALGO_ALLPAIRS && !(flags & TMDHIP_COUNT_PAIRS)) {
       for (auto &rp : ctx->rep) rp.n_compute++;
-      return ctx->d.dtype == TMDHIP_F32
-                 ? launch_allpairs<float>(ctx, pos_dev, box_host, forces_dev, energies_dev, flags, nullptr, st, nrep)
-                 : launch_allpairs<double>(ctx, pos_dev, box_host, forces_dev, energies_dev, flags, nullptr, st, nrep);
+      TMD_TRY(ctx->d.dtype == TMDHIP_F32
+                  ? launch_allpairs<float>(ctx, pos_dev, box_host, forces_dev, energies_dev, flags, nullptr, st, nrep)
+                  : launch_allpairs<double>(ctx, pos_dev, box_host, forces_dev, energies_dev, flags, nullptr, st, nrep));
+      for (int r = 0; r < nrep && ctx->pme; ++r)  // reciprocal-space part of every replica (pme.hip)
+        TMD_TRY(pme_hook(ctx, r, (const char *)pos_dev + r * stride, box_host + 3 * r,
+                         forces_dev ? (char *)forces_dev + r * stride : nullptr,
+                         energies_dev ? energies_dev + (size_t)r * TMDHIP_NENERGY : nullptr, flags, st));
+      return 0;
     }
     for (int r = 0; r < nrep; ++r)  // (a cell-list context may fall back to all pairs on the way: still correct)
       TMD_TRY(tmdhip_compute_nonbonded(ctx, r, (const char *)pos_dev + r * stride, box_host + 3 * r,
@@ -611,7 +617,7 @@ int tmdhip_compute_nonbonded(tmdhip_ctx *ctx, int replica, const void *pos_dev, 
   if (ctx->algorithm == TMDHIP_ALGO_CELLLIST) {
     const int rc = f32 ? compute_list<float>(ctx, rp, pos_dev, box_host, forces_dev, energies_dev, flags, st)
                        : compute_list<double>(ctx, rp, pos_dev, box_host, forces_dev, energies_dev, flags, st);
-    if (rc != kFallbackAllPairs) return rc;
+    if (rc != kFallbackAllPairs) return rc ? rc : pme_hook(ctx, replica, pos_dev, box_host, forces_dev, energies_dev, flags, st);
     ctx->algorithm = TMDHIP_ALGO_ALLPAIRS;  // AUTO and the box holds fewer than 3 cells per edge
   }
   unsigned long long *pc = nullptr;
@@ -619,8 +625,9 @@ int tmdhip_compute_nonbonded(tmdhip_ctx *ctx, int replica, const void *pos_dev, 
     pc = rp.paircount.as<unsigned long long>();
     TMD_HIP(hipMemsetAsync(pc, 0, sizeof(unsigned long long), st));
   }
-  return f32 ? launch_allpairs<float>(ctx, pos_dev, box_host, forces_dev, energies_dev, flags, pc, st)
-             : launch_allpairs<double>(ctx, pos_dev, box_host, forces_dev, energies_dev, flags, pc, st);
+  TMD_TRY(f32 ? launch_allpairs<float>(ctx, pos_dev, box_host, forces_dev, energies_dev, flags, pc, st)
+              : launch_allpairs<double>(ctx, pos_dev, box_host, forces_dev, energies_dev, flags, pc, st));
+  return pme_hook(ctx, replica, pos_dev, box_host, forces_dev, energies_dev, flags, st);
 }
 
 int tmdhip_update_atoms(tmdhip_ctx *ctx, int natoms, const int32_t *types_host, const void *charges_host,
@@ -628,6 +635,7 @@ int tmdhip_update_atoms(tmdhip_ctx *ctx, int natoms, const int32_t *types_host, 
   if (!ctx || !types_host) return fail("tmdhip_update_atoms: null argument");
   if (natoms <= 0 || natoms >= (1 << 23)) return fail("tmdhip_update_atoms: natoms out of range");
   if (ctx->nexcl != 0 || ctx->bonded) return fail("tmdhip_update_atoms: only for atomic systems (no exclusions, no bonded terms)");
+  if (ctx->pme) return fail("tmdhip_update_atoms: not for PME contexts (the self and background terms hold the charges)");
   if ((ctx->d.terms & TMDHIP_TERM_ELECTROSTATICS) && !charges_host)
     return fail("tmdhip_update_atoms: electrostatics needs charges");
   for (int i = 0; i < natoms; ++i)
@@ -739,6 +747,8 @@ int tmdhip_get_stats(tmdhip_ctx *ctx, int replica, tmdhip_stats *out) {
   out->fused_step_timeouts = ctx->fused_step_timeouts;
   out->final_steps_in_pair_launch = ctx->final_steps_in_pair_launch;
   out->batched_launches = ctx->batched_launches;
+  out->pme_evaluations = pme_evaluations(ctx, replica);
+  out->pme_bytes = pme_bytes(ctx);
   out->pairs_in_cutoff = (int64_t)pc;
   out->algorithm = ctx->algorithm;
   out->max_neighbours = rp.lg.maxn;

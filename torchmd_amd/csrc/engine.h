@@ -621,6 +621,9 @@ struct tmdhip_ctx {
   std::vector<tmd::Replica> rep;
   // bonded part lives in bonded.hip
   void *bonded = nullptr;
+  // smooth PME (tmdhip_set_pme), pme.hip; null: off (no PME buffer, no PME launch)
+  void *pme = nullptr;
+  double pme_beta = 0;
   // timing of the dominant kernel
   bool timing = false;
   int timing_stride = 1;    // every n-th launch is timed
@@ -672,6 +675,8 @@ PairConsts<R> make_consts(const tmdhip_ctx *ctx, const double *box) {
   } else {
     c.krf = c.crf = 0;
   }
+  c.ewald = ctx->pme ? 1 : 0;
+  c.beta = (R)ctx->pme_beta;
   return c;
 }
 
@@ -775,6 +780,17 @@ int launch_pair_lean_f64(tmdhip_ctx *ctx, Replica &rp, const PairConsts<double> 
 void fused_grid_shape(const tmdhip_ctx *ctx, const Replica &rp, int bonded, int &pair_blocks, int &step_blocks);
 int launch_pair_fast_f32_batch(tmdhip_ctx *ctx, int rep0, const PairConsts<float> &c, const BatchLaunch &bl, int lpa, bool energy,
                                bool langevin, hipStream_t st);
+// pme.hip: the reciprocal-space part, excluded-pair correction, self and background terms of replica `r` — adds into
+// `forces` (null: none) and energies[TMDHIP_E_ELECTROSTATICS] (null: none), stream-ordered behind the pair launch.  No-op
+// unless the context has PME on.
+template <typename R>
+int pme_apply(tmdhip_ctx *ctx, int r, const R *pos, const double *box, R *forces, double *energies, hipStream_t st);
+// the same for an entry point's flags and untyped buffers: forces only with TMDHIP_WANT_FORCES, energies only with
+// TMDHIP_WANT_ENERGY
+int pme_hook(tmdhip_ctx *ctx, int r, const void *pos, const double *box, void *forces, double *energies, int flags, hipStream_t st);
+void pme_release(tmdhip_ctx *ctx);
+int64_t pme_evaluations(const tmdhip_ctx *ctx, int r);
+int64_t pme_bytes(const tmdhip_ctx *ctx);
 // md_loop.hip
 template <typename R>
 int md_run(tmdhip_ctx *ctx, const tmdhip_md_desc *d, hipStream_t st);

@@ -288,6 +288,7 @@ bool fused_step_possible(const tmdhip_ctx *ctx, const Replica &rp, const PairCon
   const char *e = std::getenv("TMDHIP_FUSED_STEP");  // (read per call: tests switch it within a process)
   if (e && std::atoi(e) == 0) return false;
   if (ctx->fused_off_call || ctx->fused_disabled) return false;  // repetition of a batch whose fused launch timed out
+  if (ctx->pme) return false;  // PME: generic real-space kernel + the reciprocal-space launches (pme.hip) after it
   const bool only_lj_el = c.terms != 0 && (c.terms & ~(TMDHIP_TERM_LJ | TMDHIP_TERM_ELECTROSTATICS)) == 0;
   return only_lj_el && ctx->d.ntypes <= kEntryTypes && rp.lg.lpa >= 4 && rp.lg.lpa <= 64 && kFastThreads / rp.lg.lpa <= 64;
 }
@@ -305,7 +306,7 @@ int compute_fused_eval(tmdhip_ctx *ctx, const void *pos_dev, const double *box, 
   const char *e_on = std::getenv("TMDHIP_FUSED_EVAL");  // (0: the separate kernels; A/B, tests)
   if (e_on && std::atoi(e_on) == 0) return 0;
   if (ctx->d.dtype != TMDHIP_F32 || ctx->algorithm != TMDHIP_ALGO_CELLLIST || ctx->rep.size() != 1 || !forces_dev || ctx->d.terms == 0 ||
-      ctx->no_fused_once)
+      ctx->no_fused_once || ctx->pme)
     return 0;
   Replica &rp = ctx->rep[0];
   const PairConsts<float> c = make_consts<float>(ctx, box);
@@ -370,6 +371,7 @@ static int batch_replicas_min() {
 static int launch_replica_batch(tmdhip_ctx *ctx, std::vector<BatchItem> &items, int bonded, uint64_t noise_step, bool energy,
                                 bool langevin, hipStream_t st) {
   const int nrep = (int)items.size(), n = ctx->d.natoms;
+  if (ctx->pme) return fail("batched pair + step launch: not for PME contexts");
   TMD_TRY(ctx->batch_tab.ensure(sizeof(BatchRep) * (size_t)nrep));
   if ((int)ctx->batch_host.size() != nrep) {
     ctx->batch_host.assign(nrep, BatchRep{});
@@ -568,6 +570,9 @@ int md_run(tmdhip_ctx *ctx, const tmdhip_md_desc *d, hipStream_t st) {
         const bool ride = bmode == 2 && (size_t)n * nrep <= kRideMaxAtoms;
         TMD_TRY(launch_allpairs<R>(ctx, pos, d->box_host, f, en, flags_c | TMDHIP_OVERWRITE_FORCES | kForcesZeroed,
                                    nullptr, st, nrep, ride ? &A : nullptr));
+        for (int r = 0; r < nrep && ctx->pme; ++r)  // reciprocal-space part of every replica (pme.hip)
+          TMD_TRY(pme_hook(ctx, r, pos + r * stride, d->box_host + 3 * r, f + r * stride, en ? en + (size_t)r * TMDHIP_NENERGY : nullptr,
+                           flags_c, st));
         bonded_done = bonded_done || ride;
       } else {
         TMD_HIP(hipMemsetAsync(f, 0, sizeof(R) * stride * nrep, st));
@@ -851,6 +856,8 @@ int md_run(tmdhip_ctx *ctx, const tmdhip_md_desc *d, hipStream_t st) {
             list = false;
           } else if (rc != 0) {
             return rc;
+          } else {
+            TMD_TRY(pme_hook(ctx, r, pos, box, f, en, flags_c, st));
           }
         }
         if (!list) {
@@ -859,6 +866,7 @@ int md_run(tmdhip_ctx *ctx, const tmdhip_md_desc *d, hipStream_t st) {
           TMD_TRY(launch_allpairs<R>(ctx, pos, box, f, en,
                                      flags_c | TMDHIP_OVERWRITE_FORCES | (zeroed ? kForcesZeroed : 0), nullptr, st, 1,
                                      ride ? &A : nullptr));
+          TMD_TRY(pme_hook(ctx, r, pos, box, f, en, flags_c, st));
           if (ride) continue;  // forces (and energies) of this step are complete
         }
       } else {

@@ -379,7 +379,8 @@ int launch_list_pair(tmdhip_ctx *ctx, Replica &rp, const PairConsts<R> &c, R *f,
   // the lean fp32 kernel covers LJ (with or without switching) and/or electrostatics (reaction field or plain Coulomb)
   const bool only_lj_el = c.terms != 0 && (c.terms & ~(TMDHIP_TERM_LJ | TMDHIP_TERM_ELECTROSTATICS)) == 0;
   const bool fast = only_lj_el;  // (switching, if any, acts on the LJ term and is a kernel variant)
-  const bool lean = fast && !paircount && ctx->d.ntypes <= kEntryTypes;  // (the entry's type field holds 32 LJ classes)
+  // (PME contexts: the lean kernels have no real-space Ewald term, the generic kernel serves them)
+  const bool lean = fast && !paircount && ctx->d.ntypes <= kEntryTypes && !c.ewald;  // (the entry's type field holds 32 LJ classes)
   if constexpr (std::is_same<R, float>::value) {
     if (lean && (f || ENERGY || fl)) {  // lean fp32 kernel (n > 2^20: every iteration in its checked loop)
       TMD_TRY(launch_pair_fast_f32<ENERGY>(ctx, rp, c, f, overwrite, st, e0, e1, lmode, fl));
@@ -402,7 +403,7 @@ int launch_list_pair(tmdhip_ctx *ctx, Replica &rp, const PairConsts<R> &c, R *f,
                      overwrite, ctx->escratch.as<double>(), paircount, rp.pub_ptr, rp.pub_val)
   // the generic kernel's branch-free FAST=1 body hard-codes LJ + electrostatics (krf = 0: plain Coulomb)
   const bool fast_generic =
-      fast && !c.switch_on && !ENERGY && c.terms == (TMDHIP_TERM_LJ | TMDHIP_TERM_ELECTROSTATICS);
+      fast && !c.switch_on && !ENERGY && !c.ewald && c.terms == (TMDHIP_TERM_LJ | TMDHIP_TERM_ELECTROSTATICS);
 #define TMD_LAUNCH_LPA(L)     \
   if (fast_generic) {         \
     TMD_LAUNCH(L, 1);         \

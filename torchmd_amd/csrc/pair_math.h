@@ -35,6 +35,10 @@ struct PairConsts {
   int32_t switch_on;
   int32_t switch_reference_mode;
   int32_t rfa;
+  // smooth PME (tmdhip_set_pme): the electrostatics term is the real-space Ewald part erfc(beta r)/r (appended after the
+  // fields the lean kernels read; they never serve a PME context)
+  int32_t ewald;
+  R beta;
 };
 
 __device__ __forceinline__ float round_half_even(float x) { return rintf(x); }
@@ -102,6 +106,11 @@ __device__ __forceinline__ R pair_terms(const PairConsts<R> &c, R r2, R qq, R A,
     if (c.rfa) {
       dEdr += qq * (R(2) * c.krf * r - rinv2);
       if (ENERGY) e[1] += qq * (rinv + c.krf * r2 - c.crf);
+    } else if (c.ewald) {  // real-space Ewald: E = qq erfc(beta r)/r, dE/dr = -qq (erfc(beta r)/r^2 + 2 beta/sqrt(pi) e^(-beta^2 r^2)/r)
+      const R br = c.beta * r;
+      const R eel = qq * erfc(br) * rinv;
+      dEdr -= (eel + qq * R(1.1283791670955126) * c.beta * exp(-br * br)) * rinv;
+      if (ENERGY) e[1] += eel;
     } else {
       const R eel = qq * rinv;
       dEdr -= eel * rinv;

@@ -603,6 +603,8 @@ class DomainSet:
 
     def __init__(self, box, world, device, dtype, terms, cutoff, A=None, B=None, skin=1.5, grid=None, transport=None,
                  dry=False, **engine_kwargs):
+        if engine_kwargs.get("pme"):
+            raise ValueError("PME electrostatics cannot be domain-decomposed (no distributed FFT)")
         self.dry = bool(dry)  # CPU tensors, no force engine (DryDomain): the plumbing of an N-rank run without a GPU
         self.grid = BrickGrid(box, world, grid)
         self.device, self.dtype = torch.device(device), dtype

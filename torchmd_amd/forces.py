@@ -128,6 +128,14 @@ class _Engine:
         d.algorithm = {"auto": L.ALGO_AUTO, "allpairs": L.ALGO_ALLPAIRS, "celllist": L.ALGO_CELLLIST}[owner.algorithm]
         d.skin = float(owner.skin) if owner.skin else 0.0
         L.check(lib.tmdhip_create(C.byref(self.ctx), C.byref(d)), "tmdhip_create")
+        if owner.pme:
+            pd = L.PmeDesc()
+            pd.struct_size = C.sizeof(L.PmeDesc)
+            pd.enable = 1
+            pd.beta = owner.ewald_beta
+            pd.grid[:] = owner.pme_grid
+            pd.order = owner.pme_order
+            L.check(lib.tmdhip_set_pme(self.ctx, C.byref(pd)), "tmdhip_set_pme")
 
         b = L.BondedDesc()
         b.struct_size = C.sizeof(L.BondedDesc)
@@ -242,6 +250,14 @@ class Forces:
                           at least 0.2 (measured on flexible TIP3P: the oxygens' largest displacement is 0.28 of
                           the hydrogens'); systems with a single mass keep the uniform skin.
     algorithm : str       "auto" | "allpairs" | "celllist"
+    pme : bool            smooth particle-mesh Ewald for the "electrostatics" term (periodic boxes; needs a cutoff, no
+                          `rfa`): real space erfc(beta r)/r within the cutoff, reciprocal space on an FFT grid, the
+                          excluded-pair correction -k q_i q_j erf(beta r)/r (1-4 pairs included; their scaled Coulomb
+                          term in "1-4" is unchanged), the self term and the neutralising background
+    ewald_tolerance       delta: beta = sqrt(-ln(2 delta)) / cutoff; grid per edge ceil(2 beta L / (3 delta^(1/5)))
+                          rounded up to a 2^a 3^b 5^c 7^d size (OpenMM's rules; L = the first box the forces see)
+    pme_order : int       B-spline order, 4 .. 6
+    pme_grid              (nx, ny, nz) overrides the grid
     switch_mode : str     "reference" (upstream's explicit switching force, extra 1/r,
                           forces.py:410-412) | "exact" (-dE/dr)
     """
@@ -265,6 +281,10 @@ class Forces:
         skin_weights="mass",
         algorithm="auto",
         switch_mode="reference",
+        pme=False,
+        ewald_tolerance=5e-4,
+        pme_order=5,
+        pme_grid=None,
     ):
         self.par = parameters
         if terms is None:
@@ -295,6 +315,29 @@ class Forces:
             raise ValueError("switch_dist must be positive (use None for no switching)")
         if switch_dist is not None and cutoff is not None and not switch_dist < cutoff:
             raise ValueError("switch_dist must be smaller than cutoff")
+
+        self.pme = bool(pme)
+        self.ewald_beta = None
+        self.pme_order = int(pme_order)
+        self.pme_grid = None
+        if self.pme:
+            if rfa:
+                raise ValueError("pme=True excludes rfa=True")
+            if cutoff is None:
+                raise ValueError("pme=True needs a cutoff")
+            if "electrostatics" not in self.energies:
+                raise ValueError("pme=True needs the 'electrostatics' term")
+            if not 4 <= self.pme_order <= 6 or self.pme_order != pme_order:
+                raise ValueError("pme_order must be 4, 5 or 6")
+            if not 0 < ewald_tolerance < 0.5:
+                raise ValueError("ewald_tolerance must lie in (0, 0.5)")
+            self.ewald_beta = float(np.sqrt(-np.log(2.0 * ewald_tolerance)) / cutoff)
+            self.ewald_tolerance = float(ewald_tolerance)
+            if pme_grid is not None:
+                g = tuple(int(v) for v in pme_grid)
+                if len(g) != 3 or min(g) < self.pme_order:
+                    raise ValueError("pme_grid must be three sizes, each at least pme_order")
+                self.pme_grid = g
 
         self.natoms = len(parameters.masses)
         self.require_distances = any(f in self.nonbonded for f in self.energies)
@@ -399,6 +442,17 @@ class Forces:
             A, B = self.par.get_AB()
         return A, B
 
+    # ------------------------------------------------------------------ PME
+    def _pme_box(self, hbox):
+        """PME needs a periodic box; the first one the forces see fixes the grid unless `pme_grid` was given."""
+        if not self.pme:
+            return
+        hb = np.asarray(hbox, dtype=np.float64).reshape(-1, 3)
+        if not (hb > 0).all():
+            raise ValueError("pme=True needs a periodic box: every box edge must be positive")
+        if self.pme_grid is None:
+            self.pme_grid = tuple(pme_grid_size(self.ewald_beta, float(hb[:, d].max()), self.ewald_tolerance) for d in range(3))
+
     # ------------------------------------------------------------------ engine plumbing
     def _engine(self, pos, exact=None):
         """`exact` selects the switching-force flavour: the explicit path keeps upstream's formula,
@@ -488,6 +542,7 @@ class Forces:
                 raise RuntimeError("forces must have the dtype and shape of pos")
             if not forces.is_contiguous():
                 target, forces = forces, torch.empty_like(p)
+        self._pme_box(self._host_box(box))
         eng = self._engine(p, exact)
         with torch.cuda.device(p.device):
             for _ in range(4):
@@ -518,8 +573,9 @@ class Forces:
                 raise RuntimeError("forces must have the dtype and shape of pos")
             if not forces.is_contiguous():
                 target, forces = forces, torch.empty_like(p)
-        eng = self._engine(p, exact)
         hbox = self._host_box(box)
+        self._pme_box(hbox)
+        eng = self._engine(p, exact)
         R = p.shape[0]
         boxes = hbox if len(hbox) == R else np.ascontiguousarray(np.stack([hbox[min(r, len(hbox) - 1)] for r in range(R)]))
         out = np.empty((R, L.NENERGY), dtype=np.float64)
@@ -656,8 +712,9 @@ class Forces:
         L.require_device_tensor(pos, "systems.pos")
         if pos.shape[1] != self.natoms:
             raise RuntimeError(f"systems.pos must have {self.natoms} atoms")
-        eng = self._engine(pos)
         hbox = self._host_box(system.box)
+        self._pme_box(hbox)
+        eng = self._engine(pos)
         R = pos.shape[0]
         # the descriptor and the per-replica box array are kept between calls (a 20-step call is short enough for
         # the Python in front of its first launch to show)
@@ -729,6 +786,8 @@ class Forces:
             "chains_skipped": int(st.chains_skipped),
             "steps_in_pair_launch": int(st.steps_in_pair_launch),
             "fused_step_timeouts": int(st.fused_step_timeouts),
+            "pme_evaluations": int(st.pme_evaluations),
+            "pme_bytes": int(st.pme_bytes),
         }
 
     def enable_timing(self, pos, on=True, every=1, limit=0, skip=0, interior_only=False):
@@ -748,6 +807,24 @@ class Forces:
         ms, n = C.c_double(), C.c_int64()
         L.check(eng.lib.tmdhip_timing_read(eng.ctx, C.byref(ms), C.byref(n), 1 if reset else 0))
         return ms.value, n.value
+
+
+def _fft_size(n):
+    """Smallest 2^a 3^b 5^c 7^d >= n."""
+    n = max(int(n), 1)
+    while True:
+        m = n
+        for p in (2, 3, 5, 7):
+            while m % p == 0:
+                m //= p
+        if m == 1:
+            return n
+        n += 1
+
+
+def pme_grid_size(beta, box_edge, tolerance):
+    """OpenMM's PME grid rule: ceil(2 beta L / (3 delta^(1/5))) points per edge, rounded up to an FFT-friendly size."""
+    return _fft_size(int(np.ceil(2.0 * beta * box_edge / (3.0 * tolerance ** 0.2))))
 
 
 def _is_batched(t) -> bool:

@@ -39,7 +39,7 @@ DEFAULTS = dict(
     structure=None, topology=None, coordinates=None, forcefield=None, seed=1, output_period=10,
     save_period=0, steps=10000, log_dir="./", output="output", forceterms=["LJ"], cutoff=None,
     switch_dist=None, precision="single", external=None, rfa=False, replicas=1, extended_system=None,
-    minimize=None, exclusions=("bonds", "angles", "1-4"),
+    minimize=None, exclusions=("bonds", "angles", "1-4"), pme=False, ewald_tolerance=5e-4, pme_order=5, pme_grid=None,
 )
 
 
@@ -52,7 +52,7 @@ def get_args(arguments=None):
             ap.add_argument(opt, dest=key, action="store_true", default=None)
         elif key in ("forceterms", "structure"):
             ap.add_argument(opt, dest=key, nargs="+", default=None)
-        elif key in ("external", "exclusions"):
+        elif key in ("external", "exclusions", "pme_grid"):
             continue
         else:
             ap.add_argument(opt, dest=key, default=None, type=type(val) if val is not None else str)
@@ -66,7 +66,11 @@ def get_args(arguments=None):
     for k in ("cutoff", "switch_dist", "timestep", "temperature", "langevin_temperature", "langevin_gamma"):
         if getattr(args, k) is not None:
             setattr(args, k, float(getattr(args, k)))
-    for k in ("steps", "output_period", "save_period", "replicas", "seed"):
+    args.ewald_tolerance = float(args.ewald_tolerance)
+    args.pme = bool(args.pme)
+    if args.pme_grid is not None:
+        args.pme_grid = tuple(int(v) for v in args.pme_grid)
+    for k in ("steps", "output_period", "save_period", "replicas", "seed", "pme_order"):
         setattr(args, k, int(getattr(args, k)))
     if isinstance(args.forceterms, str):
         args.forceterms = [args.forceterms]
@@ -166,7 +170,8 @@ def setup(args):
     system.set_box(mol.box)
     system.set_velocities(maxwell_boltzmann(parameters.masses, args.temperature, args.replicas))
     forces = Forces(parameters, terms=terms, external=external, cutoff=args.cutoff, rfa=args.rfa,
-                    switch_dist=args.switch_dist, exclusions=tuple(args.exclusions))
+                    switch_dist=args.switch_dist, exclusions=tuple(args.exclusions), pme=args.pme,
+                    ewald_tolerance=args.ewald_tolerance, pme_order=args.pme_order, pme_grid=args.pme_grid)
     return mol, system, forces
 
 
