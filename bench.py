@@ -1,14 +1,19 @@
 #!/usr/bin/env python
-"""Headline benchmark: ns/day (+ pair-interactions/s) of the 100k-atom TIP3P water box (config C3 of
-BASELINE.json / SURVEY.md §8) on N MI355X, one independent replica per GPU (config C4, weak scaling).
+"""Headline benchmark: ns/day of the 100k-atom TIP3P water box (config C3 of BASELINE.json / SURVEY.md §8)
+on N MI355X, one independent replica per GPU (config C4, weak scaling).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
            --master-port P bench.py --gpus N --steps K --warmup W
 
 One "step" = one MD time step of the whole hot path: first velocity-Verlet half step, bonded +
 nonbonded forces (incl. the amortised cell/Verlet-list rebuilds), Langevin kick + second half step.
 State is resident in HBM before the timed region.  Rank 0 prints ONE JSON line.
+
+A plain run does only what the headline needs: set-up, warm-up, the K timed steps, the outputs of
+--dump-outputs and the line.  --full adds everything else the line can carry, each measured behind
+the timed region: the pair count (pair-interactions/s), the pass that times the dominant kernel and
+its roofline, the secondary legs on one GPU (switched C3, C5) and the CPU baselines.
 """
 
 import argparse
@@ -260,10 +265,11 @@ def dry_run_c5(args, rank, world):
 C5_TRAFFIC_FILES = ("r06_c5_pmc_traffic.json", "r05_a_c5_pmc_traffic.json", "r04_c_c5_pmc_traffic.json", "r04_b_c5_pmc_traffic.json", "r04_c5_pmc_traffic.json", "r03_d_c5_pmc_traffic.json", "r03_c5_pmc_traffic.json")  # newest committed PMC pass first
 
 
-def c5_single_gpu(args, device, cpu_budget_s=15.0, steps=None, warmup=None, defer_cpu=False):
+def c5_single_gpu(args, device, cpu_budget_s=15.0, steps=None, warmup=None, defer_cpu=False, full=True):
     """Config C5 on ONE GPU: the whole 10^6-atom argon box on the single-domain engine.  Returns the fields of a bench
-    line (value, ms_per_step, roofline, cpu_baseline, ...): `--config c5 --gpus 1` prints them as its line, the default
-    run embeds them as `secondary.c5`."""
+    line (value, ms_per_step, roofline, cpu_baseline, ...): `--config c5 --gpus 1` prints them as its line, a --full run
+    of C3 embeds them as `secondary.c5`.  full=False: the timed steps and what they report, no pair count, kernel
+    timing pass, roofline or CPU baseline."""
     from torchmd_amd.builders import argon_forcefield, lj_box
     from torchmd_amd.forces import Forces
     from torchmd_amd.integrator import Integrator, maxwell_boltzmann
@@ -295,6 +301,18 @@ def c5_single_gpu(args, device, cpu_budget_s=15.0, steps=None, warmup=None, defe
     elapsed = time.perf_counter() - t0
     st1 = f.stats(s.pos)
     replays = integ.replays - replays0
+    lst = {"rebuilds_in_timed_region": int(st1["n_rebuilds"] - st0["n_rebuilds"]),
+           "rebuild_chains_left_out": int(st1["chains_skipped"] - st0["chains_skipped"]),
+           "batches_rewound_and_repeated": int(replays),
+           "entries": int(st1["list_entries"]), "ncell": list(st1["ncell"]), "skin": st1["skin"]}
+    if not full:
+        out = {"value": ns_per_day(steps, elapsed), "unit": "ns/day", "steps": steps, "warmup": warmup,
+               "ms_per_step": elapsed / steps * 1e3, "dtype": "f32", "natoms": natoms, "box": [float(x) for x in box],
+               "list": lst, "temperature_K": [float(temp[0])]}
+        f.close()
+        del s, f, integ
+        torch.cuda.empty_cache()
+        return out
     pair_ms, pair_launches = time_pair_launches(f, integ, s)
     pcut = f.count_pairs(s.pos, s.box)[0]
     # (as in the C3 line: the timed launches also make the MD step -> SURVEY 8(d)'s whole-step bytes)
@@ -326,10 +344,7 @@ def c5_single_gpu(args, device, cpu_budget_s=15.0, steps=None, warmup=None, defe
             "alu": {"flops_per_launch": 30.0 * pcut, "achieved_tflops": 30.0 * pcut / pair_avg_s / 1e12 if pair_avg_s > 0 else 0.0,
                     "peak": FP32_VECTOR_PEAK_TFLOPS, "unit": "TFLOP/s", "note": "~30 FLOP per LJ-only pair"},
         },
-        "list": {"rebuilds_in_timed_region": int(st1["n_rebuilds"] - st0["n_rebuilds"]),
-                 "rebuild_chains_left_out": int(st1["chains_skipped"] - st0["chains_skipped"]),
-                 "batches_rewound_and_repeated": int(replays),
-                 "entries": int(st1["list_entries"]), "ncell": list(st1["ncell"]), "skin": st1["skin"]},
+        "list": lst,
         "temperature_K": [float(temp[0])],
     }
     if not args.no_cpu_baseline and not defer_cpu:  # (defer_cpu: the caller runs the CPU legs behind all GPU legs)
@@ -357,8 +372,8 @@ def run_c5(args, rank, world, local_rank, device, launched):
     fan = ReplicaFanout(total_replicas=world, device=device)
     extra = {}
     if world == 1:
-        r = c5_single_gpu(args, device)
-        natoms, box, elapsed, pcut = r["natoms"], r["box"], r["ms_per_step"] * 1e-3 * args.steps, r["pairs_in_cutoff"]
+        r = c5_single_gpu(args, device, full=args.full)
+        natoms, box, elapsed, pcut = r["natoms"], r["box"], r["ms_per_step"] * 1e-3 * args.steps, r.get("pairs_in_cutoff")
         extra = {k: r[k] for k in ("roofline", "list", "temperature_K", "cpu_baseline") if k in r}
     else:
         from torchmd_amd.builders import argon_forcefield, lj_box
@@ -572,12 +587,29 @@ def cpu_baseline(par, state, box, budget_s=20.0):
     }
 
 
-def c3_leg(forces, integ, system, natoms, steps, fan, pmc=True, switched=False, keep_outputs=False):
+def list_block(steps, st0, st1, st2, replays):
+    """`list` block of a bench line: the rebuilds of the timed region (statistics `st0` before it, `st1` behind it) and
+    the list as `st2` finds it."""
+    rebuilds = st1["n_rebuilds"] - st0["n_rebuilds"]
+    return {
+        "algorithm": st2["algorithm"],
+        "rebuilds_in_timed_region": int(rebuilds),
+        "steps_per_rebuild": (steps / rebuilds) if rebuilds else None,
+        "entries": int(st2["list_entries"]),
+        "skin": st2["skin"],
+        "rebuild_chains_left_out": int(st1["chains_skipped"] - st0["chains_skipped"]),
+        "batches_rewound_and_repeated": int(replays),  # (a list that outlived its skin in a step without a chain: the call repeats its batch)
+        "capacity_per_atom": int(st2["max_neighbours"]),
+        "ncell": list(st2["ncell"]),
+    }
+
+
+def c3_leg(forces, integ, system, natoms, steps, fan, pmc=True, switched=False, keep_outputs=False, full=True):
     """One timed leg on the water box: `integ.step(steps)` between barrier + synchronize on both sides (nothing else in
     the region: no events, no read-backs), then — outside the region — the statistics, the pass that times the dominant
     kernel (time_pair_launches) and the pair count; returns the elapsed time, the observables and the `roofline` /
     `list` blocks of a bench line.  keep_outputs: also `outputs`, what the timed call computed (timed_outputs), taken
-    before the timing pass moves the system on."""
+    before the timing pass moves the system on.  full=False: no timing pass, no pair count, no `roofline`."""
     st0 = forces.stats(system.pos)
     replays0 = integ.replays
     fan.barrier()
@@ -592,12 +624,13 @@ def c3_leg(forces, integ, system, natoms, steps, fan, pmc=True, switched=False, 
     st1 = forces.stats(system.pos)
     replays = integ.replays - replays0
     obs = fan.gather_observables(ekin, epot, temp)
+    if not full:
+        return {"elapsed": elapsed, "obs": obs, "list": list_block(steps, st0, st1, st1, replays), "outputs": outputs}
     sp0 = forces.stats(system.pos)
     pair_ms, pair_launches = time_pair_launches(forces, integ, system)
     sp1 = forces.stats(system.pos)
     pcut = forces.count_pairs(system.pos, system.box)[0]
     st2 = forces.stats(system.pos)
-    rebuilds = st1["n_rebuilds"] - st0["n_rebuilds"]
 
     # roofline of the dominant kernel.  Algorithmic bytes of the pair part per launch = 4 B per unique in-cutoff pair
     # (one int32 neighbour index) + 28 B per atom (16 B xyzq read, 12 B force write); since round 3 the timed
@@ -652,18 +685,8 @@ def c3_leg(forces, integ, system, natoms, steps, fan, pmc=True, switched=False, 
                 "unit": "TFLOP/s", "frac": alu_tflops / FP32_VECTOR_PEAK_TFLOPS},
         "valu_issue": valu_issue,
     }
-    lst = {
-        "algorithm": st2["algorithm"],
-        "rebuilds_in_timed_region": int(rebuilds),
-        "steps_per_rebuild": (steps / rebuilds) if rebuilds else None,
-        "entries": int(st2["list_entries"]),
-        "skin": st2["skin"],
-        "rebuild_chains_left_out": int(st1["chains_skipped"] - st0["chains_skipped"]),
-        "batches_rewound_and_repeated": int(replays),  # (a list that outlived its skin in a step without a chain: the call repeats its batch)
-        "capacity_per_atom": int(st2["max_neighbours"]),
-        "ncell": list(st2["ncell"]),
-    }
-    return {"elapsed": elapsed, "obs": obs, "pairs_in_cutoff": pcut, "roofline": roofline, "list": lst, "outputs": outputs}
+    return {"elapsed": elapsed, "obs": obs, "pairs_in_cutoff": pcut, "roofline": roofline,
+            "list": list_block(steps, st0, st1, st2, replays), "outputs": outputs}
 
 
 def main():
@@ -673,14 +696,17 @@ def main():
     ap.add_argument("--warmup", type=int, default=200)
     ap.add_argument("--nside", type=int, default=32, help="molecules per box edge (32 -> 98 304 atoms)")
     ap.add_argument("--relax-steps", type=int, default=1500)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the secondary legs of the default run (switched C3, C5)")
+    ap.add_argument("--full", action="store_true",
+                    help="beyond the headline: the pair count, the timing pass and roofline of the dominant kernel, the "
+                    "secondary legs (switched C3, C5) and the CPU baselines; a plain run only times the steps")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
+    ap.add_argument("--no-secondary", action="store_true", help="with --full: skip the secondary legs (switched C3, C5)")
     ap.add_argument("--skin", type=float, default=None, help="Verlet skin in A (default: the library's)")
     ap.add_argument("--skin-weights", default="mass", choices=["mass", "none"],
                     help="per-atom Verlet skins by mass (default) or one skin for every atom")
     ap.add_argument("--switch-dist", type=float, default=None,
                     help="profiling aid: run the MAIN leg with the LJ switching function from this distance (the line's "
-                    "`config.workload` says so; the default line carries the switched box as `secondary.c3_switch`)")
+                    "`config.workload` says so; a --full line carries the switched box as `secondary.c3_switch`)")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend (nccl = RCCL; gloo with --dry)")
     ap.add_argument("--dry", action="store_true", help="launcher/collective plumbing only, no GPU work (CPU test)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
@@ -738,9 +764,9 @@ def main():
         integ.step(args.warmup)
 
     leg = c3_leg(forces, integ, system, natoms, args.steps, fan, pmc=args.nside == 32, switched=args.switch_dist is not None,
-                 keep_outputs=bool(args.dump_outputs) and rank == 0)
+                 keep_outputs=bool(args.dump_outputs) and rank == 0, full=args.full)
     dumped = dump_outputs(args.dump_outputs, leg["outputs"]) if leg["outputs"] is not None else None
-    elapsed, obs, pcut = leg["elapsed"], leg["obs"], leg["pairs_in_cutoff"]
+    elapsed, obs = leg["elapsed"], leg["obs"]
     steps_per_s = args.steps / elapsed
     value = ns_per_day(args.steps, elapsed) * world
 
@@ -768,21 +794,23 @@ def main():
             "relax_steps": args.relax_steps,
         },
         "ns_per_day_per_replica": ns_per_day(args.steps, elapsed),
-        "pair_interactions_per_s": pcut * steps_per_s * world,
-        "pairs_in_cutoff": pcut,
-        "temperature_K": [float(x) for x in obs[:, 2]],
-        "epot_kcal_mol": [float(x) for x in obs[:, 1]],
-        "list": dict(leg["list"], skin_weights=args.skin_weights),
-        "roofline": leg["roofline"],
     }
+    if args.full:
+        out["pair_interactions_per_s"] = leg["pairs_in_cutoff"] * steps_per_s * world
+        out["pairs_in_cutoff"] = leg["pairs_in_cutoff"]
+    out["temperature_K"] = [float(x) for x in obs[:, 2]]
+    out["epot_kcal_mol"] = [float(x) for x in obs[:, 1]]
+    out["list"] = dict(leg["list"], skin_weights=args.skin_weights)
+    if args.full:
+        out["roofline"] = leg["roofline"]
     if dumped:
         out["outputs"] = {"dir": args.dump_outputs, "arrays": dumped[0], "atoms_sampled": dumped[1]}
     if world > 1:
         out["rccl"] = rccl_info(world, args.backend)
-    want_cpu = rank == 0 and world == 1 and not args.no_cpu_baseline
+    want_cpu = args.full and rank == 0 and world == 1 and not args.no_cpu_baseline
     cpu_state = host_state(system) if want_cpu else None  # (the CPU legs run behind every GPU leg: see cpu_baseline)
     secondary = {}
-    if rank == 0 and world == 1 and not args.no_secondary and args.switch_dist is None:
+    if args.full and rank == 0 and world == 1 and not args.no_secondary and args.switch_dist is None:
         # Secondary leg on the SAME box and state: the reference's production settings switch the LJ term from 7.5 A
         # (tests/prod_alanine_dipeptide_amber/conf.yaml:8-9, forces.py:399-413) — the SWITCH variant of the dominant launch.
         # max(--steps, 200) steps so that the window holds the list rebuilds in their steady proportion.
@@ -815,7 +843,7 @@ def main():
         except Exception as exc:  # noqa: BLE001
             secondary["c3_switch"] = {"error": f"{type(exc).__name__}: {exc}"[:500]}
     forces.close()
-    if rank == 0 and world == 1 and args.nside == 32 and not args.no_secondary:
+    if args.full and rank == 0 and world == 1 and args.nside == 32 and not args.no_secondary:
         # Secondary configuration in the same line (headline keys untouched): BASELINE.json's config 5 on this one GPU —
         # the 10^6-atom argon box on the single-domain engine, max(--steps, 200) steps.  A failure is recorded, not raised.
         del system, forces, integ
