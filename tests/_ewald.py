@@ -186,13 +186,42 @@ def pme_reciprocal(pos, q, box, beta, grid, order):
     return E, F
 
 
-def real_space(pos, q, box, beta, cutoff, excl=None, chunk=1024):
-    """erfc(beta r)/r over the non-excluded pairs within the cutoff (minimum image)."""
+def _real_space_kdtree(pos, q, box, beta, cutoff, exkeys):
+    """real_space over the pairs a periodic k-d tree finds (O(N) memory; for systems of 10^5 atoms)."""
+    from scipy.spatial import cKDTree
+
+    n = len(q)
+    wrapped = pos - box * np.floor(pos / box)
+    wrapped[wrapped >= box] = 0.0  # (x - L floor(x / L) may round up to L)
+    # a slightly wider search, then the dense path's own test r^2 <= cutoff^2 on the minimum-image difference
+    pairs = cKDTree(wrapped, boxsize=box).query_pairs(cutoff * (1 + 1e-9), output_type="ndarray")
+    gi, gj = np.minimum(pairs[:, 0], pairs[:, 1]), np.maximum(pairs[:, 0], pairs[:, 1])
+    dd = _min_image(pos[gi] - pos[gj], box)
+    r2 = np.sum(dd * dd, axis=1)
+    keep = r2 <= cutoff * cutoff
+    if len(exkeys):
+        keep &= ~np.isin(gi * n + gj, exkeys)
+    gi, gj, dd, r2 = gi[keep], gj[keep], dd[keep], r2[keep]
+    r = np.sqrt(r2)
+    qq = KE * q[gi] * q[gj]
+    e = qq * erfc(beta * r) / r
+    dEdr = -(e / r + qq * 2 * beta / math.sqrt(math.pi) * np.exp(-(beta * r) ** 2) / r)
+    f = -(dEdr / r)[:, None] * dd
+    F = np.stack([np.bincount(gi, f[:, d], n) - np.bincount(gj, f[:, d], n) for d in range(3)], axis=1)
+    return float(e.sum()), F
+
+
+def real_space(pos, q, box, beta, cutoff, excl=None, chunk=1024, pairs="dense"):
+    """erfc(beta r)/r over the non-excluded pairs within the cutoff (minimum image).  pairs="dense": every pair, in
+    chunks of rows; pairs="kdtree": the pairs of a periodic k-d tree (scipy.spatial.cKDTree), same result to rounding."""
     pos = np.asarray(pos, np.float64)
     q = np.asarray(q, np.float64)
     n = len(q)
     ex = _excl_pairs(excl)
     exkeys = np.sort(ex[:, 0] * n + ex[:, 1])
+    if pairs == "kdtree":
+        return _real_space_kdtree(pos, q, np.asarray(box, np.float64), beta, cutoff, exkeys)
+    assert pairs == "dense", pairs
     E = 0.0
     F = np.zeros_like(pos)
     for s in range(0, n, chunk):
@@ -216,11 +245,11 @@ def real_space(pos, q, box, beta, cutoff, excl=None, chunk=1024):
     return E, F
 
 
-def pme(pos, q, box, beta, cutoff, grid, order, excl=None):
+def pme(pos, q, box, beta, cutoff, grid, order, excl=None, pairs="dense"):
     """Smooth PME total: real space + reciprocal + excluded-pair correction + self + background."""
     box = np.asarray(box, np.float64)
     q = np.asarray(q, np.float64)
-    Er, Fr = real_space(pos, q, box, beta, cutoff, excl)
+    Er, Fr = real_space(pos, q, box, beta, cutoff, excl, pairs=pairs)
     Ek, Fk = pme_reciprocal(pos, q, box, beta, grid, order)
     Ex, Fx = excluded_correction(pos, q, box, beta, excl)
     return Er + Ek + Ex + self_and_background(q, box, beta), Fr + Fk + Fx

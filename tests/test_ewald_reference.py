@@ -97,3 +97,37 @@ def test_grid_rule_matches_openmm_sizes():
     beta = E.ewald_beta(9.0, 5e-4)
     assert abs(beta - math.sqrt(-math.log(1e-3)) / 9.0) < 1e-15
     assert pme_grid_size(beta, 98.6, 5e-4) == _fft_size(math.ceil(2 * beta * 98.6 / (3 * 5e-4 ** 0.2)))
+
+
+@pytest.mark.parametrize("case", ["ions", "ions_unwrapped", "water_like", "tiny_box"])
+def test_kdtree_real_space_equals_dense(case):
+    """The k-d tree pair search of real_space (for systems of 10^5 atoms) against the O(N^2) path: the same pairs, the same
+    exclusions, energy and forces equal to rounding — on wrapped positions, on positions shifted by up to +-3 boxes, and
+    with a cutoff close to half the box."""
+    rng = np.random.default_rng(11)
+    box = np.array([18.0, 19.0, 20.0])
+    cutoff, excl = 8.0, [(0, 1), (2, 3), (5, 9), (9, 5)]
+    if case.startswith("ions"):
+        pos, q = E.random_ions(120, box, seed=2, net=2)
+        if case == "ions_unwrapped":
+            pos = pos + rng.integers(-3, 4, size=pos.shape) * box
+    elif case == "water_like":  # bonded triples straddling the faces, each moved as a whole by whole boxes
+        o = rng.uniform(0, 1, (60, 3)) * box
+        pos = np.concatenate([o, o + [0.96, 0, 0], o + [-0.24, 0.93, 0]], axis=1).reshape(-1, 3)
+        pos = (pos.reshape(-1, 3, 3) + rng.integers(-3, 4, size=(60, 1, 3)) * box).reshape(-1, 3)
+        pos[0] = [0.0, box[1], -1e-7 * box[2]]
+        q = np.tile([-0.834, 0.417, 0.417], 60)
+        excl = [(3 * m + a, 3 * m + b) for m in range(60) for a, b in ((0, 1), (0, 2), (1, 2))]
+    else:
+        box = np.array([12.0, 12.5, 13.0])
+        pos, q = E.random_ions(30, box, seed=3, min_dist=1.5)
+        cutoff = 5.99
+    e0, f0 = E.real_space(pos, q, box, 0.33, cutoff, excl)
+    e1, f1 = E.real_space(pos, q, box, 0.33, cutoff, excl, pairs="kdtree")
+    assert abs(e1 - e0) <= 1e-12 * max(1.0, abs(e0)), (e0, e1)
+    assert np.abs(f1 - f0).max() <= 1e-11 * max(1.0, np.abs(f0).max())
+    # the total of pme() is unchanged by the pair search
+    ep0, fp0 = E.pme(pos, q, box, 0.33, cutoff, (16, 18, 20), 4, excl)
+    ep1, fp1 = E.pme(pos, q, box, 0.33, cutoff, (16, 18, 20), 4, excl, pairs="kdtree")
+    assert abs(ep1 - ep0) <= 1e-12 * max(1.0, abs(ep0))
+    assert np.abs(fp1 - fp0).max() <= 1e-11 * max(1.0, np.abs(fp0).max())

@@ -96,8 +96,11 @@ __device__ __forceinline__ void bspline(R w, R (&th)[P], R (&dth)[P]) {
   for (int j = 0; j < P; ++j) th[j] = a[j];
 }
 
+// (no contraction: fused into fma(x, invL, -floor(x * invL)), s is negative when x * invL rounds up to an integer — x = L
+// for L = 30 in fp64 — and the atom lands in bin 0 instead of bin K - 1, one grid spacing from where it is)
 template <typename R>
 __device__ __forceinline__ void frac_coord(R x, R L, R invL, int K, int &iu, R &w) {
+#pragma clang fp contract(off)
   R s = x * invL;
   s -= floor(s);
   const R u = s * R(K);
@@ -288,7 +291,7 @@ __device__ __forceinline__ void erf_over_x(R x, R &f0, R &f1) {
   if (x < R(2e-2)) {
     const R x2 = x * x;
     f0 = tsp * (R(1) - x2 * (R(1) / R(3) - x2 * (R(0.1) - x2 / R(42))));
-    f1 = tsp * (R(-2) / R(3) + x2 * (R(0.4) - x2 * (R(1) / R(7) - x2 * R(17) / R(216))));
+    f1 = tsp * (R(-2) / R(3) + x2 * (R(0.4) - x2 * (R(1) / R(7) - x2 / R(27))));
   } else {
     const R e = erf(x), ix = R(1) / x;
     f0 = e * ix;
