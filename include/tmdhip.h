@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define TMDHIP_ABI_VERSION 9
+#define TMDHIP_ABI_VERSION 10
 
 /* dtype */
 #define TMDHIP_F32 0
@@ -167,6 +167,31 @@ typedef struct tmdhip_pme_desc {
   int32_t order;       /* B-spline order (4..6) */
 } tmdhip_pme_desc;
 int tmdhip_set_pme(tmdhip_ctx *ctx, const tmdhip_pme_desc *desc);
+
+/* Holonomic constraints of the MD loop (ABI 10): rigid waters and X-H bond clusters.  tmdhip_md_run then steps every unit —
+ * a rigid water, a cluster or an unconstrained atom — in one thread (md_loop.hip: md_step_cons_kernel), in double: after the
+ * second half kick the velocity constraint of the unit (its k x k linear system solved exactly), after the drift the position
+ * constraint relative to the positions before it (analytic SETTLE for waters, Miyamoto & Kollman 1992; iterated SHAKE for
+ * clusters), then v += dx / dt.  The fused pair + step launches, the inline bonded integrator kernel and the replica-batched
+ * launch are not used; tmdhip_compute is unaffected (the constrained bond and angle terms stay in the energies).  A cluster
+ * that does not converge within max_iter sweeps (or a water too distorted for SETTLE) makes the next tmdhip_md_observe /
+ * tmdhip_check return an error.  Copies to the device and synchronises.  enable = 0, or no units, releases everything.
+ * Domain decomposition refuses a context with constraints. */
+typedef struct tmdhip_constraint_desc {
+  int32_t struct_size;               /* = sizeof(tmdhip_constraint_desc) */
+  int32_t enable;
+  int32_t nwaters;
+  int32_t nclusters;
+  const int32_t *water_host;         /* [nwaters][3]: O, H1, H2 */
+  const double *water_dist_host;     /* [nwaters][2]: d_OH, d_HH (Angstrom) */
+  const int32_t *cluster_offsets_host; /* [nclusters + 1]: CSR into cluster_atoms_host (2 .. 5 atoms per cluster) */
+  const int32_t *cluster_atoms_host; /* the central atom first, then its hydrogens */
+  const double *cluster_dist_host;   /* per entry of cluster_atoms_host: bond length to the central atom (central: unused) */
+  double tolerance;                  /* SHAKE: relative bond-length tolerance */
+  int32_t max_iter;                  /* SHAKE: sweeps at most */
+  int32_t reserved;
+} tmdhip_constraint_desc;
+int tmdhip_set_constraints(tmdhip_ctx *ctx, const tmdhip_constraint_desc *desc);
 
 /* Nonbonded block of Forces.compute (forces.py:260-319) for one replica: minimum-image distances
  * (360-372), `dist <= cutoff` filter (76-81), LJ (+switch) / Coulomb / reaction field / repulsion

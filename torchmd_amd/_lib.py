@@ -13,7 +13,7 @@ PKG = os.path.dirname(os.path.abspath(__file__))
 # TMDHIP_LIB: developer knob for A/B runs of differently built libraries (kernel experiments)
 LIBPATH = os.environ.get("TMDHIP_LIB") or os.path.join(PKG, "lib", "libtmdhip.so")
 
-ABI_VERSION = 9
+ABI_VERSION = 10
 F32, F64 = 0, 1
 TERM_LJ, TERM_ELECTROSTATICS, TERM_REPULSION, TERM_REPULSIONCG = 1, 2, 4, 8
 E_LJ, E_ELECTROSTATICS, E_REPULSION, E_REPULSIONCG, E_BONDS, E_ANGLES, E_DIHEDRALS, E_IMPROPERS = range(8)
@@ -217,6 +217,23 @@ class PmeDesc(C.Structure):
     ]
 
 
+class ConstraintDesc(C.Structure):
+    _fields_ = [
+        ("struct_size", C.c_int32),
+        ("enable", C.c_int32),
+        ("nwaters", C.c_int32),
+        ("nclusters", C.c_int32),
+        ("water_host", C.c_void_p),
+        ("water_dist_host", C.c_void_p),
+        ("cluster_offsets_host", C.c_void_p),
+        ("cluster_atoms_host", C.c_void_p),
+        ("cluster_dist_host", C.c_void_p),
+        ("tolerance", C.c_double),
+        ("max_iter", C.c_int32),
+        ("reserved", C.c_int32),
+    ]
+
+
 # name -> (restype, argtypes): every symbol include/tmdhip.h declares
 SIGNATURES = {
     "tmdhip_abi_version": (C.c_int, []),
@@ -225,6 +242,7 @@ SIGNATURES = {
     "tmdhip_set_bonded": (C.c_int, [C.c_void_p, C.POINTER(BondedDesc)]),
     "tmdhip_destroy": (None, [C.c_void_p]),
     "tmdhip_set_pme": (C.c_int, [C.c_void_p, C.POINTER(PmeDesc)]),
+    "tmdhip_set_constraints": (C.c_int, [C.c_void_p, C.POINTER(ConstraintDesc)]),
     "tmdhip_compute_nonbonded": (
         C.c_int,
         [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_double), C.c_void_p, C.c_void_p, C.c_int, C.c_void_p],

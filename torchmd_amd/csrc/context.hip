@@ -578,6 +578,7 @@ void tmdhip_destroy(tmdhip_ctx *ctx) {
   ctx->obs_ke.release();
   tmd::bonded_release(ctx);
   tmd::pme_release(ctx);
+  tmd::cons_release(ctx);
   delete ctx;
 }
 
@@ -768,8 +769,12 @@ int tmdhip_check(tmdhip_ctx *ctx, int replica, void *stream) {
   if (!ctx) return fail("tmdhip_check: null ctx");
   if (replica < 0 || replica >= (int)ctx->rep.size()) return fail("tmdhip_check: bad replica index");
   Replica &rp = ctx->rep[replica];
-  if (ctx->algorithm != TMDHIP_ALGO_CELLLIST || !rp.have_list) return 0;
   hipStream_t st = (hipStream_t)stream;
+  if (ctx->cons) {  // (a constrained step that did not converge: the device raised a host-mapped word)
+    TMD_HIP(hipStreamSynchronize(st));
+    TMD_TRY(cons_verdict(ctx));
+  }
+  if (ctx->algorithm != TMDHIP_ALGO_CELLLIST || !rp.have_list) return 0;
   int h[F_COUNT];
   TMD_HIP(hipMemcpyAsync(h, rp.flags.p, sizeof(h), hipMemcpyDeviceToHost, st));
   TMD_HIP(hipStreamSynchronize(st));

@@ -868,8 +868,9 @@ static int dd_run_body(tmdhip_ctx *ctx, tmdhip_comm *c, const tmdhip_dd_desc *d,
 }
 
 int tmdhip_dd_run(tmdhip_ctx *ctx, tmdhip_comm *c, const tmdhip_dd_desc *d, int32_t *iters_done, void *stream) {
-  const int rc = (ctx && ctx->pme) ? fail("tmdhip_dd_run: PME contexts cannot be decomposed (no distributed FFT)")
-                                   : dd_run_body(ctx, c, d, iters_done, stream);
+  const int rc = (ctx && ctx->pme)    ? fail("tmdhip_dd_run: PME contexts cannot be decomposed (no distributed FFT)")
+                 : (ctx && ctx->cons) ? fail("tmdhip_dd_run: contexts with constraints cannot be decomposed (units would straddle bricks)")
+                                      : dd_run_body(ctx, c, d, iters_done, stream);
   // in-process transport: a rank that fails leaves the others waiting at the hub's next rendezvous — wake them up now
   // (their calls fail with "broken hub") instead of after the barrier's 30-s time-out
   if (rc < 0 && c && c->hub) c->hub->abort();

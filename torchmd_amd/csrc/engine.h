@@ -624,6 +624,8 @@ struct tmdhip_ctx {
   // smooth PME (tmdhip_set_pme), pme.hip; null: off (no PME buffer, no PME launch)
   void *pme = nullptr;
   double pme_beta = 0;
+  // holonomic constraints of the MD loop (tmdhip_set_constraints), md_loop.hip; null: off
+  void *cons = nullptr;
   // timing of the dominant kernel
   bool timing = false;
   int timing_stride = 1;    // every n-th launch is timed
@@ -789,6 +791,11 @@ int pme_apply(tmdhip_ctx *ctx, int r, const R *pos, const double *box, R *forces
 // TMDHIP_WANT_ENERGY
 int pme_hook(tmdhip_ctx *ctx, int r, const void *pos, const double *box, void *forces, double *energies, int flags, hipStream_t st);
 void pme_release(tmdhip_ctx *ctx);
+// md_loop.hip: the constraint state of the MD loop (tmdhip_set_constraints).  cons_verdict: < 0 (and the message) when a
+// constrained step since the last look failed to converge; reads a host-mapped word, so the caller must have waited for the
+// stream (or for a report enqueued behind the steps).
+void cons_release(tmdhip_ctx *ctx);
+int cons_verdict(tmdhip_ctx *ctx);
 int64_t pme_evaluations(const tmdhip_ctx *ctx, int r);
 int64_t pme_bytes(const tmdhip_ctx *ctx);
 // md_loop.hip

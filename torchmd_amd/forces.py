@@ -196,6 +196,7 @@ class _Engine:
         if have:
             L.check(lib.tmdhip_set_bonded(self.ctx, C.byref(b)), "tmdhip_set_bonded")
         self.has_nonbonded = terms != 0
+        self._constraints = None
         st = L.Stats()
         L.check(lib.tmdhip_get_stats(self.ctx, 0, C.byref(st)), "tmdhip_get_stats")
         # the nonbonded kernels *store* forces when asked to (the cell-list pair kernel owns every atom
@@ -211,6 +212,28 @@ class _Engine:
         self.kebuf = self.comb[nreplicas * L.NENERGY:]
         _LIVE_ENGINES.add(self)
         del keep
+
+    def set_constraints(self, cs):
+        """Hand a `constraints.ConstraintSet` to the context (tmdhip_set_constraints); None releases it."""
+        d = L.ConstraintDesc()
+        d.struct_size = C.sizeof(L.ConstraintDesc)
+        keep = []
+        if cs is not None:
+            def ptr(a):
+                keep.append(a)
+                return a.ctypes.data_as(C.c_void_p)
+
+            d.enable = 1
+            d.nwaters, d.nclusters = cs.nwaters, cs.nclusters
+            d.water_host = ptr(np.ascontiguousarray(cs.waters, dtype=np.int32))
+            d.water_dist_host = ptr(np.ascontiguousarray(cs.water_dist, dtype=np.float64))
+            d.cluster_offsets_host = ptr(np.ascontiguousarray(cs.offsets, dtype=np.int32))
+            d.cluster_atoms_host = ptr(np.ascontiguousarray(cs.atoms if len(cs.atoms) else np.zeros(1), dtype=np.int32))
+            d.cluster_dist_host = ptr(np.ascontiguousarray(cs.dist if len(cs.dist) else np.zeros(1), dtype=np.float64))
+            d.tolerance = cs.tolerance
+            d.max_iter = cs.max_iter
+        L.check(self.lib.tmdhip_set_constraints(self.ctx, C.byref(d)), "tmdhip_set_constraints")
+        self._constraints = cs
 
     def close(self):
         if self.ctx:
@@ -704,7 +727,7 @@ class Forces:
                 return ebuf, torch.as_tensor(ext_ene, device=pos.device).detach().to(torch.float64).reshape(-1)
         return (ebuf, None) if want_energy else (None, None)
 
-    def _md_run(self, system, masses, vcoeff, dt, gamma, seed, step0, niter, restore=False):
+    def _md_run(self, system, masses, vcoeff, dt, gamma, seed, step0, niter, restore=False, constraints=None):
         """Integrator fast path: `niter` MD steps enqueued by one C call; returns the energy buffer of the
         last step (device, [R, NENERGY]).  `restore`: first rewind to the state at the entry of the previous
         call (tmdhip_md_restore) — the replay after a neighbour-list validity failure."""
@@ -715,6 +738,8 @@ class Forces:
         hbox = self._host_box(system.box)
         self._pme_box(hbox)
         eng = self._engine(pos)
+        if getattr(eng, "_constraints", None) is not constraints:
+            eng.set_constraints(constraints)
         R = pos.shape[0]
         # the descriptor and the per-replica box array are kept between calls (a 20-step call is short enough for
         # the Python in front of its first launch to show)

@@ -2,7 +2,8 @@
 
 Mirror of the reference module (`torchmd/integrator.py`): same constants, helper functions,
 `Integrator(systems, forces, timestep, device, gamma=None, T=None, batch=None)` constructor and
-`step(niter) -> (Ekin, pot, T)` contract.  Each iteration is
+`step(niter) -> (Ekin, pot, T)` contract, plus an opt-in `constraints` keyword ("water": rigid waters by SETTLE;
+"hbonds": also every X-H bond by SHAKE/RATTLE) that this package adds.  Each iteration is
 
     tmdhip_first_vv  ->  forces.compute  ->  tmdhip_langevin_second_vv | tmdhip_second_vv
 
@@ -96,7 +97,7 @@ _LIST_INVALID = ("Integrator.step(): a neighbour list overflowed or outlived its
 
 
 class Integrator:
-    def __init__(self, systems, forces, timestep, device, gamma=None, T=None, batch=None):
+    def __init__(self, systems, forces, timestep, device, gamma=None, T=None, batch=None, constraints=None):
         self.dt = timestep / TIMEFACTOR
         self.systems = systems
         self.forces = forces
@@ -124,7 +125,43 @@ class Integrator:
         self._seed = int(torch.randint(0, 2**62, (1,), dtype=torch.int64).item())
         self._nstep = 0
         self._ke = None
+        self.constraints = None  # constraints.ConstraintSet
+        if constraints is not None:
+            self._init_constraints(constraints)
         self.replays = 0  # batches that were rewound and repeated (list validity failure / step-block time-out)
+
+    def _init_constraints(self, mode):
+        from .constraints import find_constraints
+        from .forces import Forces
+
+        if not isinstance(self.forces, Forces) or self.forces.external:
+            raise ValueError("constraints need this package's Forces without an `external` term (the tmdhip_md_run path); "
+                             "duck-typed force objects and external forces are not supported")
+        par = self.forces.par
+        self.constraints = find_constraints(self.masses.detach().cpu().double().reshape(-1).numpy(), par.bond_params,
+                                            getattr(par, "angle_params", None), mode)
+        self._ndof = self.constraints.ndof(self.batch)
+        self._projected = False
+
+    def _temperature(self, Ekin):
+        if self.constraints is None:
+            return kinetic_to_temp(Ekin, self.natoms)
+        return 2.0 / (np.asarray(self._ndof, dtype=np.float64) * BOLTZMAN) * Ekin
+
+    def _project_start(self):
+        """OpenMM's applyConstraints at the first step: SHAKE the positions onto the constraints (the current positions as
+        reference), remove the velocity components along them, and evaluate the forces of the projected positions."""
+        s, cs = self.systems, self.constraints
+        pos = s.pos.detach().cpu().double().numpy()
+        vel = s.vel.detach().cpu().double().numpy()
+        for r in range(pos.shape[0]):
+            ref = pos[r].copy()
+            cs.shake_positions(pos[r], ref)
+            cs.project_velocities(pos[r], vel[r])
+        s.pos.copy_(torch.as_tensor(pos).to(s.pos.dtype))
+        s.vel.copy_(torch.as_tensor(vel).to(s.vel.dtype))
+        self.forces.compute(s.pos, s.box, s.forces)
+        self._projected = True
 
     def _check_layout(self):
         s = self.systems
@@ -152,6 +189,8 @@ class Integrator:
         fast = isinstance(self.forces, Forces)
         fused = fast and not self.forces.external and niter > 0
         with torch.cuda.device(dev):
+            if self.constraints is not None and not self._projected:
+                self._project_start()
             return self._step_body(lib, s, dev, code, R, N, fast, fused, niter, replay=False)
 
     def _step_body(self, lib, s, dev, code, R, N, fast, fused, niter, replay):
@@ -165,6 +204,7 @@ class Integrator:
             ebuf = self.forces._md_run(
                 s, self.masses, self.vcoeff if self.T else None, self.dt,
                 float(self.gamma) if self.T else 0.0, self._seed, step0, niter, restore=replay,
+                constraints=self.constraints,
             )
             if not replay:
                 self._nstep += niter
@@ -219,7 +259,7 @@ class Integrator:
             pot = [float(v) for v in tot]
             Ekin = obs[:, L.NENERGY].copy()
             Ekin = Ekin.astype(np.dtype("float32") if s.pos.dtype == torch.float32 else np.float64)
-            return Ekin, pot, kinetic_to_temp(Ekin, self.natoms)
+            return Ekin, pot, self._temperature(Ekin)
         if self.batch is None:
             if eng is not None:
                 kebuf = eng.kebuf  # shares one buffer with the energies: a single read-back below
@@ -258,5 +298,5 @@ class Integrator:
         else:
             Ekin = ke.flatten().cpu().numpy()
         Ekin = Ekin.astype(np.dtype("float32") if s.pos.dtype == torch.float32 else np.float64)
-        T = kinetic_to_temp(Ekin, self.natoms)
+        T = self._temperature(Ekin)
         return Ekin, pot, T

@@ -40,6 +40,7 @@ DEFAULTS = dict(
     save_period=0, steps=10000, log_dir="./", output="output", forceterms=["LJ"], cutoff=None,
     switch_dist=None, precision="single", external=None, rfa=False, replicas=1, extended_system=None,
     minimize=None, exclusions=("bonds", "angles", "1-4"), pme=False, ewald_tolerance=5e-4, pme_order=5, pme_grid=None,
+    constraints=None,  # None, "water" (rigid waters) or "hbonds" (rigid waters and X-H bonds): DESIGN §10
 )
 
 
@@ -68,6 +69,10 @@ def get_args(arguments=None):
             setattr(args, k, float(getattr(args, k)))
     args.ewald_tolerance = float(args.ewald_tolerance)
     args.pme = bool(args.pme)
+    if isinstance(args.constraints, str) and args.constraints.lower() in ("none", "null", ""):
+        args.constraints = None
+    if args.constraints not in (None, "water", "hbonds"):
+        raise ValueError(f"constraints must be None, 'water' or 'hbonds', got {args.constraints!r}")
     if args.pme_grid is not None:
         args.pme_grid = tuple(int(v) for v in args.pme_grid)
     for k in ("steps", "output_period", "save_period", "replicas", "seed", "pme_order"):
@@ -211,7 +216,7 @@ def dynamics(args, mol, system, forces):
     torch.manual_seed(args.seed)
     device = torch.device(args.device)
     integrator = Integrator(system, forces, args.timestep, device, gamma=args.langevin_gamma,
-                            T=args.langevin_temperature)
+                            T=args.langevin_temperature, constraints=args.constraints)
     wrapper = Wrapper(mol.numAtoms, mol.bonds if len(mol.bonds) else None, device)
     nper = args.steps // args.output_period
     stager = FrameStager(system, nper)
