@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define TMDHIP_ABI_VERSION 10
+#define TMDHIP_ABI_VERSION 11
 
 /* dtype */
 #define TMDHIP_F32 0
@@ -327,6 +327,18 @@ int tmdhip_kinetic_energy(int dtype, int64_t nreplicas, int64_t natoms, const vo
 int tmdhip_wrap(int dtype, int64_t nreplicas, int64_t natoms, void *pos_dev, const void *box_dev, int32_t ngroups,
                 const int32_t *group_offsets_dev, const int32_t *group_members_dev, int32_t has_big_groups,
                 void *stream);
+/* The move of a Monte Carlo barostat (ABI 11): for every replica r and every group g, c = unweighted mean of the
+ * group's positions (the centre tmdhip_wrap uses, accumulated in double in both precisions), then every atom of
+ * the group is translated by (scale[r] - 1) * c, component by component: the centres follow a box whose edges are
+ * multiplied by scale[r], distances inside a group do not change.  A replica whose three factors are exactly 1 is
+ * not written.  saved_pos_dev (real [R,N,3], or NULL) receives the positions as they were, from the same launch;
+ * restoring a rejected move is a copy from there, never a scaling by 1/s.  scale_host is double [R][3] (read before
+ * the call returns).  Groups as for tmdhip_wrap (a CSR that covers every atom once).  Molecules must be whole, not
+ * split across the periodic boundary (true of what tmdhip_wrap leaves and of unwrapped trajectories).  Stateless:
+ * no context, no atomics, members summed in index order, so two calls on the same input give the same bits. */
+int tmdhip_scale_groups(int dtype, int64_t nreplicas, int64_t natoms, void *pos_dev, void *saved_pos_dev,
+                        const double *scale_host, int32_t ngroups, const int32_t *group_offsets_dev,
+                        const int32_t *group_members_dev, int32_t has_big_groups, void *stream);
 /* Fill `out_dev` (real [n]) with the N(0,1) stream used by tmdhip_langevin_second_vv (for tests). */
 int tmdhip_normal_fill(int dtype, int64_t n, void *out_dev, uint64_t seed, uint64_t step, void *stream);
 

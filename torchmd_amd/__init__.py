@@ -3,6 +3,7 @@
 Public surface mirrors the reference package for this path:
     torchmd_amd.forces.Forces, torchmd_amd.integrator.Integrator, torchmd_amd.systems.System,
     torchmd_amd.parameters.Parameters, torchmd_amd.forcefields.ForceField
+plus `torchmd_amd.MonteCarloBarostat` (constant pressure; imported on first use only)
 backed by hand-written HIP kernels in `torchmd_amd/lib/libtmdhip.so` (C ABI: include/tmdhip.h).
 """
 
@@ -11,9 +12,21 @@ from .integrator import Integrator, kinetic_energy, kinetic_to_temp, maxwell_bol
 from .parameters import Parameters
 from .systems import System
 
+
+
+def __getattr__(name):
+    # the barostat module is loaded on first use: a run without it never imports it
+    if name == "MonteCarloBarostat":
+        from .barostat import MonteCarloBarostat
+
+        return MonteCarloBarostat
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
+
+
 __all__ = [
     "Forces",
     "Integrator",
+    "MonteCarloBarostat",
     "Parameters",
     "System",
     "kinetic_energy",

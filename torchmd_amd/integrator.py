@@ -3,7 +3,8 @@
 Mirror of the reference module (`torchmd/integrator.py`): same constants, helper functions,
 `Integrator(systems, forces, timestep, device, gamma=None, T=None, batch=None)` constructor and
 `step(niter) -> (Ekin, pot, T)` contract, plus an opt-in `constraints` keyword ("water": rigid waters by SETTLE;
-"hbonds": also every X-H bond by SHAKE/RATTLE) that this package adds.  Each iteration is
+"hbonds": also every X-H bond by SHAKE/RATTLE) and an opt-in `barostat` keyword (a
+`barostat.MonteCarloBarostat`: constant pressure) that this package adds.  Each iteration is
 
     tmdhip_first_vv  ->  forces.compute  ->  tmdhip_langevin_second_vv | tmdhip_second_vv
 
@@ -96,8 +97,20 @@ _LIST_INVALID = ("Integrator.step(): a neighbour list overflowed or outlived its
                  "the previous step() call is invalid (restart from the last saved state; the list capacity has been grown)")
 
 
+def cut_segments(nstep, niter, frequency):
+    """How `step(niter)` is cut when something has to happen every `frequency` steps counted over the integrator's life:
+    [(n, attempt), ...] with sum(n) == niter; a segment ends where `nstep` + the steps so far reaches a multiple of
+    `frequency` (attempt = True) or where the call ends."""
+    out, done = [], 0
+    while done < niter:
+        n = min(frequency - (nstep + done) % frequency, niter - done)
+        done += n
+        out.append((n, (nstep + done) % frequency == 0))
+    return out
+
+
 class Integrator:
-    def __init__(self, systems, forces, timestep, device, gamma=None, T=None, batch=None, constraints=None):
+    def __init__(self, systems, forces, timestep, device, gamma=None, T=None, batch=None, constraints=None, barostat=None):
         self.dt = timestep / TIMEFACTOR
         self.systems = systems
         self.forces = forces
@@ -129,6 +142,9 @@ class Integrator:
         if constraints is not None:
             self._init_constraints(constraints)
         self.replays = 0  # batches that were rewound and repeated (list validity failure / step-block time-out)
+        self.barostat = barostat  # barostat.MonteCarloBarostat
+        if barostat is not None:
+            barostat.check(systems, forces, temperature=T if T else 0)
 
     def _init_constraints(self, mode):
         from .constraints import find_constraints
@@ -191,7 +207,23 @@ class Integrator:
         with torch.cuda.device(dev):
             if self.constraints is not None and not self._projected:
                 self._project_start()
+            if self.barostat is not None and niter > 0:
+                return self._step_npt(lib, s, dev, code, R, N, fast, niter)
             return self._step_body(lib, s, dev, code, R, N, fast, fused, niter, replay=False)
+
+    def _step_npt(self, lib, s, dev, code, R, N, fast, niter):
+        """`step(niter)` at constant pressure: segments that end on multiples of the barostat's frequency (counted over the
+        integrator's life), each run as `step` runs it, and a volume move after every segment that ends on a multiple.
+        After an accepted move the returned potential energy and `systems.forces` are those of the scaled state."""
+        out = None
+        for n, attempt in cut_segments(self._nstep, niter, self.barostat.frequency):
+            fused = fast and not self.forces.external
+            out = self._step_body(lib, s, dev, code, R, N, fast, fused, n, replay=False)
+            if attempt:
+                rec = self.barostat.attempt(s, self.forces, out[1])
+                pot = [float(un if ok else u) for u, un, ok in zip(rec["U"], rec["U_new"], rec["accepted"])]
+                out = (out[0], pot, out[2])
+        return out
 
     def _step_body(self, lib, s, dev, code, R, N, fast, fused, niter, replay):
 

@@ -8,6 +8,8 @@ file.coor|.pdb` + `extended_system: file.xsc` (AMBER), `forcefield: *.yaml | *.p
 Outputs like the reference (`run.py:230-291`): `monitor_{k}.csv` (iter, ns, epot, ekin, etot, T, t),
 `{output}_{k}.npy` trajectory `[N,3,frames]`, `input.yaml` echo.  Frames are staged through a pinned
 host ring with asynchronous copies instead of a blocking `.cpu()` per period.
+With `barostat_pressure` set (constant pressure) the box edges of every frame are saved as
+`{output}_box_{k}.npy` `[frames,3]` and the monitor file gains a `volume` column.
 """
 
 from __future__ import annotations
@@ -41,6 +43,8 @@ DEFAULTS = dict(
     switch_dist=None, precision="single", external=None, rfa=False, replicas=1, extended_system=None,
     minimize=None, exclusions=("bonds", "angles", "1-4"), pme=False, ewald_tolerance=5e-4, pme_order=5, pme_grid=None,
     constraints=None,  # None, "water" (rigid waters) or "hbonds" (rigid waters and X-H bonds): DESIGN §10
+    barostat_pressure=None,  # bar; None: constant volume.  Monte Carlo barostat at langevin_temperature: DESIGN §11
+    barostat_frequency=25,  # steps between two volume moves
 )
 
 
@@ -73,6 +77,13 @@ def get_args(arguments=None):
         args.constraints = None
     if args.constraints not in (None, "water", "hbonds"):
         raise ValueError(f"constraints must be None, 'water' or 'hbonds', got {args.constraints!r}")
+    if isinstance(args.barostat_pressure, str) and args.barostat_pressure.lower() in ("none", "null", ""):
+        args.barostat_pressure = None
+    if args.barostat_pressure is not None:
+        args.barostat_pressure = float(args.barostat_pressure)
+    args.barostat_frequency = int(args.barostat_frequency)
+    if args.barostat_frequency < 1:
+        raise ValueError(f"barostat_frequency must be a positive number of steps, got {args.barostat_frequency}")
     if args.pme_grid is not None:
         args.pme_grid = tuple(int(v) for v in args.pme_grid)
     for k in ("steps", "output_period", "save_period", "replicas", "seed", "pme_order"):
@@ -215,13 +226,22 @@ class FrameStager:
 def dynamics(args, mol, system, forces):
     torch.manual_seed(args.seed)
     device = torch.device(args.device)
+    barostat = None
+    if args.barostat_pressure is not None:
+        from .barostat import MonteCarloBarostat
+
+        if not args.langevin_temperature:
+            raise ValueError("barostat_pressure needs a thermostat: set langevin_temperature")
+        barostat = MonteCarloBarostat(args.barostat_pressure, args.langevin_temperature, args.barostat_frequency)
+    extra = {} if barostat is None else {"barostat": barostat}
     integrator = Integrator(system, forces, args.timestep, device, gamma=args.langevin_gamma,
-                            T=args.langevin_temperature, constraints=args.constraints)
+                            T=args.langevin_temperature, constraints=args.constraints, **extra)
     wrapper = Wrapper(mol.numAtoms, mol.bonds if len(mol.bonds) else None, device)
     nper = args.steps // args.output_period
     stager = FrameStager(system, nper)
-    logs = [LogWriter(args.log_dir, ("iter", "ns", "epot", "ekin", "etot", "T"), name=f"monitor_{k}.csv")
-            for k in range(args.replicas)]
+    columns = ("iter", "ns", "epot", "ekin", "etot", "T") + (("volume",) if barostat is not None else ())
+    logs = [LogWriter(args.log_dir, columns, name=f"monitor_{k}.csv") for k in range(args.replicas)]
+    boxes = []  # [frames][R,3] box edges, constant-pressure runs only
     if args.minimize is not None:
         minimize_bfgs(system, forces, steps=int(args.minimize))
     forces.compute(system.pos, system.box, system.forces)
@@ -231,12 +251,18 @@ def dynamics(args, mol, system, forces):
         Ekin, Epot, T = integrator.step(niter=args.output_period)
         wrapper.wrap(system.pos, system.box)
         stager.push(system.pos)
+        if barostat is not None:
+            boxes.append(torch.diagonal(system.box, dim1=-2, dim2=-1).to("cpu", torch.float64).numpy().copy())
         for k in range(args.replicas):
             if (i * args.output_period) % args.save_period == 0 or i == nper:
                 np.save(os.path.join(args.log_dir, f"{name}_{k}{ext or '.npy'}"), stager.frames(k))
-            logs[k].write_row({"iter": i * args.output_period, "ns": FS2NS * i * args.output_period * args.timestep,
-                               "epot": Epot[k], "ekin": float(Ekin[k]), "etot": Epot[k] + float(Ekin[k]),
-                               "T": float(T[k])})
+                if barostat is not None:
+                    np.save(os.path.join(args.log_dir, f"{name}_box_{k}{ext or '.npy'}"), np.stack([b[k] for b in boxes]))
+            row = {"iter": i * args.output_period, "ns": FS2NS * i * args.output_period * args.timestep,
+                   "epot": Epot[k], "ekin": float(Ekin[k]), "etot": Epot[k] + float(Ekin[k]), "T": float(T[k])}
+            if barostat is not None:
+                row["volume"] = float(np.prod(boxes[-1][k]))
+            logs[k].write_row(row)
     wall = time.time() - t0
     print(f"{args.steps} steps in {wall:.2f} s = {args.steps * args.timestep * FS2NS / wall * 86400:.1f} ns/day per replica")
     return stager
