@@ -193,6 +193,30 @@ typedef struct tmdhip_constraint_desc {
 } tmdhip_constraint_desc;
 int tmdhip_set_constraints(tmdhip_ctx *ctx, const tmdhip_constraint_desc *desc);
 
+/* Virtual interaction sites (added to ABI 11: new symbols only, no existing struct or call changes, so the version constant
+ * stays): massless sites at r_s = sum_k w_k r_parent_k with two or three parents and sum_k w_k = 1
+ * (the charge site of four-site water: TIP4P-Ew, TIP4P/2005, OPC).  The tables: site [nsites] atom indices, parent [nsites][3]
+ * (-1 in the third column: a two-parent site), weight double [nsites][3].  No site is a parent and no two sites share a parent.
+ * tmdhip_set_vsites copies them to the device for the context's own launches: in tmdhip_md_run the thread that steps a rigid
+ * water (tmdhip_set_constraints) also folds w_k F_site into the three parents' forces before any division by a mass, places the
+ * site from the constrained positions as rounded for storage (the expression of tmdhip_vsite_construct), writes its cell-sorted
+ * record and runs the Verlet-list displacement test for it; the site's velocity is stored as 0, and when the call returns the
+ * forces in forces_dev have been spread (zero site rows).  A site is never a unit of its own: nothing divides by its mass or
+ * draws noise for it.  Call it BEFORE tmdhip_set_constraints (which then requires every site's parents to be the O, H1, H2 of
+ * one of its waters, in that order, and fails otherwise); with constraints in place it returns an error.  tmdhip_compute* do not
+ * look at the tables: a caller of plain evaluations runs the stateless kernels below around them (torchmd_amd.forces does).
+ * Copies to the device and synchronises.  enable = 0, or no sites, releases everything. */
+typedef struct tmdhip_vsite_desc {
+  int32_t struct_size; /* = sizeof(tmdhip_vsite_desc) */
+  int32_t enable;
+  int32_t nsites;
+  int32_t reserved;
+  const int32_t *site_host;   /* [nsites] */
+  const int32_t *parent_host; /* [nsites][3], -1 = unused (third column only) */
+  const double *weight_host;  /* [nsites][3] */
+} tmdhip_vsite_desc;
+int tmdhip_set_vsites(tmdhip_ctx *ctx, const tmdhip_vsite_desc *desc);
+
 /* Nonbonded block of Forces.compute (forces.py:260-319) for one replica: minimum-image distances
  * (360-372), `dist <= cutoff` filter (76-81), LJ (+switch) / Coulomb / reaction field / repulsion
  * (381-491), force scatter and per-term energy sums (316-319).
@@ -339,6 +363,16 @@ int tmdhip_wrap(int dtype, int64_t nreplicas, int64_t natoms, void *pos_dev, con
 int tmdhip_scale_groups(int dtype, int64_t nreplicas, int64_t natoms, void *pos_dev, void *saved_pos_dev,
                         const double *scale_host, int32_t ngroups, const int32_t *group_offsets_dev,
                         const int32_t *group_members_dev, int32_t has_big_groups, void *stream);
+/* Virtual sites, stateless (added to ABI 11; tables as for tmdhip_set_vsites, but device arrays).  One thread per site, blockIdx.y =
+ * replica; arithmetic in double in both precisions, rounded once on the store, parents summed in table order, no atomics: two
+ * calls on the same input give the same bits.  Molecules must be whole (as for tmdhip_scale_groups): no minimum image.  A row
+ * index outside [0, natoms) makes the kernel skip that site.
+ * construct: pos_dev (real [R,N,3]) site rows = sum_k w_k * parent rows.
+ * spread:    forces_dev (real [R,N,3]) parent rows += w_k * site row, then the site row is stored as zero. */
+int tmdhip_vsite_construct(int dtype, int64_t nreplicas, int64_t natoms, void *pos_dev, int32_t nsites, const int32_t *site_dev,
+                           const int32_t *parent_dev, const double *weight_dev, void *stream);
+int tmdhip_vsite_spread(int dtype, int64_t nreplicas, int64_t natoms, void *forces_dev, int32_t nsites, const int32_t *site_dev,
+                        const int32_t *parent_dev, const double *weight_dev, void *stream);
 /* Fill `out_dev` (real [n]) with the N(0,1) stream used by tmdhip_langevin_second_vv (for tests). */
 int tmdhip_normal_fill(int dtype, int64_t n, void *out_dev, uint64_t seed, uint64_t step, void *stream);
 

@@ -234,6 +234,18 @@ class ConstraintDesc(C.Structure):
     ]
 
 
+class VsiteDesc(C.Structure):
+    _fields_ = [
+        ("struct_size", C.c_int32),
+        ("enable", C.c_int32),
+        ("nsites", C.c_int32),
+        ("reserved", C.c_int32),
+        ("site_host", C.c_void_p),
+        ("parent_host", C.c_void_p),
+        ("weight_host", C.c_void_p),
+    ]
+
+
 # name -> (restype, argtypes): every symbol include/tmdhip.h declares
 SIGNATURES = {
     "tmdhip_abi_version": (C.c_int, []),
@@ -299,6 +311,15 @@ SIGNATURES = {
         C.c_int,
         [C.c_int, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.POINTER(C.c_double), C.c_int32, C.c_void_p, C.c_void_p,
          C.c_int32, C.c_void_p],
+    ),
+    "tmdhip_set_vsites": (C.c_int, [C.c_void_p, C.POINTER(VsiteDesc)]),
+    "tmdhip_vsite_construct": (
+        C.c_int,
+        [C.c_int, C.c_int64, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
+    ),
+    "tmdhip_vsite_spread": (
+        C.c_int,
+        [C.c_int, C.c_int64, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
     ),
     "tmdhip_normal_fill": (C.c_int, [C.c_int, C.c_int64, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p]),
     "tmdhip_dd_step": (

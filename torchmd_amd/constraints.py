@@ -12,6 +12,11 @@ of units the constrained MD step integrates (include/tmdhip.h, tmdhip_set_constr
 A hydrogen is an atom of mass < 1.5 amu.  `ConstraintSet.ndof()` counts the degrees of freedom the reported temperature
 divides by: 3 N minus the number of constraints (a rigid water counts 3), the centre-of-mass motion not subtracted.
 
+Virtual sites (`vsites.VirtualSites`) are no atoms here: a massless site is never a hydrogen, every bond or angle
+that touches one is ignored, and a site adds no degrees of freedom (ndof = 3 (N - N_sites) - N_constraints).  Every site's
+parents must be the three atoms of one rigid water, the heavy atom first: the water's thread of the constrained MD step
+carries the site (`ConstraintSet.water_sites`).
+
 The start-up projection of `Integrator` (`shake_positions`, `project_velocities`) is vectorised over the units: constraint
 slot k of every unit at once (the units touch disjoint atoms), Gauss-Seidel over the slots.
 """
@@ -50,7 +55,9 @@ class ConstraintSet:
     dist        float64        per entry of `atoms`: the bond length to the central atom (0 for the central atom)
     """
 
-    def __init__(self, natoms, masses, waters, water_dist, offsets, atoms, dist, mode):
+    def __init__(self, natoms, masses, waters, water_dist, offsets, atoms, dist, mode, nsites=0, water_sites=None):
+        self.nsites = int(nsites)  # massless virtual sites among the atoms: no degrees of freedom
+        self.water_sites = water_sites  # int32 [W]: the site each water carries, -1 = none (None: no sites at all)
         self.natoms = int(natoms)
         self.masses = np.asarray(masses, dtype=np.float64)
         self.waters = np.ascontiguousarray(waters, dtype=np.int32).reshape(-1, 3)
@@ -93,10 +100,10 @@ class ConstraintSet:
     def ndof(self, batch=None):
         """3 N - N_constraints, per atom group when `batch` (natoms,) assigns atoms to groups."""
         if batch is None:
-            return 3 * self.natoms - self.nconstraints
+            return 3 * (self.natoms - self.nsites) - self.nconstraints
         b = np.asarray(_host(batch), dtype=np.int64)
         ng = int(b.max()) + 1
-        dof = 3 * np.bincount(b, minlength=ng).astype(np.int64)
+        dof = 3 * np.bincount(b, weights=(self.masses > 0) if self.nsites else None, minlength=ng).astype(np.int64)
         ij, _ = self.pairs()
         if len(ij):
             if np.any(b[ij[:, 0]] != b[ij[:, 1]]):
@@ -122,9 +129,13 @@ class ConstraintSet:
             self._slot_cache = slots
         return self._slot_cache
 
+    def _inverse_masses(self):
+        # (massless virtual sites are in no constraint: their entry is never read)
+        return np.divide(1.0, self.masses, out=np.zeros_like(self.masses), where=self.masses > 0)
+
     def shake_positions(self, x, ref, tol=1e-13, max_iter=1000):
         """SHAKE `x` [N, 3] (fp64, in place) onto the constraints along the bond vectors of `ref`."""
-        im = 1.0 / self.masses
+        im = self._inverse_masses()
         slots = self._slots()
         for _ in range(max_iter):
             worst = 0.0
@@ -142,7 +153,7 @@ class ConstraintSet:
 
     def project_velocities(self, x, v, sweeps=200, tol=1e-14):
         """Remove the velocity components along every constraint (v [N, 3] fp64, in place), Gauss-Seidel over the slots."""
-        im = 1.0 / self.masses
+        im = self._inverse_masses()
         slots = self._slots()
         for _ in range(sweeps):
             worst = 0.0
@@ -160,17 +171,26 @@ class ConstraintSet:
         return v
 
 
-def find_constraints(masses, bond_params, angle_params=None, mode="water"):
+def find_constraints(masses, bond_params, angle_params=None, mode="water", virtual_sites=None):
     """Rigid waters (and, with mode="hbonds", X-H clusters) of a topology.  `masses` [N] or [N, 1]; `bond_params` /
-    `angle_params`: the `Parameters` tables ({"idx", "map", "params"}; params[:, 1] = req / theta0)."""
+    `angle_params`: the `Parameters` tables ({"idx", "map", "params"}; params[:, 1] = req / theta0).  `virtual_sites`: a
+    `vsites.VirtualSites` — the sites, and every bond or angle that touches one, are left out of the search; every site's
+    parents must then be the atoms of one rigid water (heavy atom first), whose hydrogens are listed in the parents' order."""
     if mode not in MODES:
         raise ValueError(f"constraints must be None, 'water' or 'hbonds', got {mode!r}")
     m = np.asarray(_host(masses), dtype=np.float64).reshape(-1)
     n = len(m)
-    hyd = m < HYDROGEN_MASS
+    is_site = np.zeros(n, dtype=bool)
+    if virtual_sites is not None and virtual_sites.nsites:
+        virtual_sites.check_masses(m)
+        is_site = virtual_sites.site_mask(n)
+    hyd = (m < HYDROGEN_MASS) & ~is_site
     bidx, bprm = _table(bond_params, 2)
     breq = bprm[:, 1] if len(bprm) else np.zeros(0)
-    bidx = bidx[bidx[:, 0] != bidx[:, 1]]
+    keep = (bidx[:, 0] != bidx[:, 1]) & ~is_site[bidx[:, 0]] & ~is_site[bidx[:, 1]]
+    if len(breq) == len(bidx):
+        breq = breq[keep]
+    bidx = bidx[keep]
     breq = breq[: len(bidx)] if len(breq) == len(bidx) else breq
     neigh = [dict() for _ in range(n)]  # atom -> {bonded atom: req}
     for (i, j), r in zip(bidx, breq):
@@ -179,13 +199,15 @@ def find_constraints(masses, bond_params, angle_params=None, mode="water"):
     aidx, aprm = _table(angle_params, 3)
     theta = {}
     for (i, j, k), p in zip(aidx, aprm):
+        if is_site[i] or is_site[j] or is_site[k]:
+            continue
         theta[(int(i), int(j), int(k))] = theta[(int(k), int(j), int(i))] = float(p[1])
 
     # rigid waters: a heavy atom bonded to exactly two hydrogens, which are bonded to nothing but it and each other
     in_water = np.zeros(n, dtype=bool)
     waters, wdist = [], []
     for o in range(n):
-        if hyd[o]:
+        if hyd[o] or is_site[o]:
             continue
         nb = list(neigh[o])
         if len(nb) != 2 or not (hyd[nb[0]] and hyd[nb[1]]):
@@ -227,5 +249,20 @@ def find_constraints(masses, bond_params, angle_params=None, mode="water"):
             atoms += [x] + hs
             dist += [0.0] + [neigh[x][h] for h in hs]
             offsets.append(len(atoms))
+    nsites, water_sites = 0, None
+    if is_site.any():
+        # every site rides with the rigid water its parents form
+        nsites = int(is_site.sum())
+        water_of = {int(w[0]): k for k, w in enumerate(waters)}
+        water_sites = -np.ones(len(waters), dtype=np.int32)
+        waters = [list(w) for w in waters]
+        for s, pa in zip(virtual_sites.sites, virtual_sites.parents):
+            k = water_of.get(int(pa[0]))
+            if k is None or pa[2] < 0 or {int(pa[1]), int(pa[2])} != {int(waters[k][1]), int(waters[k][2])} or water_sites[k] >= 0:
+                raise ValueError(f"constraints: the parents of virtual site {int(s)} must be exactly the three atoms of one rigid "
+                                 "water, the heavy atom first (sites on flexible molecules are supported by Forces.compute only)")
+            waters[k][1], waters[k][2] = int(pa[1]), int(pa[2])  # (SETTLE is symmetric in the hydrogens)
+            water_sites[k] = int(s)
     return ConstraintSet(n, m, np.asarray(waters, dtype=np.int32).reshape(-1, 3), np.asarray(wdist).reshape(-1, 2),
-                         np.asarray(offsets), np.asarray(atoms, dtype=np.int32), np.asarray(dist, dtype=np.float64), mode)
+                         np.asarray(offsets), np.asarray(atoms, dtype=np.int32), np.asarray(dist, dtype=np.float64), mode,
+                         nsites=nsites, water_sites=water_sites)

@@ -579,6 +579,7 @@ void tmdhip_destroy(tmdhip_ctx *ctx) {
   tmd::bonded_release(ctx);
   tmd::pme_release(ctx);
   tmd::cons_release(ctx);
+  tmd::vsite_release(ctx);
   delete ctx;
 }
 

@@ -502,6 +502,15 @@ struct DevBuf {
   }
 };
 
+// tmdhip_set_vsites: the site tables on the device (the layout of tmdhip_vsite_construct) and on the host (tmdhip_set_constraints
+// attaches every site to the rigid water it belongs to)
+struct VsiteState {
+  DevBuf site, parent, weight;
+  int nsites = 0;
+  std::vector<int32_t> site_h, parent_h;
+  std::vector<double> weight_h;
+};
+
 struct Replica {
   int64_t step = 0;
   int64_t n_compute = 0;
@@ -626,6 +635,8 @@ struct tmdhip_ctx {
   double pme_beta = 0;
   // holonomic constraints of the MD loop (tmdhip_set_constraints), md_loop.hip; null: off
   void *cons = nullptr;
+  // virtual sites the context's own launches serve (tmdhip_set_vsites), vsite.hip; null: none
+  void *vsites = nullptr;
   // timing of the dominant kernel
   bool timing = false;
   int timing_stride = 1;    // every n-th launch is timed
@@ -796,6 +807,8 @@ void pme_release(tmdhip_ctx *ctx);
 // stream (or for a report enqueued behind the steps).
 void cons_release(tmdhip_ctx *ctx);
 int cons_verdict(tmdhip_ctx *ctx);
+// vsite.hip
+void vsite_release(tmdhip_ctx *ctx);
 int64_t pme_evaluations(const tmdhip_ctx *ctx, int r);
 int64_t pme_bytes(const tmdhip_ctx *ctx);
 // md_loop.hip

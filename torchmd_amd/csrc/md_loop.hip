@@ -6,6 +6,7 @@
 #include "cons_math.h"
 #include "engine.h"
 #include "md_step.h"
+#include "vsite_math.h"
 
 namespace tmd {
 
@@ -112,22 +113,47 @@ struct ConsArgs {
   int *fail;  // host-mapped word: a unit did not converge (cons_verdict)
 };
 
+// Four-site rigid waters (tmdhip_set_vsites): the massless site of water w, or -1, and its weights in the order
+// O, H1, H2 — the order of the site's parent table.  The water's thread serves the site as well (md_step_cons_vs_kernel).
+struct ConsSiteArgs {
+  const int *wsite;       // [W]
+  const double *wweight;  // [W][3]
+};
+
 struct ConsState {
   DevBuf units, water, wdist, coff, catom, cdist;
+  DevBuf wsite, wweight;  // (only with sites)
+  bool has_sites = false;
   int nunits = 0;
   double tol = 1e-10;
   int max_iter = 200;
   int *fail_host = nullptr;
 };
 
-template <typename R, bool SECOND, bool LANGEVIN, bool FIRST, bool CHECK, int NA, int NC, bool WATER>
+// VS (waters only): the unit also carries the massless site `site` with weights sw (parents O, H1, H2 in this order) — its force
+// is folded into the parents' before anything divides by a mass, the site is placed from the parents' positions as stored, and
+// it gets what every atom gets but an update: f_zero, the entry snapshot, the cell-sorted record, the displacement test;
+// velocity 0.  Nothing here reads the site's mass or draws noise for it.
+template <typename R, bool SECOND, bool LANGEVIN, bool FIRST, bool CHECK, int NA, int NC, bool WATER, bool VS = false>
 __device__ __forceinline__ void cons_unit(const MdStepArgs<R> &s, const PairConsts<R> &c, const ConsArgs &k, const int (&at)[NA],
-                                          const double (&d)[NA], size_t off, uint64_t row0) {
+                                          const double (&d)[NA], size_t off, uint64_t row0, int site = -1, const double *sw = nullptr) {
 #pragma clang fp contract(off)
+  static_assert(!VS || (WATER && NA == 3), "a site belongs to a rigid water");
   using R4 = typename Vec<R>::T4;
   const R *vel = s.vel + off, *f = s.f + off, *pin = s.pos_in + off;
   R *pout = s.pos_out + off, *vout = s.vel + off;
   AtomIn<R> x[NA];
+  AtomIn<R> xs{};  // the site: force, and with FIRST && CHECK reference point, limit, charge and slot (p, v: entry snapshot only)
+  if constexpr (VS) {
+#pragma unroll
+    for (int q = 0; q < 3; ++q) {
+      xs.f[q] = f[3 * site + q];
+      xs.r[q] = (FIRST && CHECK) ? s.chk.ref[3 * site + q] : R(0);
+    }
+    xs.q = (FIRST && CHECK) ? s.qs[site] : R(0);
+    xs.h2 = (FIRST && CHECK) ? list_check_limit(s.chk, site) : R(0);
+    xs.slot = (FIRST && CHECK) ? s.inv[site] : 0;
+  }
 #pragma unroll
   for (int j = 0; j < NA; ++j) {  // every load first (md_load_atom), the positions also without a drift (velocity constraint)
     const int i = at[j];
@@ -157,6 +183,15 @@ __device__ __forceinline__ void cons_unit(const MdStepArgs<R> &s, const PairCons
         }
         if (s.zero && i < s.nzero) s.zero[i] = 0.0;
       }
+      if constexpr (VS) {
+#pragma unroll
+        for (int q = 0; q < 3; ++q) {
+          s.snap_pos[3 * site + q] = pin[3 * site + q];
+          s.snap_vel[3 * site + q] = vel[3 * site + q];
+          s.snap_f[3 * site + q] = xs.f[q];
+        }
+        if (s.zero && site < s.nzero) s.zero[site] = 0.0;
+      }
     }
   }
   if (s.f_zero) {
@@ -165,6 +200,16 @@ __device__ __forceinline__ void cons_unit(const MdStepArgs<R> &s, const PairCons
     for (int j = 0; j < NA; ++j)
 #pragma unroll
       for (int q = 0; q < 3; ++q) fz[3 * at[j] + q] = R(0);
+    if constexpr (VS) {
+#pragma unroll
+      for (int q = 0; q < 3; ++q) fz[3 * site + q] = R(0);
+    }
+  }
+  if constexpr (VS) {  // what tmdhip_vsite_spread stores in the parents' rows, rounding included
+#pragma unroll
+    for (int j = 0; j < NA; ++j)
+#pragma unroll
+      for (int q = 0; q < 3; ++q) x[j].f[q] = vsite_share<R>(x[j].f[q], sw[j], xs.f[q]);
   }
   const double dt = (double)s.dt, hdt = (double)s.half_dt, gamma = (double)s.gamma;
   double p[NA][3], v[NA][3], a[NA][3], im[NA];
@@ -206,6 +251,7 @@ __device__ __forceinline__ void cons_unit(const MdStepArgs<R> &s, const PairCons
     if constexpr (WATER) ok = settle_water(p, xn, (double)x[0].m, (double)x[1].m, d[0], d[1]);
     else if constexpr (NC > 0) ok = shake_cluster<NA>(p, xn, im, d, k.tol, k.max_iter);
     if (!ok) *k.fail = 1;
+    R stored[VS ? NA : 1][3];  // (VS) the parents' positions as rounded for storage
 #pragma unroll
     for (int j = 0; j < NA; ++j) {
       const int i = at[j];
@@ -215,6 +261,7 @@ __device__ __forceinline__ void cons_unit(const MdStepArgs<R> &s, const PairCons
         if (NC > 0) v[j][q] += (xn[j][q] - u[j][q]) / dt;
         pr[q] = (R)xn[j][q];
         pout[3 * i + q] = pr[q];
+        if constexpr (VS) stored[j][q] = pr[q];
       }
       if (CHECK) {
         R4 sv;
@@ -227,11 +274,33 @@ __device__ __forceinline__ void cons_unit(const MdStepArgs<R> &s, const PairCons
         list_check_point<R>(s.chk, c, pr[0] - x[j].r[0], pr[1] - x[j].r[1], pr[2] - x[j].r[2], x[j].h2);
       }
     }
+    if constexpr (VS) {  // the site, from the stored parents: tmdhip_vsite_construct's expression
+      R pr[3];
+#pragma unroll
+      for (int q = 0; q < 3; ++q) {
+        pr[q] = vsite_coord<R>(sw[0], sw[1], sw[2], stored[0][q], stored[1][q], stored[2][q], true);
+        pout[3 * site + q] = pr[q];
+      }
+      if (CHECK) {
+        R4 sv;
+        sv.x = pr[0];
+        sv.y = pr[1];
+        sv.z = pr[2];
+        sv.w = xs.q;
+        s.sorted[xs.slot] = sv;
+        extent_note<R>(s.chk.ext, pr[0], pr[1], pr[2]);
+        list_check_point<R>(s.chk, c, pr[0] - xs.r[0], pr[1] - xs.r[1], pr[2] - xs.r[2], xs.h2);
+      }
+    }
   }
 #pragma unroll
   for (int j = 0; j < NA; ++j)
 #pragma unroll
     for (int q = 0; q < 3; ++q) vout[3 * at[j] + q] = (R)v[j][q];
+  if constexpr (VS) {
+#pragma unroll
+    for (int q = 0; q < 3; ++q) vout[3 * site + q] = R(0);
+  }
 }
 
 template <typename R, bool SECOND, bool LANGEVIN, bool FIRST, bool CHECK, int NA>
@@ -275,6 +344,40 @@ __global__ __launch_bounds__(256) void md_step_cons_kernel(MdStepArgs<R> s, Pair
   }
 }
 
+// The same for a context with virtual sites: a water with a site is stepped together with it.
+template <typename R, bool SECOND, bool LANGEVIN, bool FIRST, bool CHECK>
+__global__ __launch_bounds__(256) void md_step_cons_vs_kernel(MdStepArgs<R> s, PairConsts<R> c, ConsArgs k, ConsSiteArgs vs) {
+  const int u = blockIdx.x * blockDim.x + threadIdx.x;
+  if (CHECK && u == 0) list_check_clear(s.chk.flags, s.chk.parity);
+  if (u >= k.nunits) return;
+  const size_t off = CHECK ? 0 : (size_t)blockIdx.y * 3 * s.n;
+  const uint64_t row0 = s.row0 + (CHECK ? 0 : (uint64_t)blockIdx.y * (uint64_t)s.n);
+  const int2 e = k.units[u];
+  if (e.x == kConsWater) {
+    const int at[3] = {k.water[3 * e.y], k.water[3 * e.y + 1], k.water[3 * e.y + 2]};
+    const double d[3] = {k.wdist[2 * e.y], k.wdist[2 * e.y + 1], 0.0};
+    const int site = vs.wsite[e.y];
+    if (site >= 0) {
+      const double sw[3] = {vs.wweight[3 * e.y], vs.wweight[3 * e.y + 1], vs.wweight[3 * e.y + 2]};
+      cons_unit<R, SECOND, LANGEVIN, FIRST, CHECK, 3, 3, true, true>(s, c, k, at, d, off, row0, site, sw);
+    } else {
+      cons_unit<R, SECOND, LANGEVIN, FIRST, CHECK, 3, 3, true>(s, c, k, at, d, off, row0);
+    }
+  } else if (e.x == kConsCluster) {
+    const int s0 = k.coff[e.y], na = k.coff[e.y + 1] - s0;
+    switch (na) {
+      case 2: cons_cluster<R, SECOND, LANGEVIN, FIRST, CHECK, 2>(s, c, k, s0, off, row0); break;
+      case 3: cons_cluster<R, SECOND, LANGEVIN, FIRST, CHECK, 3>(s, c, k, s0, off, row0); break;
+      case 4: cons_cluster<R, SECOND, LANGEVIN, FIRST, CHECK, 4>(s, c, k, s0, off, row0); break;
+      default: cons_cluster<R, SECOND, LANGEVIN, FIRST, CHECK, 5>(s, c, k, s0, off, row0); break;
+    }
+  } else {
+    const int at[1] = {e.y};
+    const double d[1] = {0.0};
+    cons_unit<R, SECOND, LANGEVIN, FIRST, CHECK, 1, 0, false>(s, c, k, at, d, off, row0);
+  }
+}
+
 static ConsArgs cons_args(const tmdhip_ctx *ctx) {
   const ConsState *S = (const ConsState *)ctx->cons;
   ConsArgs k;
@@ -294,7 +397,7 @@ static ConsArgs cons_args(const tmdhip_ctx *ctx) {
 void cons_release(tmdhip_ctx *ctx) {
   ConsState *S = (ConsState *)ctx->cons;
   if (!S) return;
-  for (DevBuf *b : {&S->units, &S->water, &S->wdist, &S->coff, &S->catom, &S->cdist}) b->release();
+  for (DevBuf *b : {&S->units, &S->water, &S->wdist, &S->coff, &S->catom, &S->cdist, &S->wsite, &S->wweight}) b->release();
   if (S->fail_host) (void)hipHostFree(S->fail_host);
   delete S;
   ctx->cons = nullptr;
@@ -449,6 +552,15 @@ void launch_step(const tmdhip_ctx *ctx, const MdStepArgs<R> &a, const PairConsts
   if (!ctx->cons) return launch_md_step<R, SECOND, LANGEVIN, FIRST>(a, c, check, st, nrep);
   const ConsArgs k = cons_args(ctx);
   const dim3 grid((k.nunits + 255) / 256, check ? 1 : nrep), block(256);
+  const ConsState *S = (const ConsState *)ctx->cons;
+  if (S->has_sites) {
+    const ConsSiteArgs vs{S->wsite.as<int>(), S->wweight.as<double>()};
+    if (check)
+      hipLaunchKernelGGL((md_step_cons_vs_kernel<R, SECOND, LANGEVIN, FIRST, true>), grid, block, 0, st, a, c, k, vs);
+    else
+      hipLaunchKernelGGL((md_step_cons_vs_kernel<R, SECOND, LANGEVIN, FIRST, false>), grid, block, 0, st, a, c, k, vs);
+    return;
+  }
   if (check)
     hipLaunchKernelGGL((md_step_cons_kernel<R, SECOND, LANGEVIN, FIRST, true>), grid, block, 0, st, a, c, k);
   else
@@ -1186,6 +1298,9 @@ int tmdhip_md_run(tmdhip_ctx *ctx, const tmdhip_md_desc *desc, void *stream) {
   if (!desc->pos_dev || !desc->vel_dev || !desc->forces_dev || !desc->mass_dev || !desc->box_host)
     return fail("tmdhip_md_run: null buffer");
   if (desc->niter == 0) return 0;
+  if (ctx->vsites && !(ctx->cons && ((const ConsState *)ctx->cons)->has_sites))
+    return fail("tmdhip_md_run: a context with virtual sites steps them with their rigid waters: set the constraints "
+                "(tmdhip_set_constraints after tmdhip_set_vsites)");
   hipStream_t st = (hipStream_t)stream;
   const int nzero = (int)(TMDHIP_NENERGY * ctx->rep.size());
   bool zeroed = desc->energies_dev == nullptr;
@@ -1216,6 +1331,13 @@ int tmdhip_md_run(tmdhip_ctx *ctx, const tmdhip_md_desc *desc, void *stream) {
   for (auto &rp : ctx->rep) rp.spec_valid = false;  // (a plain evaluation's report says nothing about positions this call moves)
   const int rc = ctx->d.dtype == TMDHIP_F32 ? md_run<float>(ctx, desc, st) : md_run<double>(ctx, desc, st);
   for (auto &rp : ctx->rep) rp.skin_vel = nullptr;  // rebuilds outside an MD run know no velocities: static skins
+  if (rc == 0 && ctx->vsites) {
+    // the forces of the last step leave the call spread (zero site rows), as a plain evaluation leaves them; the final kick has
+    // folded the same shares in registers
+    const VsiteState *V = (const VsiteState *)ctx->vsites;
+    TMD_TRY(tmdhip_vsite_spread(ctx->d.dtype, (int64_t)ctx->rep.size(), ctx->d.natoms, desc->forces_dev, V->nsites, V->site.as<int32_t>(),
+                                V->parent.as<int32_t>(), V->weight.as<double>(), stream));
+  }
   if (rc == 0 && ctx->snap_pending) {
     ctx->snap_pending = false;
     return fail("tmdhip_md_run: the state at entry was not saved (internal error)");
@@ -1337,6 +1459,26 @@ int tmdhip_set_constraints(tmdhip_ctx *ctx, const tmdhip_constraint_desc *desc) 
     }
     units.push_back({lo, make_int2(kConsCluster, q)});
   }
+  // virtual sites: each belongs to the water whose O, H1, H2 are its parents (in this order), and is no unit of its own
+  const VsiteState *V = (const VsiteState *)ctx->vsites;
+  std::vector<int32_t> wsite;
+  std::vector<double> wweight;
+  if (V) {
+    std::vector<int> water_of(n, -1);
+    for (int w = 0; w < nw; ++w) water_of[desc->water_host[3 * w]] = w;
+    wsite.assign(nw, -1);
+    wweight.assign(3 * (size_t)nw, 0.0);
+    for (int s = 0; s < V->nsites; ++s) {
+      const int32_t *pa = V->parent_h.data() + 3 * (size_t)s;
+      const int w = (pa[0] >= 0 && pa[0] < n) ? water_of[pa[0]] : -1;
+      if (w < 0 || wsite[w] >= 0 || pa[1] != desc->water_host[3 * w + 1] || pa[2] != desc->water_host[3 * w + 2])
+        return fail("tmdhip_set_constraints: the parents of virtual site " + std::to_string(V->site_h[s]) +
+                    " are not the O, H1, H2 (in this order) of one rigid water");
+      TMD_TRY(take(V->site_h[s], 3));
+      wsite[w] = V->site_h[s];
+      for (int k = 0; k < 3; ++k) wweight[3 * (size_t)w + k] = V->weight_h[3 * (size_t)s + k];
+    }
+  }
   for (int i = 0; i < n; ++i)
     if (owner[i] < 0) units.push_back({i, make_int2(kConsAtom, i)});
   std::sort(units.begin(), units.end(), [](const std::pair<int, int2> &x, const std::pair<int, int2> &y) { return x.first < y.first; });
@@ -1356,6 +1498,11 @@ int tmdhip_set_constraints(tmdhip_ctx *ctx, const tmdhip_constraint_desc *desc) 
   if (!rc) rc = up(S->coff, desc->cluster_offsets_host, nc ? sizeof(int32_t) * (nc + 1) : 0);
   if (!rc) rc = up(S->catom, desc->cluster_atoms_host, sizeof(int32_t) * ncat);
   if (!rc) rc = up(S->cdist, desc->cluster_dist_host, sizeof(double) * ncat);
+  if (!rc && V && nw) {
+    rc = up(S->wsite, wsite.data(), sizeof(int32_t) * nw);
+    if (!rc) rc = up(S->wweight, wweight.data(), sizeof(double) * 3 * nw);
+    S->has_sites = !rc;
+  }
   if (!rc && hipHostMalloc((void **)&S->fail_host, 64, hipHostMallocMapped) != hipSuccess) rc = fail("tmdhip_set_constraints: hipHostMalloc failed");
   if (rc) {
     cons_release(ctx);

@@ -605,6 +605,8 @@ class DomainSet:
                  dry=False, **engine_kwargs):
         if engine_kwargs.get("pme"):
             raise ValueError("PME electrostatics cannot be domain-decomposed (no distributed FFT)")
+        if engine_kwargs.get("virtual_sites") is not None:
+            raise ValueError("virtual sites cannot be domain-decomposed (a site and its parents would straddle bricks)")
         self.dry = bool(dry)  # CPU tensors, no force engine (DryDomain): the plumbing of an N-rank run without a GPU
         self.grid = BrickGrid(box, world, grid)
         self.device, self.dtype = torch.device(device), dtype

@@ -197,6 +197,19 @@ class _Engine:
             L.check(lib.tmdhip_set_bonded(self.ctx, C.byref(b)), "tmdhip_set_bonded")
         self.has_nonbonded = terms != 0
         self._constraints = None
+        # virtual sites: the tables on the device for the stateless kernels around every evaluation, and in the context for
+        # the launches of tmdhip_md_run (before any constraints: tmdhip_set_constraints attaches the sites to their waters)
+        self.vsites = None
+        vs = owner.virtual_sites
+        if vs is not None and vs.nsites:
+            self.vsites = (vs.nsites, torch.as_tensor(vs.sites, device=device), torch.as_tensor(vs.parents, device=device),
+                           torch.as_tensor(vs.weights, device=device))
+            vd = L.VsiteDesc()
+            vd.struct_size = C.sizeof(L.VsiteDesc)
+            vd.enable = 1
+            vd.nsites = vs.nsites
+            vd.site_host, vd.parent_host, vd.weight_host = ptr(vs.sites), ptr(vs.parents), ptr(vs.weights)
+            L.check(lib.tmdhip_set_vsites(self.ctx, C.byref(vd)), "tmdhip_set_vsites")
         st = L.Stats()
         L.check(lib.tmdhip_get_stats(self.ctx, 0, C.byref(st)), "tmdhip_get_stats")
         # the nonbonded kernels *store* forces when asked to (the cell-list pair kernel owns every atom
@@ -234,6 +247,24 @@ class _Engine:
             d.max_iter = cs.max_iter
         L.check(self.lib.tmdhip_set_constraints(self.ctx, C.byref(d)), "tmdhip_set_constraints")
         self._constraints = cs
+
+    def place_sites(self, pos):
+        """tmdhip_vsite_construct on the current stream: the site rows of `pos` [R, N, 3], in place."""
+        if self.vsites is None:
+            return
+        ns, site, parent, weight = self.vsites
+        L.check(self.lib.tmdhip_vsite_construct(L.dtype_code(pos.dtype), pos.shape[0], pos.shape[1], pos.data_ptr(), ns, site.data_ptr(),
+                                                parent.data_ptr(), weight.data_ptr(),
+                                                C.c_void_p(torch.cuda.current_stream(pos.device).cuda_stream)), "tmdhip_vsite_construct")
+
+    def spread_sites(self, forces):
+        """tmdhip_vsite_spread on the current stream: parents += w F_site, site rows = 0."""
+        if self.vsites is None:
+            return
+        ns, site, parent, weight = self.vsites
+        L.check(self.lib.tmdhip_vsite_spread(L.dtype_code(forces.dtype), forces.shape[0], forces.shape[1], forces.data_ptr(), ns,
+                                             site.data_ptr(), parent.data_ptr(), weight.data_ptr(),
+                                             C.c_void_p(torch.cuda.current_stream(forces.device).cuda_stream)), "tmdhip_vsite_spread")
 
     def close(self):
         if self.ctx:
@@ -283,6 +314,12 @@ class Forces:
     pme_grid              (nx, ny, nz) overrides the grid
     switch_mode : str     "reference" (upstream's explicit switching force, extra 1/r,
                           forces.py:410-412) | "exact" (-dE/dr)
+    virtual_sites         a `vsites.VirtualSites`: massless linear sites (the M site of four-site water).  Every
+                          evaluation first places the sites — `compute()` WRITES THE SITE ROWS OF `pos`, in place —, then
+                          evaluates with the site an ordinary charged / LJ atom (pair search, PME and the exclusion correction
+                          all see it), then hands every site's force to its parents: the forces returned have zero site
+                          rows.  Every (site, parent) pair is excluded.  Not with `explicit_forces=False`, `torch.vmap`,
+                          `update_atoms` or the domain decomposition.
     """
 
     bonded = ["bonds", "angles", "dihedrals", "impropers", "1-4"]
@@ -308,6 +345,7 @@ class Forces:
         ewald_tolerance=5e-4,
         pme_order=5,
         pme_grid=None,
+        virtual_sites=None,
     ):
         self.par = parameters
         if terms is None:
@@ -374,9 +412,18 @@ class Forces:
         self.skin_weights = skin_weights
         self.algorithm = algorithm
         self.switch_mode = switch_mode
-        self._excl_csr = build_exclusion_csr(
-            self.natoms, parameters.get_exclusions(exclusions) if self.require_distances else []
-        )
+        self.virtual_sites = virtual_sites
+        excl = parameters.get_exclusions(exclusions) if self.require_distances else []
+        if virtual_sites is not None:
+            from .vsites import VirtualSites
+
+            if not isinstance(virtual_sites, VirtualSites):
+                raise ValueError("virtual_sites must be a vsites.VirtualSites")
+            virtual_sites.check_masses(parameters.masses)
+            if self.require_distances and virtual_sites.nsites:
+                # a union: nothing changes when the topology excludes the pairs already
+                excl = list(excl) + virtual_sites.exclusion_pairs().tolist()
+        self._excl_csr = build_exclusion_csr(self.natoms, excl)
         self._engines = {}
         self._box_cache = None
         self._ava_idx = None
@@ -390,6 +437,11 @@ class Forces:
             if sw != "mass":
                 raise ValueError("skin_weights must be 'mass', None or an array of per-atom weights")
             m = np.asarray(self.par.masses.detach().cpu().numpy(), dtype=np.float64).ravel()
+            vs = self.virtual_sites
+            if vs is not None and vs.nsites and len(m) == self.natoms:
+                # a massless site moves with its parents: it takes the weight of the first one (never a division by its mass)
+                m = m.copy()
+                m[vs.sites] = m[vs.parents[:, 0]]
             if len(m) != self.natoms or not (m > 0).all() or m.min() == m.max():
                 return None
             return np.maximum((m.min() / m) ** 0.45, 0.2)
@@ -403,6 +455,8 @@ class Forces:
         with the same LJ table but other atoms (count, types, charges) — keeping the device contexts and
         their buffers; atoms with index >= `nactive` become passive (they act on the others but get no
         neighbour list and zero force).  Used by the domain decomposition at every atom migration."""
+        if self.virtual_sites is not None:
+            raise ValueError("update_atoms is not available with virtual_sites")
         if any(t in self.energies for t in self.bonded) or len(self._excl_csr[1]):
             raise RuntimeError("update_atoms is only available for atomic systems")
         self.par = parameters
@@ -568,12 +622,17 @@ class Forces:
         self._pme_box(self._host_box(box))
         eng = self._engine(p, exact)
         with torch.cuda.device(p.device):
+            eng.place_sites(p)  # first launch (no-op without virtual sites)
             for _ in range(4):
                 self._launch(eng, p, box, forces, want_energy, want_forces, count_pairs)
                 if not (want_energy or count_pairs) or self._verify(eng, p):
                     break
             else:
                 raise RuntimeError("neighbour list kept overflowing; increase `skin` capacity")
+            if want_forces:
+                eng.spread_sites(forces)  # last launch
+            if eng.vsites is not None and p.data_ptr() != pos.data_ptr():
+                pos.detach().copy_(p)  # (a non-contiguous `pos` was evaluated through a copy: the sites go back)
         if target is not None:
             target.copy_(forces)
         return eng.ebuf
@@ -604,6 +663,7 @@ class Forces:
         out = np.empty((R, L.NENERGY), dtype=np.float64)
         with torch.cuda.device(p.device):
             stream = C.c_void_p(torch.cuda.current_stream(p.device).cuda_stream)
+            eng.place_sites(p)  # first launch (no-op without virtual sites)
             for _ in range(4):
                 rc = L.check(
                     eng.lib.tmdhip_compute(
@@ -617,6 +677,10 @@ class Forces:
                     break
             else:
                 raise RuntimeError("neighbour list kept overflowing; increase `skin` capacity")
+            if forces is not None:
+                eng.spread_sites(forces)  # last launch
+            if eng.vsites is not None and p.data_ptr() != pos.data_ptr():
+                pos.detach().copy_(p)  # (a non-contiguous `pos` was evaluated through a copy: the sites go back)
         if target is not None:
             target.copy_(forces)
         return out
@@ -632,6 +696,12 @@ class Forces:
         toNumpy=True,
         calculateForces=True,
     ):
+        if self.virtual_sites is not None:
+            if _is_batched(pos):
+                raise ValueError("compute() with virtual_sites cannot run under torch.vmap (the sites are written into `pos` in place)")
+            if not explicit_forces:
+                raise ValueError("virtual_sites need explicit_forces=True (the autograd path would differentiate with respect "
+                                 "to site rows that are no degrees of freedom)")
         if _is_batched(pos):  # called under torch.vmap (reference tests/test_torchmd.py:590-598)
             return self._compute_vmapped(pos, box, forces, returnDetails, explicit_forces, toNumpy, calculateForces)
         if calculateForces:

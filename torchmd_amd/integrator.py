@@ -129,6 +129,7 @@ class Integrator:
             if gamma is None:
                 raise RuntimeError("Langevin temperature T requires a friction gamma")
             self.vcoeff = torch.sqrt(2.0 * gamma / self.masses * BOLTZMAN * T * self.dt).to(device).contiguous()
+            self.vcoeff[self.masses == 0] = 0.0  # (massless virtual sites: no noise, and no division by their mass)
         self.batch = batch
         if batch is not None:
             self.natoms = torch.bincount(batch).cpu().numpy()
@@ -139,6 +140,12 @@ class Integrator:
         self._nstep = 0
         self._ke = None
         self.constraints = None  # constraints.ConstraintSet
+        self.virtual_sites = getattr(forces, "virtual_sites", None)
+        if self.virtual_sites is not None and not self.virtual_sites.nsites:
+            self.virtual_sites = None
+        if self.virtual_sites is not None and constraints is None:
+            raise ValueError("a Forces with virtual_sites is integrated with constraints='water' or 'hbonds' only: a site is "
+                             "stepped as part of its rigid water (sites on flexible molecules: Forces.compute only)")
         if constraints is not None:
             self._init_constraints(constraints)
         self.replays = 0  # batches that were rewound and repeated (list validity failure / step-block time-out)
@@ -155,7 +162,7 @@ class Integrator:
                              "duck-typed force objects and external forces are not supported")
         par = self.forces.par
         self.constraints = find_constraints(self.masses.detach().cpu().double().reshape(-1).numpy(), par.bond_params,
-                                            getattr(par, "angle_params", None), mode)
+                                            getattr(par, "angle_params", None), mode, virtual_sites=self.virtual_sites)
         self._ndof = self.constraints.ndof(self.batch)
         self._projected = False
 
@@ -174,6 +181,9 @@ class Integrator:
             ref = pos[r].copy()
             cs.shake_positions(pos[r], ref)
             cs.project_velocities(pos[r], vel[r])
+            if self.virtual_sites is not None:  # sites on the projected parents, at rest (maxwell_boltzmann gave them inf)
+                self.virtual_sites.construct(pos[r])
+                vel[r][self.virtual_sites.sites] = 0.0
         s.pos.copy_(torch.as_tensor(pos).to(s.pos.dtype))
         s.vel.copy_(torch.as_tensor(vel).to(s.vel.dtype))
         self.forces.compute(s.pos, s.box, s.forces)

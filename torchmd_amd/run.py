@@ -45,6 +45,7 @@ DEFAULTS = dict(
     constraints=None,  # None, "water" (rigid waters) or "hbonds" (rigid waters and X-H bonds): DESIGN §10
     barostat_pressure=None,  # bar; None: constant volume.  Monte Carlo barostat at langevin_temperature: DESIGN §11
     barostat_frequency=25,  # steps between two volume moves
+    virtual_sites=None,  # None or "tip4p": four-site waters O,H1,H2,M; geometry from the force field's `virtual_sites` section: DESIGN §12
 )
 
 
@@ -77,6 +78,10 @@ def get_args(arguments=None):
         args.constraints = None
     if args.constraints not in (None, "water", "hbonds"):
         raise ValueError(f"constraints must be None, 'water' or 'hbonds', got {args.constraints!r}")
+    if isinstance(args.virtual_sites, str) and args.virtual_sites.lower() in ("none", "null", ""):
+        args.virtual_sites = None
+    if args.virtual_sites not in (None, "tip4p"):
+        raise ValueError(f"virtual_sites must be None or 'tip4p', got {args.virtual_sites!r}")
     if isinstance(args.barostat_pressure, str) and args.barostat_pressure.lower() in ("none", "null", ""):
         args.barostat_pressure = None
     if args.barostat_pressure is not None:
@@ -184,11 +189,28 @@ def setup(args):
     system = System(mol.numAtoms, args.replicas, precision, device)
     system.set_positions(mol.coords)
     system.set_box(mol.box)
-    system.set_velocities(maxwell_boltzmann(parameters.masses, args.temperature, args.replicas))
+    vel = maxwell_boltzmann(parameters.masses, args.temperature, args.replicas)
+    vsites = None
+    if args.virtual_sites == "tip4p":
+        vsites = tip4p_sites(ff, mol)
+        vel[:, torch.as_tensor(vsites.sites, dtype=torch.long)] = 0.0  # (massless: the draw divided by zero)
+    system.set_velocities(vel)
+    extra = {} if vsites is None else {"virtual_sites": vsites}
     forces = Forces(parameters, terms=terms, external=external, cutoff=args.cutoff, rfa=args.rfa,
                     switch_dist=args.switch_dist, exclusions=tuple(args.exclusions), pme=args.pme,
-                    ewald_tolerance=args.ewald_tolerance, pme_order=args.pme_order, pme_grid=args.pme_grid)
+                    ewald_tolerance=args.ewald_tolerance, pme_order=args.pme_order, pme_grid=args.pme_grid, **extra)
     return mol, system, forces
+
+
+def tip4p_sites(ff, mol):
+    """`virtual_sites: tip4p` — the M sites of a system of four-site waters (atom order O,H1,H2,M), with the geometry the
+    force-field file states: `virtual_sites: {tip4p: {r_om: ..., r_oh: ..., theta: ...}}` (Angstrom, degrees)."""
+    from .vsites import VirtualSites
+
+    geo = ((getattr(ff, "prm", None) or {}).get("virtual_sites") or {}).get("tip4p")
+    if not geo or not all(k in geo for k in ("r_om", "r_oh", "theta")):
+        raise ValueError("virtual_sites: tip4p needs a `virtual_sites: {tip4p: {r_om, r_oh, theta}}` section in the force-field file")
+    return VirtualSites.tip4p(mol, geo["r_om"], geo["r_oh"], geo["theta"])
 
 
 class FrameStager:
