@@ -373,6 +373,34 @@ int tmdhip_vsite_construct(int dtype, int64_t nreplicas, int64_t natoms, void *p
                            const int32_t *parent_dev, const double *weight_dev, void *stream);
 int tmdhip_vsite_spread(int dtype, int64_t nreplicas, int64_t natoms, void *forces_dev, int32_t nsites, const int32_t *site_dev,
                         const int32_t *parent_dev, const double *weight_dev, void *stream);
+/* FIRE energy minimisation, stateless (added to ABI 11): one iteration of every replica from forces that are already in
+ * forces_dev.  Bitzek et al., PRL 97, 170201 (2006), with a semi-implicit Euler step on the real masses and a per-atom step cap.
+ * state_dev is double [R][2][TMDHIP_FIRE_STATE_DOUBLES]: two slots per replica, each {dt, alpha, npos, done, iterations, fmax,
+ * nuphill, 0} (the counters are whole numbers held as doubles).  tmdhip_fire_init writes {dt_start, alpha_start, 0, ...} into
+ * both slots.  tmdhip_fire_step reads slot `iteration & 1` and writes the other one, so after k calls with iteration = 0 .. k-1
+ * the live slot is k & 1.  partials_dev is scratch, double [R][TMDHIP_FIRE_MAX_BLOCKS][4].
+ * For a replica that is not done (all sums over the rows with mass > 0; rows with mass == 0 are neither read nor written):
+ *   1. fmax = max_i |F_i|; if fmax < f_tol: done = 1 and nothing moves (`iterations` keeps the number of moves made so far).
+ *   2. P = sum F.v, vv = sum v.v, ff = sum F.F.  P > 0: v = (1 - alpha) v + alpha sqrt(vv / ff) F, npos += 1, and if npos > n_min:
+ *      dt = min(dt * f_inc, dt_max), alpha *= f_alpha.  Otherwise v = 0, dt *= f_dec, alpha = alpha_start, npos = 0, nuphill += 1.
+ *   3. v += dt F / m; if |v_i| dt > max_step: v_i *= (max_step / dt) / |v_i|; x += dt v; iterations += 1.
+ * A done replica is never written again.  Two launches (a reduction into per-block partials, an update whose blocks all re-sum
+ * the partials in one order), sums and state arithmetic in double in both precisions, no atomics: two runs give the same bits. */
+#define TMDHIP_FIRE_STATE_DOUBLES 8
+#define TMDHIP_FIRE_MAX_BLOCKS 256
+typedef struct tmdhip_fire_params {
+  int32_t struct_size; /* = sizeof(tmdhip_fire_params) */
+  int32_t n_min;
+  double f_tol;    /* force units of forces_dev */
+  double dt_start; /* time units in which dt * F / m is a velocity and dt * v a length */
+  double dt_max;
+  double max_step; /* length: the largest move of one atom in one iteration */
+  double f_inc, f_dec, alpha_start, f_alpha;
+} tmdhip_fire_params;
+int tmdhip_fire_init(int64_t nreplicas, double *state_dev, const tmdhip_fire_params *params, void *stream);
+int tmdhip_fire_step(int dtype, int64_t nreplicas, int64_t natoms, void *pos_dev, void *vel_dev, const void *forces_dev,
+                     const void *mass_dev, double *state_dev, double *partials_dev, const tmdhip_fire_params *params,
+                     int64_t iteration, void *stream);
 /* Fill `out_dev` (real [n]) with the N(0,1) stream used by tmdhip_langevin_second_vv (for tests). */
 int tmdhip_normal_fill(int dtype, int64_t n, void *out_dev, uint64_t seed, uint64_t step, void *stream);
 

@@ -246,6 +246,24 @@ class VsiteDesc(C.Structure):
     ]
 
 
+class FireParams(C.Structure):
+    _fields_ = [
+        ("struct_size", C.c_int32),
+        ("n_min", C.c_int32),
+        ("f_tol", C.c_double),
+        ("dt_start", C.c_double),
+        ("dt_max", C.c_double),
+        ("max_step", C.c_double),
+        ("f_inc", C.c_double),
+        ("f_dec", C.c_double),
+        ("alpha_start", C.c_double),
+        ("f_alpha", C.c_double),
+    ]
+
+
+FIRE_STATE_DOUBLES, FIRE_MAX_BLOCKS = 8, 256  # TMDHIP_FIRE_STATE_DOUBLES, TMDHIP_FIRE_MAX_BLOCKS
+FIRE_DT, FIRE_ALPHA, FIRE_NPOS, FIRE_DONE, FIRE_ITERATIONS, FIRE_FMAX, FIRE_NUPHILL = range(7)  # fields of a state slot
+
 # name -> (restype, argtypes): every symbol include/tmdhip.h declares
 SIGNATURES = {
     "tmdhip_abi_version": (C.c_int, []),
@@ -320,6 +338,12 @@ SIGNATURES = {
     "tmdhip_vsite_spread": (
         C.c_int,
         [C.c_int, C.c_int64, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
+    ),
+    "tmdhip_fire_init": (C.c_int, [C.c_int64, C.c_void_p, C.POINTER(FireParams), C.c_void_p]),
+    "tmdhip_fire_step": (
+        C.c_int,
+        [C.c_int, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+         C.POINTER(FireParams), C.c_int64, C.c_void_p],
     ),
     "tmdhip_normal_fill": (C.c_int, [C.c_int, C.c_int64, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p]),
     "tmdhip_dd_step": (

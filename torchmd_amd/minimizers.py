@@ -3,14 +3,22 @@ same function names, arguments and effect on `system.pos`).  They are callers of
 of it: every energy/force evaluation is one `forces.compute(pos, box, forces)` on the device; the
 optimisation logic runs on the host (scipy L-BFGS-B), in torch (LBFGS on the differentiable potential)
 or as a few tensor operations per line-search point (conjugate gradient).
+
+`minimize_fire` has no counterpart in the reference and is built differently: FIRE needs forces only, so an
+iteration is the integrator's force-only evaluation plus two HIP launches (`tmdhip_fire_step`), the state of every replica
+stays on the device, and the host reads it back once per `check_every` iterations.
 """
 
 from __future__ import annotations
 
+import ctypes as C
 import logging
+from dataclasses import dataclass
 
 import numpy as np
 import torch
+
+from . import _lib as L
 
 logger = logging.getLogger(__name__)
 
@@ -134,3 +142,176 @@ def minimize_cg(system, forces, steps=1000, start_step: int = 0, threshold=None)
         system.pos[0] = pos
     forces.compute(system.pos, system.box, system.forces)
     return last
+
+
+@dataclass
+class FireResult:
+    """What `minimize_fire` did, one entry per replica: `converged` (bool; the largest atom force fell below `fmax`),
+    `iterations` (moves made), `fmax` (largest atom force norm at the returned positions, kcal/mol/A) and `nuphill` (how often
+    the power F.v was not positive and the velocities were dropped)."""
+
+    converged: np.ndarray
+    iterations: np.ndarray
+    fmax: np.ndarray
+    nuphill: np.ndarray
+
+
+_SEGMENT_FAILED = ("minimize_fire(): a stretch of iterations was rewound to its check point and repeated once with fresh "
+                   "neighbour lists and failed again; system.pos holds the check point.  The library says: ")
+
+
+def _fire_segments(ops, steps, check_every):
+    """The host side of `minimize_fire`: enqueue `check_every` iterations at a time, then look once.  `ops` supplies
+    `save()` (snapshot of positions, velocities and state: the check point), `advance(first, n)` (enqueue iterations first ..
+    first + n - 1), `verify()` (False: a neighbour list overflowed or outlived its skin during the stretch), `restore()`,
+    `invalidate()`, `all_done()` (one read-back of the state) and `error()` (the library's message).  A stretch that fails is
+    rewound to its check point and repeated once with fresh lists; a second failure raises.  Returns the number of iterations
+    enqueued (a replica that converged earlier was frozen on the device from then on)."""
+    first = 0
+    ops.save()
+    while first < steps:
+        n = min(check_every, steps - first)
+        ops.advance(first, n)
+        if not ops.verify():
+            ops.restore()
+            ops.invalidate()
+            ops.advance(first, n)
+            if not ops.verify():
+                why = ops.error()
+                ops.restore()
+                raise RuntimeError(_SEGMENT_FAILED + why)
+        first += n
+        if ops.all_done():
+            break
+        if first < steps:
+            ops.save()
+    return first
+
+
+class _FireOps:
+    """`_fire_segments` on the device: this package's `Forces` and `tmdhip_fire_step`."""
+
+    def __init__(self, system, forces, masses, prm):
+        pos = system.pos
+        self.system, self.forces, self.masses, self.prm = system, forces, masses, prm
+        self.lib = L.load()
+        self.code = L.dtype_code(pos.dtype)
+        R = pos.shape[0]
+        self.vel = torch.zeros_like(pos)  # FIRE's own velocities: system.vel is not touched
+        self.state = torch.zeros((R, 2, L.FIRE_STATE_DOUBLES), dtype=torch.float64, device=pos.device)
+        self.partials = torch.zeros((R, L.FIRE_MAX_BLOCKS, 4), dtype=torch.float64, device=pos.device)
+        self.saved = (torch.empty_like(pos), torch.empty_like(pos), torch.empty_like(self.state))
+        self.eng = forces._engine(pos.detach())
+        self.done = 0  # iterations enqueued: the live state slot is `done & 1`
+        L.check(self.lib.tmdhip_fire_init(R, self.state.data_ptr(), C.byref(prm), self._stream()), "tmdhip_fire_init")
+
+    def _stream(self):
+        return C.c_void_p(torch.cuda.current_stream(self.system.pos.device).cuda_stream)
+
+    def save(self):
+        for dst, src in zip(self.saved, (self.system.pos, self.vel, self.state)):
+            dst.copy_(src.detach())
+
+    def restore(self):
+        for dst, src in zip((self.system.pos, self.vel, self.state), self.saved):
+            dst.detach().copy_(src)
+
+    def invalidate(self):
+        self.forces.invalidate_lists(self.system.pos)
+
+    def advance(self, first, n):
+        s, lib = self.system, self.lib
+        pos = s.pos.detach()
+        R, N = pos.shape[0], pos.shape[1]
+        args = (self.code, R, N, pos.data_ptr(), self.vel.data_ptr(), s.forces.data_ptr(), self.masses.data_ptr(),
+                self.state.data_ptr(), self.partials.data_ptr(), C.byref(self.prm))
+        for it in range(first, first + n):
+            self.forces._compute_async(pos, s.box, s.forces, want_energy=False)
+            L.check(lib.tmdhip_fire_step(*args, it, self._stream()), "tmdhip_fire_step")
+        self.done = first + n
+
+    def verify(self):
+        return self.forces._verify(self.eng, self.system.pos)
+
+    def error(self):
+        return L.last_error()
+
+    def live_state(self):
+        return self.state[:, self.done & 1].cpu().numpy()
+
+    def all_done(self):
+        return bool((self.live_state()[:, L.FIRE_DONE] != 0).all())
+
+
+def minimize_fire(system, forces, fmax=0.5, steps=1000, timestep=1.0, dt_max=None, max_step=0.1, n_min=5, f_inc=1.1,
+                  f_dec=0.5, alpha_start=0.1, f_alpha=0.99, check_every=50):
+    """FIRE (Bitzek et al., PRL 97, 170201, 2006) on every replica of `system.pos` at once, independently and in place, until
+    the largest atom force of a replica is below `fmax` (kcal/mol/A) or `steps` iterations were made.  `timestep` (fs, converted
+    as `Integrator` does) is the first time step of the damped dynamics, `dt_max` its ceiling (default 10 x `timestep`),
+    `max_step` (A) the largest move of one atom in one iteration; the other arguments are the constants of the paper.
+
+    One iteration is `forces._compute_async(..., want_energy=False)` (forces only: virtual-site placement and spreading, PME,
+    the bonded terms and `external` included; no host synchronisation) and one `tmdhip_fire_step` (two HIP launches, DESIGN
+    §13).  The state of every replica (time step, mixing factor, counters, the `done` flag) lives on the device; a replica that
+    has converged is frozen there, bit for bit, however many iterations are still enqueued.  The host looks once per
+    `check_every` iterations: it reads the state, checks the neighbour lists (`forces._verify`) and stops when every replica is
+    done.  If a list overflowed or outlived its skin, positions, velocities and state go back to the previous check point, the
+    lists are dropped and the stretch is repeated once; a second failure raises `RuntimeError`.
+
+    Masses as in `Integrator`: `system.masses`, else `forces.par.masses`.  Rows with mass 0 (virtual sites) are no degrees of
+    freedom: they enter no sum and are moved only by the site placement of the force evaluation.  The velocities of the damped
+    dynamics are private, `system.vel` is not touched; `system.forces` holds the forces of the returned positions.
+
+    Rigid units are not handled: this minimises the flexible model, whose bond and angle minima are the rigid geometry the
+    constraint finder reads, and leaves the projection onto the constraints to `Integrator._project_start`.
+
+    Returns a `FireResult`, or None for `steps == 0`.  `ValueError` for a force object that is not this package's `Forces`
+    (the loop needs `_compute_async` and `_verify`), a non-contiguous `pos`, a `pos` whose dtype differs from that of `system.forces`,
+    and `fmax <= 0`."""
+    from .forces import Forces
+    from .integrator import TIMEFACTOR
+
+    if steps == 0:
+        return None
+    if not isinstance(forces, Forces):
+        raise ValueError("minimize_fire needs this package's Forces (its force-only evaluation `_compute_async` and its list "
+                         "check `_verify`); a duck-typed force object is not supported")
+    if not fmax > 0:
+        raise ValueError(f"fmax must be positive, got {fmax}")
+    if steps < 0 or check_every < 1:
+        raise ValueError("steps must not be negative and check_every must be at least 1")
+    pos = system.pos
+    L.require_device_tensor(pos, "system.pos")
+    if not pos.is_contiguous():
+        raise ValueError("system.pos must be contiguous (it is updated in place by the HIP kernels)")
+    if pos.dtype != system.forces.dtype or not system.forces.is_contiguous() or system.forces.shape != pos.shape:
+        raise ValueError("system.forces must be contiguous and have the dtype and shape of system.pos")
+    if torch.any(system.masses != 0):
+        masses = system.masses
+    else:
+        masses = torch.as_tensor(forces.par.masses).detach().clone()
+    masses = masses.to(device=pos.device, dtype=pos.dtype).reshape(-1).contiguous()
+    if masses.numel() != pos.shape[1]:
+        raise ValueError("one mass per atom is needed")
+    prm = L.FireParams()
+    prm.struct_size = C.sizeof(L.FireParams)
+    prm.n_min = int(n_min)
+    prm.f_tol = float(fmax)
+    prm.dt_start = float(timestep) / TIMEFACTOR
+    prm.dt_max = (10.0 * float(timestep) if dt_max is None else float(dt_max)) / TIMEFACTOR
+    prm.max_step = float(max_step)
+    prm.f_inc, prm.f_dec, prm.alpha_start, prm.f_alpha = float(f_inc), float(f_dec), float(alpha_start), float(f_alpha)
+    with torch.cuda.device(pos.device):
+        ops = _FireOps(system, forces, masses, prm)
+        _fire_segments(ops, int(steps), int(check_every))
+        # the forces of the returned positions, and their largest norm over the real atoms (once per call, not per iteration)
+        forces._compute_async(pos.detach(), system.box, system.forces, want_energy=False)
+        norm = torch.linalg.vector_norm(system.forces.detach().to(torch.float64), dim=2)
+        norm = torch.where(masses.reshape(1, -1) > 0, norm, torch.zeros_like(norm)).max(dim=1).values.cpu().numpy()
+        state = ops.live_state()
+        if not forces._verify(ops.eng, pos):
+            raise RuntimeError("minimize_fire(): a neighbour list failed in the evaluation of the returned positions: " + L.last_error())
+    res = FireResult(converged=state[:, L.FIRE_DONE] != 0, iterations=state[:, L.FIRE_ITERATIONS].astype(np.int64), fmax=norm,
+                     nuphill=state[:, L.FIRE_NUPHILL].astype(np.int64))
+    logger.info("minimize_fire: iterations %s, fmax %s, converged %s", res.iterations, res.fmax, res.converged)
+    return res

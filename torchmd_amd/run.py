@@ -27,7 +27,7 @@ from . import io as tio
 from .forcefields import ForceField
 from .forces import Forces
 from .integrator import Integrator, maxwell_boltzmann
-from .minimizers import minimize_bfgs
+from .minimizers import minimize_bfgs, minimize_fire
 from .utils import LogWriter
 from .parameters import Parameters
 from .systems import System
@@ -45,6 +45,7 @@ DEFAULTS = dict(
     constraints=None,  # None, "water" (rigid waters) or "hbonds" (rigid waters and X-H bonds): DESIGN §10
     barostat_pressure=None,  # bar; None: constant volume.  Monte Carlo barostat at langevin_temperature: DESIGN §11
     barostat_frequency=25,  # steps between two volume moves
+    minimizer="bfgs",  # what `minimize: N` runs: "bfgs" (scipy L-BFGS-B, one replica) or "fire" (on the device, every replica): DESIGN §13
     virtual_sites=None,  # None or "tip4p": four-site waters O,H1,H2,M; geometry from the force field's `virtual_sites` section: DESIGN §12
 )
 
@@ -82,6 +83,9 @@ def get_args(arguments=None):
         args.virtual_sites = None
     if args.virtual_sites not in (None, "tip4p"):
         raise ValueError(f"virtual_sites must be None or 'tip4p', got {args.virtual_sites!r}")
+    args.minimizer = str(args.minimizer).lower()
+    if args.minimizer not in ("bfgs", "fire"):
+        raise ValueError(f"minimizer must be 'bfgs' or 'fire', got {args.minimizer!r}")
     if isinstance(args.barostat_pressure, str) and args.barostat_pressure.lower() in ("none", "null", ""):
         args.barostat_pressure = None
     if args.barostat_pressure is not None:
@@ -265,7 +269,10 @@ def dynamics(args, mol, system, forces):
     logs = [LogWriter(args.log_dir, columns, name=f"monitor_{k}.csv") for k in range(args.replicas)]
     boxes = []  # [frames][R,3] box edges, constant-pressure runs only
     if args.minimize is not None:
-        minimize_bfgs(system, forces, steps=int(args.minimize))
+        if args.minimizer == "fire":
+            minimize_fire(system, forces, steps=int(args.minimize))
+        else:
+            minimize_bfgs(system, forces, steps=int(args.minimize))
     forces.compute(system.pos, system.box, system.forces)
     name, ext = os.path.splitext(args.output)
     t0 = time.time()
