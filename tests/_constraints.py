@@ -18,24 +18,28 @@ def units(cs):
 
 
 def shake(x, ref, m, us, tol=1e-14, max_iter=100000):
-    """x [N, 3] in place: every constraint |s| = d to relative tol, displacements along the bonds of `ref`."""
+    """x [N, 3] in place: every constraint |s| = d to relative tol, displacements along the bonds of `ref`.  A unit is iterated
+    in coordinates relative to its first atom's reference position (the constraints do not see a translation): at a
+    coordinate of 60 A one ulp is 7e-15 A, and |s|^2 taken from absolute positions cannot be told from d^2 to 1e-14."""
     for at, pairs in us:
+        o = ref[at[0]].copy()
+        xl, rl = x[at] - o, ref[at] - o
         for _ in range(max_iter):
             done = True
             for a, b, d in pairs:
-                i, j = at[a], at[b]
-                s = x[i] - x[j]
+                s = xl[a] - xl[b]
                 diff = d * d - s @ s
                 if abs(diff) > 2 * tol * d * d:
                     done = False
-                r = ref[i] - ref[j]
-                g = diff / (2.0 * (r @ s) * (1 / m[i] + 1 / m[j]))
-                x[i] += g * r / m[i]
-                x[j] -= g * r / m[j]
+                r = rl[a] - rl[b]
+                g = diff / (2.0 * (r @ s) * (1 / m[at[a]] + 1 / m[at[b]]))
+                xl[a] += g * r / m[at[a]]
+                xl[b] -= g * r / m[at[b]]
             if done:
                 break
         else:
             raise AssertionError("host SHAKE did not converge")
+        x[at] = xl + o
     return x
 
 

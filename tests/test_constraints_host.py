@@ -128,3 +128,49 @@ def test_host_step_holds_its_constraints(mode):
     assert np.abs(xa - xb).max() < 1e-10
     va = cs.project_velocities(xa, rng.normal(size=x0.shape))
     assert H.residuals(xa, va, pairs, d)[1] < 1e-12
+
+
+@pytest.mark.parametrize("size", ["small", "large"])
+def test_synthetic_system_holds_every_unit_kind(size):
+    """tests/_constraint_systems.py: free ions, two kinds of rigid three-atom units, clusters of 1 .. 4 hydrogens, numbered at
+    random — what `find_constraints` makes of it."""
+    import _constraint_systems as S
+    from torchmd_amd.constraints import find_constraints
+
+    s = S.build(size)
+    par = s.par()
+    m = par.masses.reshape(-1).numpy()
+    n = s.natoms
+    assert n == (S.CELLLIST_MIN_ATOMS if size == "large" else 260)
+    cs = find_constraints(par.masses, par.bond_params, par.angle_params, "hbonds")
+    c = s.meta["counts"]
+    assert cs.nwaters == c["tip3p"] + c["h2s"] == s.meta["nwaters"]
+    heavy = np.round(m[cs.waters[:, 0]], 2)
+    assert (heavy == 16.0).sum() == c["tip3p"] and (heavy == 32.06).sum() == c["h2s"]
+    for w, (doh, dhh) in zip(cs.waters, cs.water_dist):
+        want = (0.9572, 2 * 0.9572 * np.sin(np.deg2rad(104.52) / 2)) if m[w[0]] < 20 else (1.34, 2 * 1.34 * np.sin(np.deg2rad(92.0) / 2))
+        assert abs(doh - want[0]) < 1e-12 and abs(dhh - want[1]) < 1e-12
+    cl = cs.clusters()
+    sizes = sorted(len(a) - 1 for a in cl)
+    assert sizes == s.meta["cluster_sizes"] and set(sizes) == {1, 2, 3, 4}
+    for k in (1, 2, 3, 4):  # at least two of every size, around heavy atoms of different masses
+        mk = [m[a[0]] for a in cl if len(a) - 1 == k]
+        assert len(mk) >= 2 and len(set(np.round(mk, 2))) >= 2, (k, mk)
+    assert cs.nconstraints == s.meta["nconstraints"] and cs.ndof() == 3 * n - s.meta["nconstraints"]
+    # every unit's first entry is the heavy atom, the others are its hydrogens
+    for u in list(cs.waters) + cl:
+        assert m[u[0]] > 1.5 and np.all(m[u[1:]] < 1.5), u
+    # free atoms: the ions, and the heavy atoms without a hydrogen would be too (there are none)
+    in_unit = np.zeros(n, dtype=bool)
+    in_unit[np.concatenate([cs.waters.reshape(-1), cs.atoms])] = True
+    assert (~in_unit).sum() == s.meta["nions"] and np.all(s.meta["kind"][~in_unit] == "ion")
+    # scrambled numbering: units interleave (hydrogens do not follow their heavy atom) and span 64-atom blocks
+    units = [np.asarray(u) for u in list(cs.waters) + cl]
+    assert sum(1 for u in units if np.any(np.diff(u) != 1)) > 0.9 * len(units)
+    assert sum(1 for u in units if len(set(u // 64)) > 1) > 0.5 * len(units)
+    # heavy atoms bonded to each other
+    b = par.bond_params["idx"].numpy()
+    assert (np.all(m[b] > 1.5, axis=1)).sum() >= c["methanol"] + c["methylamine"] + c["methanethiol"] + 2 * c["ethanol"]
+    # in "water" mode only the three-atom units remain
+    cw = find_constraints(par.masses, par.bond_params, par.angle_params, "water")
+    assert cw.nwaters == cs.nwaters and cw.nclusters == 0
