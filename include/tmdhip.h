@@ -169,7 +169,7 @@ typedef struct tmdhip_pme_desc {
 int tmdhip_set_pme(tmdhip_ctx *ctx, const tmdhip_pme_desc *desc);
 
 /* Holonomic constraints of the MD loop (ABI 10): rigid waters and X-H bond clusters.  tmdhip_md_run then steps every unit —
- * a rigid water, a cluster or an unconstrained atom — in one thread (md_loop.hip: md_step_cons_kernel), in double: after the
+ * a rigid water, a cluster or an unconstrained atom — in one thread (md_cons.hip: md_step_cons_kernel), in double: after the
  * second half kick the velocity constraint of the unit (its k x k linear system solved exactly), after the drift the position
  * constraint relative to the positions before it (analytic SETTLE for waters, Miyamoto & Kollman 1992; iterated SHAKE for
  * clusters), then v += dx / dt.  The fused pair + step launches, the inline bonded integrator kernel and the replica-batched

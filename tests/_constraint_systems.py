@@ -1,4 +1,4 @@
-"""A seeded synthetic topology that holds every unit kind of the constrained MD step (csrc/md_loop.hip, md_step_cons_kernel)
+"""A seeded synthetic topology that holds every unit kind of the constrained MD step (csrc/md_cons.hip, md_step_cons_kernel)
 in one context: free ions, TIP3P waters, H2S-like "waters" (32.06 amu, 1.34 A, 92 degrees: `find_constraints` takes any heavy
 atom with exactly two hydrogens for a rigid three-atom unit), and X-H clusters of 1, 2, 3 and 4 hydrogens around heavy atoms
 of different masses (C, N, O, S), some of the heavy atoms bonded to each other.

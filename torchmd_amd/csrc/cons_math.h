@@ -1,4 +1,4 @@
-// Constraint arithmetic of the constrained MD step (md_loop.hip: md_step_cons_kernel), in double in both precisions:
+// Constraint arithmetic of the constrained MD step (md_cons.hip: md_step_cons_kernel), in double in both precisions:
 // analytic SETTLE for rigid waters (Miyamoto & Kollman 1992, in the form of GROMACS' settle), iterated SHAKE for X-H
 // clusters, and the exact velocity constraint of a unit (its k x k linear system, k <= 4).  Host-callable, so that the
 // formulas can be checked on a CPU.  A unit's atoms are local indices 0 .. NA-1; the constraints of a water are (0,1), (0,2),

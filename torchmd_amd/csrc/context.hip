@@ -819,7 +819,7 @@ int tmdhip_compute(tmdhip_ctx *ctx, const void *pos_dev, const double *box_host,
   TMD_TRY(tmdhip_compute_nonbonded(ctx, TMDHIP_ALL_REPLICAS, pos_dev, box_host, forces_dev, e,
                                    flags | kSpecChain | (forces_dev ? TMDHIP_OVERWRITE_FORCES : 0), stream));
   TMD_TRY(tmdhip_compute_bonded(ctx, TMDHIP_ALL_REPLICAS, pos_dev, box_host, forces_dev, e, flags, stream));
-  if (nrep <= 16) {  // results through host-mapped memory + a sequence word (md_loop.hip: observe_publish_kernel)
+  if (nrep <= 16) {  // results through host-mapped memory + a sequence word (md_observe.hip: observe_publish_kernel)
     TMD_TRY(publish_observables(ctx, e, nullptr, lists, he, hk, hf, hseq, st));  // the one host synchronisation of an energy evaluation
   } else {
     TMD_HIP(hipMemcpyAsync(he, e, ebytes, hipMemcpyDeviceToHost, st));

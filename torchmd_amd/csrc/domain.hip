@@ -449,8 +449,6 @@ int dd_csr_ready(tmdhip_comm *c, const tmdhip_dd_desc *d, hipStream_t st) {
   return 0;
 }
 
-constexpr double kDdChainNear = 0.75;  // as tmdhip_md_run's kChainSkipNear (md_loop.hip)
-
 // front half of a fused brick step: the pacing decision (leave the rebuild chain out?) and — unless the previous pair
 // launch has made this iteration's update itself (step blocks) — dd_own_kernel
 template <typename R>
@@ -476,29 +474,8 @@ int dd_fused_front(tmdhip_ctx *ctx, Replica &rp, tmdhip_comm *c, const tmdhip_dd
   a.disp2 = d->disp2_dev;
   a.chk = make_check<R>(ctx, rp);
   skip_chain = false;
-  if (chain_skip_on) {  // (tmdhip_md_run's scheme, md_loop.hip: the host stays one step behind the device)
-    if (!rp.hostpub) {
-      TMD_HIP(hipHostMalloc((void **)&rp.hostpub, 8 * sizeof(unsigned), hipHostMallocMapped));
-      for (int w = 0; w < 8; ++w) rp.hostpub[w] = 0u;
-      rp.seq = 0;
-      rp.seq_valid = false;
-    }
-    volatile unsigned *hp = rp.hostpub;
-    if (rp.seq_valid && !pace_timed_out && !wait_published(hp, rp.seq)) pace_timed_out = true;
-    if (rp.seq_valid && !pace_timed_out) {
-      const bool near = hp[1 + (rp.seq & 1u)] == rp.seq, rebuilt = hp[3 + (rp.seq & 1u)] == rp.seq;
-      skip_chain = !near || (rebuilt && !rp.prev_skipped);
-    }
-    rp.prev_skipped = skip_chain;
-    rp.seq += 1;
-    if (rp.seq == 0) rp.seq = 1;
-    a.chk.near_host = rp.hostpub + 1 + (rp.seq & 1u);
-    a.chk.seq = rp.seq;
-    a.chk.near_frac2 = (R)(kDdChainNear * kDdChainNear);
-    a.chk.skipped = skip_chain ? 1 : 0;
-    rp.seq_valid = true;
-    rp.pub_ptr = rp.hostpub;
-    rp.pub_val = rp.seq;
+  if (chain_skip_on) {  // (tmdhip_md_run's scheme, md_loop.hip: the host stays one step behind the device; a brick's steps follow each other)
+    TMD_TRY(pace_behind_device<R>(rp, a.chk, true, kChainSkipNear, pace_timed_out, skip_chain));
   } else {
     rp.seq_valid = false;
     rp.pub_ptr = nullptr;
@@ -539,7 +516,7 @@ int dd_fused_back(tmdhip_ctx *ctx, Replica &rp, tmdhip_comm *c, const tmdhip_dd_
   ListCheck<R> chk = make_check<R>(ctx, rp);
   chk.near_host = c->chk_near;
   chk.seq = c->chk_seq;
-  chk.near_frac2 = (R)(kDdChainNear * kDdChainNear);
+  chk.near_frac2 = (R)(kChainSkipNear * kChainSkipNear);
   chk.skipped = c->chk_skipped;
   if (d->nhalo > 0) {
     hipLaunchKernelGGL((dd_halo_kernel<R>), dim3((unsigned)((d->nhalo + 255) / 256)), dim3(256), 0, st, (int)d->nown, n,
@@ -553,24 +530,8 @@ int dd_fused_back(tmdhip_ctx *ctx, Replica &rp, tmdhip_comm *c, const tmdhip_dd_
     if (want_fuse_next && fused_step_possible<R>(ctx, rp, pc) && ctx->fused_step_timeouts == 0) {
       TMD_TRY(dd_csr_ready(c, d, st));
       FusedStaticT<R> now;
-      std::memset(&now, 0, sizeof(now));
-      now.s.n = n;
-      now.s.vel = (R *)d->vel_dev;
-      now.s.mass = (const R *)d->mass_dev;
-      now.s.vcoeff = (const R *)d->vcoeff_dev;
-      now.s.dt = (R)d->dt;
-      now.s.half_dt = (R)(0.5 * d->dt);
-      now.s.gamma = d->vcoeff_dev ? (R)d->gamma : R(0);
-      now.s.seed = d->seed;
-      now.s.row0 = 0;
-      now.s.qs = ctx->qs.as<R>();
-      now.s.inv = rp.inv.as<int>();
-      now.s.chk.ref = chk.ref;
-      now.s.chk.hard2 = chk.hard2;
-      now.s.chk.hs2 = chk.hs2;
-      now.s.chk.flags = chk.flags;
-      now.s.chk.near_frac2 = (R)(kDdChainNear * kDdChainNear);
-      now.s.chk.ext = chk.ext;
+      fused_static_common<R>(now, n, (R *)d->vel_dev, (const R *)d->mass_dev, (const R *)d->vcoeff_dev, d->dt,
+                             d->vcoeff_dev ? (R)d->gamma : R(0), d->seed, 0, ctx->qs.as<R>(), rp.inv.as<int>(), chk, kChainSkipNear);
       now.nactive = (int)d->nown;
       now.dd_ref = (const R *)d->ref_dev;
       now.dd_disp2 = d->disp2_dev;
@@ -587,10 +548,8 @@ int dd_fused_back(tmdhip_ctx *ctx, Replica &rp, tmdhip_comm *c, const tmdhip_dd_
       fl.step.noise_step = next_kick_step;
       fl.step.bonded = 0;
       if (rp.pub_ptr) {  // pacing on: the next iteration's sequence number
-        unsigned nseq = rp.seq + 1;
-        if (nseq == 0) nseq = 1;
-        fl.step.seq = nseq;
-        fl.step.near_host = rp.hostpub + 1 + (nseq & 1u);
+        fl.step.seq = next_seq(rp.seq);
+        fl.step.near_host = rp.hostpub + 1 + (fl.step.seq & 1u);
       }
       fused_next = true;
     }

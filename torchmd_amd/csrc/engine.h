@@ -8,7 +8,9 @@
 //   pair_generic.hip   K4 tiled all-pairs kernel, generic list pair kernel, dispatch between the pair kernels
 //   pair_fast_f32.hip  K3f lean fp32 list pair kernel (+ the MD step inside the pair launch)
 //   pair_lean_f64.hip  K3d lean fp64 list pair kernel
-//   md_loop.hip        fused MD-step kernels, tmdhip_md_run / _observe / _restore
+//   md_loop.hip        fused MD-step kernels, tmdhip_md_run / _restore
+//   md_cons.hip        the constrained MD step (tmdhip_set_constraints)
+//   md_observe.hip     reports to the host, tmdhip_md_observe
 //
 // Data layout in HBM (per replica):
 //   sorted_xyzq  real4[N]   positions in cell-sorted order + scaled charge q*sqrt(k_e)
@@ -43,6 +45,7 @@
 #include "common.h"
 #include "pair_math.h"
 #include "bonded_math.h"
+#include "pacing.h"
 #include "rng.h"
 
 namespace tmd {
@@ -633,7 +636,7 @@ struct tmdhip_ctx {
   // smooth PME (tmdhip_set_pme), pme.hip; null: off (no PME buffer, no PME launch)
   void *pme = nullptr;
   double pme_beta = 0;
-  // holonomic constraints of the MD loop (tmdhip_set_constraints), md_loop.hip; null: off
+  // holonomic constraints of the MD loop (tmdhip_set_constraints), md_cons.hip; null: off
   void *cons = nullptr;
   // virtual sites the context's own launches serve (tmdhip_set_vsites), vsite.hip; null: none
   void *vsites = nullptr;
@@ -802,11 +805,16 @@ int pme_apply(tmdhip_ctx *ctx, int r, const R *pos, const double *box, R *forces
 // TMDHIP_WANT_ENERGY
 int pme_hook(tmdhip_ctx *ctx, int r, const void *pos, const double *box, void *forces, double *energies, int flags, hipStream_t st);
 void pme_release(tmdhip_ctx *ctx);
-// md_loop.hip: the constraint state of the MD loop (tmdhip_set_constraints).  cons_verdict: < 0 (and the message) when a
+// md_cons.hip: the constraint state of the MD loop (tmdhip_set_constraints).  cons_verdict: < 0 (and the message) when a
 // constrained step since the last look failed to converge; reads a host-mapped word, so the caller must have waited for the
 // stream (or for a report enqueued behind the steps).
 void cons_release(tmdhip_ctx *ctx);
 int cons_verdict(tmdhip_ctx *ctx);
+bool cons_has_sites(const tmdhip_ctx *ctx);  // the constrained waters carry the context's virtual sites
+// the constrained integrator kernel of one phase of md_run (the five of for_md_phase, md_step.h)
+template <typename R>
+void launch_cons_step(const tmdhip_ctx *ctx, const MdStepArgs<R> &a, const PairConsts<R> &c, bool second, bool langevin, bool first,
+                      bool check, int nrep, hipStream_t st);
 // vsite.hip
 void vsite_release(tmdhip_ctx *ctx);
 int64_t pme_evaluations(const tmdhip_ctx *ctx, int r);
@@ -814,21 +822,39 @@ int64_t pme_bytes(const tmdhip_ctx *ctx);
 // md_loop.hip
 template <typename R>
 int md_run(tmdhip_ctx *ctx, const tmdhip_md_desc *d, hipStream_t st);
+// Chain skipping, one step of the pacing host (tmdhip_md_run, tmdhip_dd_run): waits for the previous step's report (Replica::hostpub,
+// allocated here), decides with pace_decide (pacing.h) whether this step goes without its rebuild chain, and fills chk.near_host /
+// seq / near_frac2 / skipped and rp.seq / seq_valid / prev_skipped / pub_ptr / pub_val.  `follows`: nothing has moved since the
+// previous report; `timed_out`: set when the device did not report in time — no more waiting in this call.
+template <typename R>
+int pace_behind_device(Replica &rp, ListCheck<R> &chk, bool follows, double near_frac, bool &timed_out, bool &skip_chain);
+// the part of a replica's FusedStatic that tmdhip_md_run and a brick fill alike (`now` is zeroed first: it is compared bytewise)
+template <typename R>
+void fused_static_common(FusedStaticT<R> &now, int n, R *vel, const R *mass, const R *vcoeff, double dt, R gamma, uint64_t seed,
+                         uint64_t row0, const R *qs, const int *inv, const ListCheck<R> &chk, double near_frac);
 // device copy of a replica's FusedStatic, re-uploaded (one-thread kernel, stream-ordered) only when a field has changed
 template <typename R>
 int upload_fused_static(Replica &rp, const FusedStaticT<R> &now, hipStream_t st);
 // can the pair launch of this replica integrate the next step itself?  (lean kernels, 4 .. 64 lanes per atom)
 template <typename R>
 bool fused_step_possible(const tmdhip_ctx *ctx, const Replica &rp, const PairConsts<R> &c);
-// tmdhip_compute's two-launch evaluation (md_loop.hip) and the wait for a report's sequence word
+// tmdhip_compute's two-launch evaluation
 int compute_fused_eval(tmdhip_ctx *ctx, const void *pos_dev, const double *box, void *forces_dev, double *e_dev, double *scratch_ke,
                        double *host_e, double *host_ke, int *host_flags, volatile unsigned *host_seq, hipStream_t st);
-int wait_observed(volatile unsigned *hseq, unsigned seq, hipStream_t st);
 // chain skipping: spin until the device has published sequence number `target` (Replica::hostpub[0]); false after 0.2 s
 bool wait_published(volatile unsigned *hp, unsigned target);
+// md_observe.hip: the wait for a report's sequence word
+int wait_observed(volatile unsigned *hseq, unsigned seq, hipStream_t st);
 // energies, kinetic energies and list flags of every replica through host-mapped memory + a sequence word the host
 // spins on (<= 16 replicas); returns when the device has written them
 int publish_observables(tmdhip_ctx *ctx, const double *energies_dev, const double *ke_dev, bool lists, double *host_e,
                         double *host_ke, int *host_flags, volatile unsigned *host_seq, hipStream_t st);
+// fold of the energy rows FINAL / evaluation-only step blocks have left + the report, in one launch (one replica); the caller
+// waits for ctx->obs_seq.  publish_final_step: for the last step of a tmdhip_md_run call, into tmdhip_md_observe's zone
+int launch_final_fold_publish(tmdhip_ctx *ctx, const Replica &rp, double *out, double *ke, double *host_e, double *host_ke,
+                              int *host_flags, volatile unsigned *host_seq, int accumulate, hipStream_t st);
+int publish_final_step(tmdhip_ctx *ctx, const Replica &rp, double *en, hipStream_t st);
+// the report of a tmdhip_md_run call that returns energies, enqueued behind its last kernel
+int enqueue_run_report(tmdhip_ctx *ctx, const tmdhip_md_desc *desc, hipStream_t st);
 
 }  // namespace tmd

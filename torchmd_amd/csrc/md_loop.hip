@@ -1,12 +1,10 @@
-// The MD loop of the nonbonded engine for gfx950 (MI355X): fused MD-step kernels and tmdhip_md_run / _observe /
-// _restore, which enqueue whole batches of steps from C.
+// The MD loop of the nonbonded engine for gfx950 (MI355X): fused MD-step kernels and tmdhip_md_run / _restore, which
+// enqueue whole batches of steps from C.  (The constrained step: md_cons.hip; the reports to the host: md_observe.hip.)
 //
 // Reference semantics: torchmd/integrator.py:61-74 (_first_VV, _second_VV, langevin) in the order of
 // Integrator.step (integrator.py:112-125): first_VV(old F) -> compute -> langevin -> second_VV(new F).
-#include "cons_math.h"
 #include "engine.h"
 #include "md_step.h"
-#include "vsite_math.h"
 
 namespace tmd {
 
@@ -93,438 +91,6 @@ __global__ __launch_bounds__(256) void md_step_bonded_kernel(MdStepArgs<R> s, Pa
   md_step_atom<R, true, LANGEVIN, true, CHECK>(s, c, mine, off, row0, x, fb, true);
 }
 
-// ---- constrained MD step (tmdhip_set_constraints) ----------------------------------------------------------
-// One thread owns one unit — a rigid water, an X-H cluster or an unconstrained atom — and does for every atom of it what
-// md_step_atom does (f_zero, the thermostat with the noise of the atom's own row, the kicks, the drift, the displacement test,
-// the cell-sorted record), with the constraints between the phases: after the second half kick the velocity constraint of the
-// unit, after the drift the position constraint relative to the undrifted positions (SETTLE / SHAKE), then v += dx / dt.
-// The arithmetic is double in both precisions (fp32: only the loads and stores are float).
-constexpr int kConsAtom = 0, kConsWater = 1, kConsCluster = 2;
-
-struct ConsArgs {
-  const int2 *units;  // {kind, index} ordered by the unit's first atom: kConsAtom (index = atom), kConsWater, kConsCluster
-  int nunits;
-  const int *water;     // [W][3] O, H1, H2
-  const double *wdist;  // [W][2] d_OH, d_HH
-  const int *coff, *catom;
-  const double *cdist;
-  double tol;
-  int max_iter;
-  int *fail;  // host-mapped word: a unit did not converge (cons_verdict)
-};
-
-// Four-site rigid waters (tmdhip_set_vsites): the massless site of water w, or -1, and its weights in the order
-// O, H1, H2 — the order of the site's parent table.  The water's thread serves the site as well (md_step_cons_vs_kernel).
-struct ConsSiteArgs {
-  const int *wsite;       // [W]
-  const double *wweight;  // [W][3]
-};
-
-struct ConsState {
-  DevBuf units, water, wdist, coff, catom, cdist;
-  DevBuf wsite, wweight;  // (only with sites)
-  bool has_sites = false;
-  int nunits = 0;
-  double tol = 1e-10;
-  int max_iter = 200;
-  int *fail_host = nullptr;
-};
-
-// VS (waters only): the unit also carries the massless site `site` with weights sw (parents O, H1, H2 in this order) — its force
-// is folded into the parents' before anything divides by a mass, the site is placed from the parents' positions as stored, and
-// it gets what every atom gets but an update: f_zero, the entry snapshot, the cell-sorted record, the displacement test;
-// velocity 0.  Nothing here reads the site's mass or draws noise for it.
-template <typename R, bool SECOND, bool LANGEVIN, bool FIRST, bool CHECK, int NA, int NC, bool WATER, bool VS = false>
-__device__ __forceinline__ void cons_unit(const MdStepArgs<R> &s, const PairConsts<R> &c, const ConsArgs &k, const int (&at)[NA],
-                                          const double (&d)[NA], size_t off, uint64_t row0, int site = -1, const double *sw = nullptr) {
-#pragma clang fp contract(off)
-  static_assert(!VS || (WATER && NA == 3), "a site belongs to a rigid water");
-  using R4 = typename Vec<R>::T4;
-  const R *vel = s.vel + off, *f = s.f + off, *pin = s.pos_in + off;
-  R *pout = s.pos_out + off, *vout = s.vel + off;
-  AtomIn<R> x[NA];
-  AtomIn<R> xs{};  // the site: force, and with FIRST && CHECK reference point, limit, charge and slot (p, v: entry snapshot only)
-  if constexpr (VS) {
-#pragma unroll
-    for (int q = 0; q < 3; ++q) {
-      xs.f[q] = f[3 * site + q];
-      xs.r[q] = (FIRST && CHECK) ? s.chk.ref[3 * site + q] : R(0);
-    }
-    xs.q = (FIRST && CHECK) ? s.qs[site] : R(0);
-    xs.h2 = (FIRST && CHECK) ? list_check_limit(s.chk, site) : R(0);
-    xs.slot = (FIRST && CHECK) ? s.inv[site] : 0;
-  }
-#pragma unroll
-  for (int j = 0; j < NA; ++j) {  // every load first (md_load_atom), the positions also without a drift (velocity constraint)
-    const int i = at[j];
-    x[j].m = s.mass[i];
-    x[j].vc = (SECOND && LANGEVIN) ? s.vcoeff[i] : R(0);
-#pragma unroll
-    for (int q = 0; q < 3; ++q) {
-      x[j].v[q] = vel[3 * i + q];
-      x[j].f[q] = f[3 * i + q];
-      x[j].p[q] = pin[3 * i + q];
-      x[j].r[q] = (FIRST && CHECK) ? s.chk.ref[3 * i + q] : R(0);
-    }
-    x[j].q = (FIRST && CHECK) ? s.qs[i] : R(0);
-    x[j].h2 = (FIRST && CHECK) ? list_check_limit(s.chk, i) : R(0);
-    x[j].slot = (FIRST && CHECK) ? s.inv[i] : 0;
-  }
-  if constexpr (FIRST && !SECOND && CHECK) {
-    if (s.snap_pos) {  // the state at the entry of the call (tmdhip_md_restore), as md_step_kernel saves it
-#pragma unroll
-      for (int j = 0; j < NA; ++j) {
-        const int i = at[j];
-#pragma unroll
-        for (int q = 0; q < 3; ++q) {
-          s.snap_pos[3 * i + q] = x[j].p[q];
-          s.snap_vel[3 * i + q] = x[j].v[q];
-          s.snap_f[3 * i + q] = x[j].f[q];
-        }
-        if (s.zero && i < s.nzero) s.zero[i] = 0.0;
-      }
-      if constexpr (VS) {
-#pragma unroll
-        for (int q = 0; q < 3; ++q) {
-          s.snap_pos[3 * site + q] = pin[3 * site + q];
-          s.snap_vel[3 * site + q] = vel[3 * site + q];
-          s.snap_f[3 * site + q] = xs.f[q];
-        }
-        if (s.zero && site < s.nzero) s.zero[site] = 0.0;
-      }
-    }
-  }
-  if (s.f_zero) {
-    R *fz = s.f_zero + off;
-#pragma unroll
-    for (int j = 0; j < NA; ++j)
-#pragma unroll
-      for (int q = 0; q < 3; ++q) fz[3 * at[j] + q] = R(0);
-    if constexpr (VS) {
-#pragma unroll
-      for (int q = 0; q < 3; ++q) fz[3 * site + q] = R(0);
-    }
-  }
-  if constexpr (VS) {  // what tmdhip_vsite_spread stores in the parents' rows, rounding included
-#pragma unroll
-    for (int j = 0; j < NA; ++j)
-#pragma unroll
-      for (int q = 0; q < 3; ++q) x[j].f[q] = vsite_share<R>(x[j].f[q], sw[j], xs.f[q]);
-  }
-  const double dt = (double)s.dt, hdt = (double)s.half_dt, gamma = (double)s.gamma;
-  double p[NA][3], v[NA][3], a[NA][3], im[NA];
-#pragma unroll
-  for (int j = 0; j < NA; ++j) {
-    im[j] = 1.0 / (double)x[j].m;
-#pragma unroll
-    for (int q = 0; q < 3; ++q) {
-      p[j][q] = x[j].p[q];
-      v[j][q] = x[j].v[q];
-      a[j][q] = (double)x[j].f[q] / (double)x[j].m;
-    }
-  }
-  if (SECOND) {
-#pragma unroll
-    for (int j = 0; j < NA; ++j) {
-      if (LANGEVIN) {
-        R g[3];
-        normal3<R>(s.seed, s.noise_step, row0 + (uint64_t)at[j], g[0], g[1], g[2]);
-#pragma unroll
-        for (int q = 0; q < 3; ++q) v[j][q] += -gamma * v[j][q] * dt + (double)g[q] * (double)x[j].vc;
-      }
-#pragma unroll
-      for (int q = 0; q < 3; ++q) v[j][q] += hdt * a[j][q];
-    }
-    if constexpr (NC > 0) cons_velocities<NA, NC, WATER>(p, v, im);
-  }
-  if (FIRST) {
-    double xn[NA][3], u[NA][3];
-#pragma unroll
-    for (int j = 0; j < NA; ++j)
-#pragma unroll
-      for (int q = 0; q < 3; ++q) {
-        xn[j][q] = p[j][q] + (v[j][q] * dt + 0.5 * a[j][q] * dt * dt);
-        u[j][q] = xn[j][q];
-        v[j][q] = v[j][q] + hdt * a[j][q];
-      }
-    bool ok = true;
-    if constexpr (WATER) ok = settle_water(p, xn, (double)x[0].m, (double)x[1].m, d[0], d[1]);
-    else if constexpr (NC > 0) ok = shake_cluster<NA>(p, xn, im, d, k.tol, k.max_iter);
-    if (!ok) *k.fail = 1;
-    R stored[VS ? NA : 1][3];  // (VS) the parents' positions as rounded for storage
-#pragma unroll
-    for (int j = 0; j < NA; ++j) {
-      const int i = at[j];
-      R pr[3];
-#pragma unroll
-      for (int q = 0; q < 3; ++q) {
-        if (NC > 0) v[j][q] += (xn[j][q] - u[j][q]) / dt;
-        pr[q] = (R)xn[j][q];
-        pout[3 * i + q] = pr[q];
-        if constexpr (VS) stored[j][q] = pr[q];
-      }
-      if (CHECK) {
-        R4 sv;
-        sv.x = pr[0];
-        sv.y = pr[1];
-        sv.z = pr[2];
-        sv.w = x[j].q;
-        s.sorted[x[j].slot] = sv;
-        extent_note<R>(s.chk.ext, pr[0], pr[1], pr[2]);
-        list_check_point<R>(s.chk, c, pr[0] - x[j].r[0], pr[1] - x[j].r[1], pr[2] - x[j].r[2], x[j].h2);
-      }
-    }
-    if constexpr (VS) {  // the site, from the stored parents: tmdhip_vsite_construct's expression
-      R pr[3];
-#pragma unroll
-      for (int q = 0; q < 3; ++q) {
-        pr[q] = vsite_coord<R>(sw[0], sw[1], sw[2], stored[0][q], stored[1][q], stored[2][q], true);
-        pout[3 * site + q] = pr[q];
-      }
-      if (CHECK) {
-        R4 sv;
-        sv.x = pr[0];
-        sv.y = pr[1];
-        sv.z = pr[2];
-        sv.w = xs.q;
-        s.sorted[xs.slot] = sv;
-        extent_note<R>(s.chk.ext, pr[0], pr[1], pr[2]);
-        list_check_point<R>(s.chk, c, pr[0] - xs.r[0], pr[1] - xs.r[1], pr[2] - xs.r[2], xs.h2);
-      }
-    }
-  }
-#pragma unroll
-  for (int j = 0; j < NA; ++j)
-#pragma unroll
-    for (int q = 0; q < 3; ++q) vout[3 * at[j] + q] = (R)v[j][q];
-  if constexpr (VS) {
-#pragma unroll
-    for (int q = 0; q < 3; ++q) vout[3 * site + q] = R(0);
-  }
-}
-
-template <typename R, bool SECOND, bool LANGEVIN, bool FIRST, bool CHECK, int NA>
-__device__ __forceinline__ void cons_cluster(const MdStepArgs<R> &s, const PairConsts<R> &c, const ConsArgs &k, int s0, size_t off,
-                                             uint64_t row0) {
-  int at[NA];
-  double d[NA];
-#pragma unroll
-  for (int j = 0; j < NA; ++j) {
-    at[j] = k.catom[s0 + j];
-    d[j] = k.cdist[s0 + j];
-  }
-  cons_unit<R, SECOND, LANGEVIN, FIRST, CHECK, NA, NA - 1, false>(s, c, k, at, d, off, row0);
-}
-
-// Without CHECK (all-pairs contexts) blockIdx.y is the replica, as in md_step_kernel.
-template <typename R, bool SECOND, bool LANGEVIN, bool FIRST, bool CHECK>
-__global__ __launch_bounds__(256) void md_step_cons_kernel(MdStepArgs<R> s, PairConsts<R> c, ConsArgs k) {
-  const int u = blockIdx.x * blockDim.x + threadIdx.x;
-  if (CHECK && u == 0) list_check_clear(s.chk.flags, s.chk.parity);
-  if (u >= k.nunits) return;
-  const size_t off = CHECK ? 0 : (size_t)blockIdx.y * 3 * s.n;
-  const uint64_t row0 = s.row0 + (CHECK ? 0 : (uint64_t)blockIdx.y * (uint64_t)s.n);
-  const int2 e = k.units[u];
-  if (e.x == kConsWater) {
-    const int at[3] = {k.water[3 * e.y], k.water[3 * e.y + 1], k.water[3 * e.y + 2]};
-    const double d[3] = {k.wdist[2 * e.y], k.wdist[2 * e.y + 1], 0.0};
-    cons_unit<R, SECOND, LANGEVIN, FIRST, CHECK, 3, 3, true>(s, c, k, at, d, off, row0);
-  } else if (e.x == kConsCluster) {
-    const int s0 = k.coff[e.y], na = k.coff[e.y + 1] - s0;
-    switch (na) {
-      case 2: cons_cluster<R, SECOND, LANGEVIN, FIRST, CHECK, 2>(s, c, k, s0, off, row0); break;
-      case 3: cons_cluster<R, SECOND, LANGEVIN, FIRST, CHECK, 3>(s, c, k, s0, off, row0); break;
-      case 4: cons_cluster<R, SECOND, LANGEVIN, FIRST, CHECK, 4>(s, c, k, s0, off, row0); break;
-      default: cons_cluster<R, SECOND, LANGEVIN, FIRST, CHECK, 5>(s, c, k, s0, off, row0); break;
-    }
-  } else {
-    const int at[1] = {e.y};
-    const double d[1] = {0.0};
-    cons_unit<R, SECOND, LANGEVIN, FIRST, CHECK, 1, 0, false>(s, c, k, at, d, off, row0);
-  }
-}
-
-// The same for a context with virtual sites: a water with a site is stepped together with it.
-template <typename R, bool SECOND, bool LANGEVIN, bool FIRST, bool CHECK>
-__global__ __launch_bounds__(256) void md_step_cons_vs_kernel(MdStepArgs<R> s, PairConsts<R> c, ConsArgs k, ConsSiteArgs vs) {
-  const int u = blockIdx.x * blockDim.x + threadIdx.x;
-  if (CHECK && u == 0) list_check_clear(s.chk.flags, s.chk.parity);
-  if (u >= k.nunits) return;
-  const size_t off = CHECK ? 0 : (size_t)blockIdx.y * 3 * s.n;
-  const uint64_t row0 = s.row0 + (CHECK ? 0 : (uint64_t)blockIdx.y * (uint64_t)s.n);
-  const int2 e = k.units[u];
-  if (e.x == kConsWater) {
-    const int at[3] = {k.water[3 * e.y], k.water[3 * e.y + 1], k.water[3 * e.y + 2]};
-    const double d[3] = {k.wdist[2 * e.y], k.wdist[2 * e.y + 1], 0.0};
-    const int site = vs.wsite[e.y];
-    if (site >= 0) {
-      const double sw[3] = {vs.wweight[3 * e.y], vs.wweight[3 * e.y + 1], vs.wweight[3 * e.y + 2]};
-      cons_unit<R, SECOND, LANGEVIN, FIRST, CHECK, 3, 3, true, true>(s, c, k, at, d, off, row0, site, sw);
-    } else {
-      cons_unit<R, SECOND, LANGEVIN, FIRST, CHECK, 3, 3, true>(s, c, k, at, d, off, row0);
-    }
-  } else if (e.x == kConsCluster) {
-    const int s0 = k.coff[e.y], na = k.coff[e.y + 1] - s0;
-    switch (na) {
-      case 2: cons_cluster<R, SECOND, LANGEVIN, FIRST, CHECK, 2>(s, c, k, s0, off, row0); break;
-      case 3: cons_cluster<R, SECOND, LANGEVIN, FIRST, CHECK, 3>(s, c, k, s0, off, row0); break;
-      case 4: cons_cluster<R, SECOND, LANGEVIN, FIRST, CHECK, 4>(s, c, k, s0, off, row0); break;
-      default: cons_cluster<R, SECOND, LANGEVIN, FIRST, CHECK, 5>(s, c, k, s0, off, row0); break;
-    }
-  } else {
-    const int at[1] = {e.y};
-    const double d[1] = {0.0};
-    cons_unit<R, SECOND, LANGEVIN, FIRST, CHECK, 1, 0, false>(s, c, k, at, d, off, row0);
-  }
-}
-
-static ConsArgs cons_args(const tmdhip_ctx *ctx) {
-  const ConsState *S = (const ConsState *)ctx->cons;
-  ConsArgs k;
-  k.units = S->units.as<int2>();
-  k.nunits = S->nunits;
-  k.water = S->water.as<int>();
-  k.wdist = S->wdist.as<double>();
-  k.coff = S->coff.as<int>();
-  k.catom = S->catom.as<int>();
-  k.cdist = S->cdist.as<double>();
-  k.tol = S->tol;
-  k.max_iter = S->max_iter;
-  k.fail = S->fail_host;
-  return k;
-}
-
-void cons_release(tmdhip_ctx *ctx) {
-  ConsState *S = (ConsState *)ctx->cons;
-  if (!S) return;
-  for (DevBuf *b : {&S->units, &S->water, &S->wdist, &S->coff, &S->catom, &S->cdist, &S->wsite, &S->wweight}) b->release();
-  if (S->fail_host) (void)hipHostFree(S->fail_host);
-  delete S;
-  ctx->cons = nullptr;
-}
-
-int cons_verdict(tmdhip_ctx *ctx) {
-  ConsState *S = (ConsState *)ctx->cons;
-  if (!S || !S->fail_host || !*(volatile int *)S->fail_host) return 0;
-  *(volatile int *)S->fail_host = 0;
-  return fail("constrained MD step: a SHAKE cluster did not converge within max_iter sweeps, or a water was too distorted for "
-              "SETTLE; the trajectory since the previous call is invalid");
-}
-
-// tmdhip_md_observe: the per-term energies, the kinetic energies and the list flags of every replica written
-// straight into host-mapped memory by one small block, followed by a sequence word the host spins on — instead of
-// three device-to-host copy commands and a stream synchronisation (whose wake-up is the slowest part of a short
-// call).  flags.p[r] = replica r's int[F_COUNT], or null.
-struct ObsFlagPtrs {
-  const int *p[16];
-};
-__global__ void observe_publish_kernel(int nrep, const double *__restrict__ energies, const double *__restrict__ ke,
-                                       ObsFlagPtrs flags, double *host_e, double *host_ke, int *host_flags,
-                                       unsigned *host_seq, unsigned seq) {
-  const int t = threadIdx.x;
-  for (int k = t; k < nrep * TMDHIP_NENERGY; k += blockDim.x) host_e[k] = energies ? energies[k] : 0.0;
-  for (int k = t; k < nrep; k += blockDim.x) host_ke[k] = ke ? ke[k] : 0.0;
-  for (int k = t; k < nrep * F_COUNT; k += blockDim.x) {
-    const int r = k / F_COUNT;
-    host_flags[k] = flags.p[r] ? flags.p[r][k - r * F_COUNT] : 0;
-  }
-  __threadfence_system();
-  __syncthreads();
-  if (t == 0) __hip_atomic_store(host_seq, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-}
-
-// host side of observe_publish_kernel: spin until the device has written `seq` (all results are then in place)
-int wait_observed(volatile unsigned *hseq, unsigned seq, hipStream_t st) {
-  const auto t0 = std::chrono::steady_clock::now();
-  for (unsigned spins = 1; *hseq != seq; ++spins) {
-    __builtin_ia32_pause();
-    if ((spins & 0xFFFFu) == 0 && std::chrono::steady_clock::now() - t0 > std::chrono::seconds(20)) {
-      TMD_HIP(hipStreamSynchronize(st));  // surfaces a device error if there is one
-      if (*hseq != seq) return fail("the device did not report the results of the call");
-    }
-  }
-  std::atomic_thread_fence(std::memory_order_acquire);
-  return 0;
-}
-
-// the launch of the report alone (<= 16 replicas); the caller waits for ctx->obs_seq (wait_observed) when it needs the values
-static int launch_publish(tmdhip_ctx *ctx, const double *energies_dev, const double *ke_dev, bool lists, double *host_e,
-                          double *host_ke, int *host_flags, volatile unsigned *host_seq, hipStream_t st) {
-  const size_t nrep = ctx->rep.size();
-  ObsFlagPtrs fp{};
-  for (size_t r = 0; r < nrep; ++r) fp.p[r] = lists ? ctx->rep[r].flags.as<int>() : nullptr;
-  if (++ctx->obs_seq == 0) ctx->obs_seq = 1;
-  hipLaunchKernelGGL(observe_publish_kernel, dim3(1), dim3(128), 0, st, (int)nrep, energies_dev, ke_dev, fp, host_e, host_ke,
-                     host_flags, const_cast<unsigned *>(host_seq), ctx->obs_seq);
-  TMD_HIP(hipGetLastError());
-  return 0;
-}
-
-int publish_observables(tmdhip_ctx *ctx, const double *energies_dev, const double *ke_dev, bool lists, double *host_e,
-                        double *host_ke, int *host_flags, volatile unsigned *host_seq, hipStream_t st) {
-  TMD_TRY(launch_publish(ctx, energies_dev, ke_dev, lists, host_e, host_ke, host_flags, host_seq, st));
-  return wait_observed(host_seq, ctx->obs_seq, st);
-}
-
-// the host-mapped landing zone of tmdhip_md_observe: energies [R][NENERGY] | kinetic energies [R] | list flags [R][F_COUNT] | sequence word
-struct ObsHost {
-  double *e, *ke;
-  int *flags;
-  volatile unsigned *seq;
-};
-static int obs_host_zone(tmdhip_ctx *ctx, ObsHost &z) {
-  const size_t nrep = ctx->rep.size();
-  const size_t ebytes = sizeof(double) * TMDHIP_NENERGY * nrep, kbytes = sizeof(double) * nrep, fbytes = sizeof(int) * F_COUNT * nrep;
-  if (!ctx->obs_host) {
-    TMD_HIP(hipHostMalloc(&ctx->obs_host, ebytes + kbytes + fbytes + 64, hipHostMallocMapped));
-    std::memset(ctx->obs_host, 0, ebytes + kbytes + fbytes + 64);
-  }
-  z.e = (double *)ctx->obs_host;
-  z.ke = z.e + TMDHIP_NENERGY * nrep;
-  z.flags = (int *)((char *)ctx->obs_host + ebytes + kbytes);
-  z.seq = (volatile unsigned *)((char *)ctx->obs_host + ebytes + kbytes + fbytes + 32);
-  return 0;
-}
-
-// The last kernel of a tmdhip_md_run call whose final step was made by FINAL step blocks (one replica): final_fold_kernel's sums
-// AND observe_publish_kernel's report in one launch (round 6) — the energies of the call, the kinetic energy and the list flags go
-// to the host-mapped zone with the sequence word behind them, so that a tmdhip_md_observe(TMDHIP_OBSERVE_AFTER_RUN) launches
-// nothing and only waits for the word.
-__global__ __launch_bounds__(kEnergySlots) void final_fold_publish_kernel(double *__restrict__ scratch, double *__restrict__ out,
-                                                                          double *__restrict__ ke, const int *__restrict__ flags,
-                                                                          double *host_e, double *host_ke, int *host_flags,
-                                                                          unsigned *host_seq, unsigned seq, int accumulate) {
-  __shared__ double part[kEnergySlots / 64][TMDHIP_NENERGY + 1];
-  double *row = scratch + (size_t)threadIdx.x * kEnergyStride;
-#pragma unroll
-  for (int k = 0; k <= TMDHIP_NENERGY; ++k) {
-    const double v = row[k];
-    if (v != 0.0) row[k] = 0.0;
-    const double s = wave_sum(v);
-    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6][k] = s;
-  }
-  __syncthreads();
-  if (threadIdx.x <= TMDHIP_NENERGY) {
-    double s = 0.0;
-#pragma unroll
-    for (int w = 0; w < kEnergySlots / 64; ++w) s += part[w][threadIdx.x];
-    if (threadIdx.x < TMDHIP_NENERGY) {
-      // (accumulate: the bonded kernel of a heavy topology has left its energies there already; a plain evaluation overwrites)
-      const double e = accumulate ? out[threadIdx.x] + s : s;
-      if (s != 0.0 || !accumulate) out[threadIdx.x] = e;
-      host_e[threadIdx.x] = e;
-    } else {
-      ke[0] = s;
-      host_ke[0] = s;
-    }
-  } else if (threadIdx.x >= 64 && threadIdx.x < 64 + F_COUNT) {
-    host_flags[threadIdx.x - 64] = flags ? flags[threadIdx.x - 64] : 0;
-  }
-  __threadfence_system();
-  __syncthreads();
-  if (threadIdx.x == 0) __hip_atomic_store(host_seq, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-}
-
 // state at the entry of an MD batch (positions, velocities, forces) in one launch; n4 = 16-byte words per array
 __global__ void snapshot3_kernel(size_t n4, const uint4 *__restrict__ a, const uint4 *__restrict__ b,
                                  const uint4 *__restrict__ c, uint4 *__restrict__ out, double *__restrict__ zero,
@@ -546,27 +112,6 @@ void launch_md_step(const MdStepArgs<R> &a, const PairConsts<R> &c, bool check, 
     hipLaunchKernelGGL((md_step_kernel<R, SECOND, LANGEVIN, FIRST, false>), grid, block, 0, st, a, c);
 }
 
-// the integrator kernel of one phase of md_run: the constrained form when the context has constraints
-template <typename R, bool SECOND, bool LANGEVIN, bool FIRST>
-void launch_step(const tmdhip_ctx *ctx, const MdStepArgs<R> &a, const PairConsts<R> &c, bool check, hipStream_t st, int nrep = 1) {
-  if (!ctx->cons) return launch_md_step<R, SECOND, LANGEVIN, FIRST>(a, c, check, st, nrep);
-  const ConsArgs k = cons_args(ctx);
-  const dim3 grid((k.nunits + 255) / 256, check ? 1 : nrep), block(256);
-  const ConsState *S = (const ConsState *)ctx->cons;
-  if (S->has_sites) {
-    const ConsSiteArgs vs{S->wsite.as<int>(), S->wweight.as<double>()};
-    if (check)
-      hipLaunchKernelGGL((md_step_cons_vs_kernel<R, SECOND, LANGEVIN, FIRST, true>), grid, block, 0, st, a, c, k, vs);
-    else
-      hipLaunchKernelGGL((md_step_cons_vs_kernel<R, SECOND, LANGEVIN, FIRST, false>), grid, block, 0, st, a, c, k, vs);
-    return;
-  }
-  if (check)
-    hipLaunchKernelGGL((md_step_cons_kernel<R, SECOND, LANGEVIN, FIRST, true>), grid, block, 0, st, a, c, k);
-  else
-    hipLaunchKernelGGL((md_step_cons_kernel<R, SECOND, LANGEVIN, FIRST, false>), grid, block, 0, st, a, c, k);
-}
-
 template <typename R>
 void launch_md_step_bonded(const MdStepArgs<R> &a, const PairConsts<R> &c, const BondedArgs<R> &A, bool langevin,
                            bool check, const R *boxes, int nrep, hipStream_t st) {
@@ -584,9 +129,6 @@ constexpr int64_t kChainSkipMinEntries = 1'000'000;  // list slots from which th
                                                     // at 2e7 "because shorter pair kernels cannot hide the host"; measured in round 3 with the gate
                                                     // open, water boxes, us per MD step: 5 184 atoms 23.9 -> 22.6, 12 288 atoms 34.6 -> 28.6,
                                                     // 24 000 atoms 42.4 -> 36.8, bit-identical trajectories.)
-constexpr double kChainSkipNear = 0.75;  // "near": beyond this fraction of the displacement limit (0.15 A of room at
-                                         // skin 1.2: 2.2 x the largest per-step move seen in the water box, 9.5
-                                         // standard deviations of a hydrogen's thermal velocity at 300 K)
 
 // spin until the device has published sequence number `target` (wrap-around safe); false after 0.2 s
 bool wait_published(volatile unsigned *hp, unsigned target) {
@@ -598,6 +140,35 @@ bool wait_published(volatile unsigned *hp, unsigned target) {
     if ((spins & 4095u) == 0 && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(200)) return false;
   }
 }
+
+// a list exists and was built for this box
+inline bool list_matches_box(const Replica &rp, const double *box) {
+  return rp.have_list && box[0] == rp.box[0] && box[1] == rp.box[1] && box[2] == rp.box[2];
+}
+
+template <typename R>
+int pace_behind_device(Replica &rp, ListCheck<R> &chk, bool follows, double near_frac, bool &timed_out, bool &skip_chain) {
+  if (!rp.hostpub) {
+    TMD_HIP(hipHostMalloc((void **)&rp.hostpub, 8 * sizeof(unsigned), hipHostMallocMapped));
+    for (int w = 0; w < 8; ++w) rp.hostpub[w] = 0u;
+    rp.seq = 0;
+    rp.seq_valid = false;
+  }
+  if (rp.seq_valid && follows && !timed_out && !wait_published(rp.hostpub, rp.seq)) timed_out = true;
+  const PaceStep p = pace_decide(rp.hostpub, rp.seq, rp.seq_valid, follows, timed_out, rp.prev_skipped);
+  skip_chain = rp.prev_skipped = p.skip_chain;
+  rp.seq = p.seq;
+  chk.near_host = rp.hostpub + 1 + (rp.seq & 1u);
+  chk.seq = rp.seq;
+  chk.near_frac2 = (R)(near_frac * near_frac);
+  chk.skipped = skip_chain ? 1 : 0;
+  rp.seq_valid = true;
+  rp.pub_ptr = rp.hostpub;
+  rp.pub_val = rp.seq;
+  return 0;
+}
+template int pace_behind_device<float>(Replica &, ListCheck<float> &, bool, double, bool &, bool &);
+template int pace_behind_device<double>(Replica &, ListCheck<double> &, bool, double, bool &, bool &);
 
 // the static arguments of the fused step travel as a kernel argument (stream-ordered, no pinned staging, no host wait)
 template <typename R>
@@ -620,6 +191,33 @@ int upload_fused_static(Replica &rp, const FusedStaticT<R> &now, hipStream_t st)
 template int upload_fused_static<float>(Replica &, const FusedStaticT<float> &, hipStream_t);
 template int upload_fused_static<double>(Replica &, const FusedStaticT<double> &, hipStream_t);
 
+template <typename R>
+void fused_static_common(FusedStaticT<R> &now, int n, R *vel, const R *mass, const R *vcoeff, double dt, R gamma, uint64_t seed,
+                         uint64_t row0, const R *qs, const int *inv, const ListCheck<R> &chk, double near_frac) {
+  std::memset(&now, 0, sizeof(now));
+  now.s.n = n;
+  now.s.vel = vel;
+  now.s.mass = mass;
+  now.s.vcoeff = vcoeff;
+  now.s.dt = (R)dt;
+  now.s.half_dt = (R)(0.5 * dt);
+  now.s.gamma = gamma;
+  now.s.seed = seed;
+  now.s.row0 = row0;
+  now.s.qs = qs;
+  now.s.inv = inv;
+  now.s.chk.ref = chk.ref;
+  now.s.chk.hard2 = chk.hard2;
+  now.s.chk.hs2 = chk.hs2;
+  now.s.chk.flags = chk.flags;
+  now.s.chk.near_frac2 = (R)(near_frac * near_frac);
+  now.s.chk.ext = chk.ext;
+}
+template void fused_static_common<float>(FusedStaticT<float> &, int, float *, const float *, const float *, double, float, uint64_t, uint64_t,
+                                         const float *, const int *, const ListCheck<float> &, double);
+template void fused_static_common<double>(FusedStaticT<double> &, int, double *, const double *, const double *, double, double, uint64_t,
+                                          uint64_t, const double *, const int *, const ListCheck<double> &, double);
+
 // can the pair launch of this replica integrate the next step itself?  (lean fp32 kernel, 4 .. 64 lanes per atom: a pair
 // block's atoms fit one wave of a step block.  fp64: built in round 4, bit-identical and slower — 151 against 124.5 us
 // per step at C3, no partial last round of pair blocks for the step blocks to hide in — and removed in round 5.)
@@ -633,7 +231,6 @@ bool fused_step_possible(const tmdhip_ctx *ctx, const Replica &rp, const PairCon
   const bool only_lj_el = c.terms != 0 && (c.terms & ~(TMDHIP_TERM_LJ | TMDHIP_TERM_ELECTROSTATICS)) == 0;
   return only_lj_el && ctx->d.ntypes <= kEntryTypes && rp.lg.lpa >= 4 && rp.lg.lpa <= 64 && kFastThreads / rp.lg.lpa <= 64;
 }
-
 
 // ---- a plain evaluation with energies in TWO launches behind the displacement test (tmdhip_compute, round 6) -------------------------
 // Cell-list contexts in fp32 with one replica and a light topology (water, ions): the ENERGY variant of the lean pair launch with
@@ -651,7 +248,7 @@ int compute_fused_eval(tmdhip_ctx *ctx, const void *pos_dev, const double *box, 
     return 0;
   Replica &rp = ctx->rep[0];
   const PairConsts<float> c = make_consts<float>(ctx, box);
-  if (!rp.have_list || box[0] != rp.box[0] || box[1] != rp.box[1] || box[2] != rp.box[2] || !fused_step_possible<float>(ctx, rp, c)) return 0;
+  if (!list_matches_box(rp, box) || !fused_step_possible<float>(ctx, rp, c)) return 0;
   BondedArgs<float> A;
   std::memset(&A, 0, sizeof(A));
   if (tmd::bonded_inline_args(ctx, box, A) != 1) return 0;
@@ -673,10 +270,7 @@ int compute_fused_eval(tmdhip_ctx *ctx, const void *pos_dev, const double *box, 
   const int rc = compute_list<float>(ctx, rp, pos_dev, box, forces_dev, e_dev,
                                      TMDHIP_WANT_FORCES | TMDHIP_WANT_ENERGY | TMDHIP_OVERWRITE_FORCES | kSpecChain, st, &fl);
   if (rc != 0) return rc < 0 ? rc : fail("tmdhip_compute: the fused evaluation could not be enqueued");
-  if (++ctx->obs_seq == 0) ctx->obs_seq = 1;
-  hipLaunchKernelGGL(final_fold_publish_kernel, dim3(1), dim3(kEnergySlots), 0, st, ctx->escratch.as<double>(), e_dev, scratch_ke,
-                     rp.flags.as<int>(), host_e, host_ke, host_flags, const_cast<unsigned *>(host_seq), ctx->obs_seq, 0);
-  TMD_HIP(hipGetLastError());
+  TMD_TRY(launch_final_fold_publish(ctx, rp, e_dev, scratch_ke, host_e, host_ke, host_flags, host_seq, 0, st));
   return 1;
 }
 
@@ -695,17 +289,6 @@ struct BatchItem {
   unsigned pub_val;
   double box[3];
 };
-
-// TMDHIP_BATCH_REPLICAS=0: the replica-by-replica loop (A/B, tests; read per call); =2: the batched launch for a single replica
-// too (A/B of the batched kernel against the plain one on the same workload)
-static bool batch_replicas_on() {
-  const char *e = std::getenv("TMDHIP_BATCH_REPLICAS");
-  return !(e && std::atoi(e) == 0);
-}
-static int batch_replicas_min() {
-  const char *e = std::getenv("TMDHIP_BATCH_REPLICAS");
-  return e && std::atoi(e) == 2 ? 1 : 2;
-}
 
 // One launch for the replicas of `items` (all of the context's): table entries that changed are re-uploaded (stream-ordered
 // one-thread kernels), the per-launch words travel as the kernel argument.  `energy`: the call's last step (FINAL step blocks).
@@ -740,7 +323,7 @@ static int launch_replica_batch(tmdhip_ctx *ctx, std::vector<BatchItem> &items, 
         TMD_HIP(hipMemsetAsync(rp.fsort.p, 0, rp.fsort.bytes, st));  // launch number 0 = never written
         rp.fused_gen = 0;
       }
-      if (++rp.fused_gen == 0) rp.fused_gen = 1;
+      rp.fused_gen = next_seq(rp.fused_gen);
       rp.fused_launches++;
       const PairConsts<float> c = make_consts<float>(ctx, it.box);
       BatchRep e;
@@ -789,495 +372,542 @@ static int launch_replica_batch(tmdhip_ctx *ctx, std::vector<BatchItem> &items, 
   return 0;
 }
 
+// ---- tmdhip_md_run ----------------------------------------------------------------------------------------------------
+static bool env_is_zero(const char *name) {
+  const char *e = std::getenv(name);
+  return e && std::atoi(e) == 0;
+}
+
+// what an iteration knows about one replica between its pacing, its integrator kernel and its forces
 template <typename R>
-int md_run(tmdhip_ctx *ctx, const tmdhip_md_desc *d, hipStream_t st) {
+struct RepStep {
+  int r;
+  Replica &rp;
+  const double *box;
+  R *home, *f;  // the caller's position / force rows of the replica
+  PairConsts<R> c;
+  bool list;         // the forces come from the Verlet list (until a box too small for cells makes the context fall back)
+  bool check;        // the displacement test rides on the integrator kernel: a list exists for this box
+  bool zeroed;       // the integrator kernel clears `f` for the all-pairs launch
+  bool pace = false, skip_chain = false;  // chain skipping: the host paces itself / leaves this step's rebuild chain out
+  bool was_stepped = false;               // the previous pair launch has made this iteration's step
+};
+
+// One tmdhip_md_run call: the state that lives across its iterations (it = 0 .. niter: first half step of step `it` behind
+// the second half of step it - 1) and the steps an iteration is made of.
+template <typename R>
+struct MdRun {
   using R4 = typename Vec<R>::T4;
-  const int n = ctx->d.natoms;
-  // TMDHIP_CHAIN_SKIP=0 switches the feature off; the two DEBUG knobs let a test reach the violation + rewind path
-  // on a small box (minimum list size, "near" fraction: > 1 = an atom is never reported near its limit)
-  const char *e_on = std::getenv("TMDHIP_CHAIN_SKIP"), *e_min = std::getenv("TMDHIP_DEBUG_CHAIN_MIN_ENTRIES"),
-             *e_near = std::getenv("TMDHIP_DEBUG_CHAIN_NEAR");
-  const bool chain_skip_on = !(e_on && std::atoi(e_on) == 0) && !ctx->no_chain_skip_once;
-  const int64_t chain_min_entries = e_min ? std::atoll(e_min) : kChainSkipMinEntries;
-  const double chain_near = e_near ? std::atof(e_near) : kChainSkipNear;
-  ctx->no_chain_skip_once = false;
-  ctx->fused_off_call = ctx->no_fused_once;
-  ctx->no_fused_once = false;
-  bool pace_timed_out = false;  // the device did not report within wait_published's limit: no more waiting in this call
-  const int nrep = (int)ctx->rep.size();
-  const bool langevin = d->vcoeff_dev != nullptr;
-  const size_t stride = (size_t)n * 3;
+  static constexpr bool kF32 = std::is_same<R, float>::value;
+  tmdhip_ctx *const ctx;
+  const tmdhip_md_desc *const d;
+  const hipStream_t st;
+  const int n, nrep;
+  const size_t stride;
+  const bool langevin;
+  // The knobs, read once per call (tests switch them within a process).  TMDHIP_CHAIN_SKIP=0 switches the feature off; the two
+  // DEBUG knobs let a test reach the violation + rewind path on a small box (minimum list size, "near" fraction: > 1 = an atom
+  // is never reported near its limit).  TMDHIP_FUSED_FINAL=0: the separate kernels behind the last pair launch.
+  // TMDHIP_BATCH_REPLICAS=0: the replica-by-replica loop; =2: the batched launch for a single replica too (A/B of the batched
+  // kernel against the plain one on the same workload).  TMDHIP_REPLICA_REBUILDS=together (list_build.hip: chain_any): every
+  // replica is in the batched rebuild launch as soon as one is.
+  bool chain_skip_on, final_on, rebuilds_together;
+  int64_t chain_min_entries;
+  double chain_near;
+  int batch_min;  // replicas from which an iteration batches
   MdStepArgs<R> a{};
-  a.n = n;
-  a.mass = (const R *)d->mass_dev;
-  a.vcoeff = (const R *)d->vcoeff_dev;
-  a.dt = (R)d->dt;
-  a.half_dt = (R)(0.5 * d->dt);
-  a.gamma = (R)d->gamma;
-  a.seed = d->seed;
-  a.qs = ctx->qs.as<R>();
   // where each replica's positions currently live (caller's tensor, or the context's second buffer while
   // the bonded force is evaluated inside the integrator kernel) and whether the bonded force of the
   // last evaluation is still owed to `forces`
-  std::vector<R *> cur(nrep);
-  std::vector<char> owed(nrep, 0);
-  std::vector<char> stepped(nrep, 0);  // the previous pair launch of the replica has made this iteration's step (FusedStep)
-  std::vector<char> finalized(nrep, 0);  // the last pair launch made the call's final kick, bonded force and energies itself (FINAL step blocks)
-  ctx->ke_from_run = nullptr;
-  ctx->run_published_seq = 0;
-  const char *e_final = std::getenv("TMDHIP_FUSED_FINAL");  // (A/B, tests: 0 = the separate kernels behind the last pair launch)
-  const bool final_on = !(e_final && std::atoi(e_final) == 0);
-  for (int r = 0; r < nrep; ++r) cur[r] = (R *)d->pos_dev + r * stride;
+  std::vector<R *> cur;
+  std::vector<char> owed;
+  std::vector<char> stepped;    // the previous pair launch of the replica has made this iteration's step (FusedStep)
+  std::vector<char> finalized;  // the last pair launch made the call's final kick, bonded force and energies itself (FINAL step blocks)
   // the same for the replica-batched all-pairs mode (all replicas move together)
-  R *const home_all = (R *)d->pos_dev;
-  R *bcur = home_all;
+  R *const home_all;
+  R *bcur;
   bool bowed = false;
+  bool pace_timed_out = false;  // the device did not report within wait_published's limit: no more waiting in this call
+  // an iteration that ends in ONE batched launch: what the walk over the replicas collects for it
+  std::vector<BatchItem> batch_items;
+  bool batching = false;
+  int batch_bonded = 0;
+  int it = 0;
+  bool first = true, second = false;
 
-  if (ctx->snap_pending) {
+  MdRun(tmdhip_ctx *ctx_, const tmdhip_md_desc *d_, hipStream_t st_)
+      : ctx(ctx_), d(d_), st(st_), n(ctx_->d.natoms), nrep((int)ctx_->rep.size()), stride((size_t)ctx_->d.natoms * 3),
+        langevin(d_->vcoeff_dev != nullptr), cur(nrep), owed(nrep, 0), stepped(nrep, 0), finalized(nrep, 0),
+        home_all((R *)d_->pos_dev), bcur((R *)d_->pos_dev) {
+    const char *e_min = std::getenv("TMDHIP_DEBUG_CHAIN_MIN_ENTRIES"), *e_near = std::getenv("TMDHIP_DEBUG_CHAIN_NEAR"),
+               *e_batch = std::getenv("TMDHIP_BATCH_REPLICAS"), *e_tog = std::getenv("TMDHIP_REPLICA_REBUILDS");
+    chain_skip_on = !env_is_zero("TMDHIP_CHAIN_SKIP") && !ctx->no_chain_skip_once;
+    chain_min_entries = e_min ? std::atoll(e_min) : kChainSkipMinEntries;
+    chain_near = e_near ? std::atof(e_near) : kChainSkipNear;
+    final_on = !env_is_zero("TMDHIP_FUSED_FINAL");
+    batch_min = !e_batch ? 2 : std::atoi(e_batch) == 0 ? std::numeric_limits<int>::max() : std::atoi(e_batch) == 2 ? 1 : 2;
+    rebuilds_together = e_tog && std::strcmp(e_tog, "together") == 0;
+    ctx->no_chain_skip_once = false;
+    ctx->fused_off_call = ctx->no_fused_once;
+    ctx->no_fused_once = false;
+    ctx->ke_from_run = nullptr;
+    ctx->run_published_seq = 0;
+    a.n = n;
+    a.mass = (const R *)d->mass_dev;
+    a.vcoeff = (const R *)d->vcoeff_dev;
+    a.dt = (R)d->dt;
+    a.half_dt = (R)(0.5 * d->dt);
+    a.gamma = (R)d->gamma;
+    a.seed = d->seed;
+    a.qs = ctx->qs.as<R>();
+    for (int r = 0; r < nrep; ++r) cur[r] = (R *)d->pos_dev + r * stride;
+  }
+
+  bool list_context() const { return ctx->algorithm == TMDHIP_ALGO_CELLLIST && ctx->d.terms != 0; }
+  bool wants_energy() const { return it == d->niter - 1 && d->energies_dev; }
+  // THE definition of "the pair launch of this replica can make a step": a list built for this box, a lean kernel, no
+  // constraints (the unfused kernels only — a step block owns 64 cell-sorted atoms, a water's atoms straddle them)
+  bool can_fuse(const Replica &rp, const double *box, const PairConsts<R> &c) const {
+    return list_context() && list_matches_box(rp, box) && !ctx->cons && fused_step_possible<R>(ctx, rp, c);
+  }
+  // ... and of the steps it can make.  Interior steps: the launch makes the next step.  The last step of a call that wants
+  // energies (`en`): the launch makes the final kick, the bonded force + energies and the kinetic energy (FINAL step blocks),
+  // `final_ok`: where the caller has a fold kernel behind it.
+  bool fusable_step(bool en, bool final_ok) const { return en ? it + 1 == d->niter && final_ok && final_on : it + 1 < d->niter; }
+  // the integrator kernel of this iteration's phase: the constrained form when the context has constraints
+  void launch_step(const PairConsts<R> &c, bool check, int reps) {
+    if (ctx->cons) return launch_cons_step<R>(ctx, a, c, second, langevin, first, check, reps, st);
+    for_md_phase(second, langevin, first, [&](auto s, auto l, auto f) {
+      launch_md_step<R, decltype(s)::value, decltype(l)::value, decltype(f)::value>(a, c, check, st, reps);
+    });
+  }
+
+  int run() {
+    TMD_TRY(snapshot_unless_first_kernel_takes_it());
+    for (it = 0; it <= d->niter; ++it) {
+      first = it < d->niter;
+      second = it > 0;
+      a.noise_step = d->step0 + (uint64_t)(it > 0 ? it - 1 : 0);
+      if (nrep > 1 && (ctx->algorithm == TMDHIP_ALGO_ALLPAIRS || ctx->d.terms == 0)) {
+        TMD_TRY(step_all_replicas_together());
+        continue;
+      }
+      plan_batch();
+      for (int r = 0; r < nrep; ++r) {
+        RepStep<R> s = begin_replica(r);
+        TMD_TRY(pace(s));
+        TMD_TRY(integrate(s));
+        if (first) TMD_TRY(forces(s));
+      }
+      if constexpr (kF32) {
+        if (batching) TMD_TRY(finish_batch());
+      }
+    }
+    return copy_home();
+  }
+
+  int snapshot_unless_first_kernel_takes_it() {
+    if (!ctx->snap_pending) return 0;
     // the first kernel of the call takes the snapshot only when it is the plain first half step of a list replica with a valid
     // list (the common case); otherwise the copy kernel runs after all
-    const Replica &rp0 = ctx->rep[0];
-    const double *box0 = d->box_host;
-    const bool takes = nrep == 1 && ctx->algorithm == TMDHIP_ALGO_CELLLIST && ctx->d.terms != 0 && rp0.have_list &&
-                       box0[0] == rp0.box[0] && box0[1] == rp0.box[1] && box0[2] == rp0.box[2];
-    if (!takes) {
-      const size_t bytes = sizeof(R) * stride * nrep, n4 = bytes / 16;
-      hipLaunchKernelGGL(snapshot3_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, st, n4, (const uint4 *)d->pos_dev,
-                         (const uint4 *)d->vel_dev, (const uint4 *)d->forces_dev, ctx->snap.as<uint4>(), ctx->snap_zero, ctx->snap_nzero);
-      TMD_HIP(hipGetLastError());
-      ctx->snap_pending = false;
-    }
+    if (nrep == 1 && list_context() && list_matches_box(ctx->rep[0], d->box_host)) return 0;
+    const size_t bytes = sizeof(R) * stride * nrep, n4 = bytes / 16;
+    hipLaunchKernelGGL(snapshot3_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, st, n4, (const uint4 *)d->pos_dev,
+                       (const uint4 *)d->vel_dev, (const uint4 *)d->forces_dev, ctx->snap.as<uint4>(), ctx->snap_zero, ctx->snap_nzero);
+    TMD_HIP(hipGetLastError());
+    ctx->snap_pending = false;
+    return 0;
   }
-  for (int it = 0; it <= d->niter; ++it) {
-    const bool first = it < d->niter, second = it > 0;
-    a.noise_step = d->step0 + (uint64_t)(it > 0 ? it - 1 : 0);
-    if (nrep > 1 && (ctx->algorithm == TMDHIP_ALGO_ALLPAIRS || ctx->d.terms == 0)) {
-      // small systems are launch-bound: one launch of every kernel serves all replicas
-      for (int r = 0; r < nrep; ++r) {  // leftovers of a cell-list context that fell back to all pairs in this call
-        R *home = home_all + r * stride;
-        if (owed[r]) {
-          TMD_TRY(tmdhip_compute_bonded(ctx, r, cur[r], d->box_host + 3 * r, (R *)d->forces_dev + r * stride, nullptr,
-                                        TMDHIP_WANT_FORCES, st));
-          owed[r] = 0;
-        }
-        if (cur[r] != home) {
-          TMD_HIP(hipMemcpyAsync(home, cur[r], sizeof(R) * stride, hipMemcpyDeviceToDevice, st));
-          cur[r] = home;
-        }
+
+  // All-pairs contexts (or none of the pair terms) with several replicas: small systems are launch-bound, one launch of every
+  // kernel serves all replicas
+  int step_all_replicas_together() {
+    for (int r = 0; r < nrep; ++r) {  // leftovers of a cell-list context that fell back to all pairs in this call
+      R *home = home_all + r * stride;
+      if (owed[r]) {
+        TMD_TRY(tmdhip_compute_bonded(ctx, r, cur[r], d->box_host + 3 * r, (R *)d->forces_dev + r * stride, nullptr,
+                                      TMDHIP_WANT_FORCES, st));
+        owed[r] = 0;
       }
-      R *f = (R *)d->forces_dev;
-      const PairConsts<R> c = make_consts<R>(ctx, d->box_host);
-      a.pos_in = a.pos_out = bcur;
-      a.vel = (R *)d->vel_dev;
-      a.f = f;
-      a.f_zero = (first && ctx->d.terms != 0) ? f : nullptr;  // saves the zero-fill launch of the all-pairs path
-      a.row0 = 0;
-      BondedArgs<R> A;
-      if (bowed) {
-        // (second && first) the bonded force of step it-1 is evaluated inside the integrator kernel from
-        // the undrifted positions in bcur; the drifted ones go to the other buffer
-        const bool ok = tmd::bonded_inline_args(ctx, d->box_host, A) == 1;
-        const R *boxes = (const R *)tmd::set_boxes(ctx, d->box_host, st);
-        if (!ok || !boxes) return fail("tmdhip_md_run: inline bonded state lost");
-        R *other = bcur == home_all ? ctx->pos_alt_all.as<R>() : home_all;
-        a.pos_out = other;
-        launch_md_step_bonded<R>(a, c, A, langevin, false, boxes, nrep, st);
-        bcur = other;
-        bowed = false;
-      } else if (second && first) {
-        if (langevin) launch_step<R, true, true, true>(ctx, a, c, false, st, nrep);
-        else launch_step<R, true, false, true>(ctx, a, c, false, st, nrep);
-      } else if (first) {
-        launch_step<R, false, false, true>(ctx, a, c, false, st, nrep);
-      } else {
-        if (langevin) launch_step<R, true, true, false>(ctx, a, c, false, st, nrep);
-        else launch_step<R, true, false, false>(ctx, a, c, false, st, nrep);
+      if (cur[r] != home) {
+        TMD_HIP(hipMemcpyAsync(home, cur[r], sizeof(R) * stride, hipMemcpyDeviceToDevice, st));
+        cur[r] = home;
       }
-      TMD_HIP(hipGetLastError());
-      if (!first) continue;
-      R *pos = bcur;
-      int flags_c = TMDHIP_WANT_FORCES;
-      double *en = nullptr;
-      if (it == d->niter - 1 && d->energies_dev) {
-        flags_c |= TMDHIP_WANT_ENERGY;
-        en = d->energies_dev;
-      }
-      const int bmode = tmd::bonded_inline_args(ctx, d->box_host, A);  // 0 none, 1 light, 2 heavy topology
-      bool bonded_done = bmode == 0;
-      if (ctx->d.terms != 0) {
-        for (auto &rp : ctx->rep) rp.n_compute++;
-        // heavy topologies, few atoms in total (launch-bound): the bonded terms ride on the all-pairs launch
-        // (one wave per atom).  Measured: alanine dipeptide x1 39 -> 32 us/step, but x16 replicas 84 -> 94.
-        const bool ride = bmode == 2 && (size_t)n * nrep <= kRideMaxAtoms;
-        TMD_TRY(launch_allpairs<R>(ctx, pos, d->box_host, f, en, flags_c | TMDHIP_OVERWRITE_FORCES | kForcesZeroed,
-                                   nullptr, st, nrep, ride ? &A : nullptr));
-        for (int r = 0; r < nrep && ctx->pme; ++r)  // reciprocal-space part of every replica (pme.hip)
-          TMD_TRY(pme_hook(ctx, r, pos + r * stride, d->box_host + 3 * r, f + r * stride, en ? en + (size_t)r * TMDHIP_NENERGY : nullptr,
-                           flags_c, st));
-        bonded_done = bonded_done || ride;
-      } else {
-        TMD_HIP(hipMemsetAsync(f, 0, sizeof(R) * stride * nrep, st));
-      }
-      if (!bonded_done) {
-        if (it + 1 < d->niter && bmode == 1 && !ctx->cons) {
-          TMD_TRY(ctx->pos_alt_all.ensure(sizeof(R) * stride * nrep));
-          bowed = true;  // the next integrator kernel evaluates this step's bonded force itself
-        } else {
-          TMD_TRY(tmdhip_compute_bonded(ctx, TMDHIP_ALL_REPLICAS, pos, d->box_host, f, en, flags_c, st));
-        }
-      }
-      continue;
     }
-    // The replicas of a cell-list context in ONE pair + step launch (round 6): when every replica of this iteration would make a
-    // fused launch of its own — same conditions as below — the loop over the replicas does the per-replica part (pacing, the
-    // first half step of a call, the rebuild chain) and the launch follows behind it.
-    std::vector<BatchItem> batch_items;
-    bool batching = false;
-    int batch_bonded = 0;
-    if constexpr (std::is_same<R, float>::value) {
-      const bool want_e = it == d->niter - 1 && d->energies_dev;
-      const bool interior = it + 1 < d->niter && !want_e, final_step = it + 1 == d->niter && want_e && final_on;
-      batching = first && !ctx->cons && nrep >= batch_replicas_min() && ctx->algorithm == TMDHIP_ALGO_CELLLIST && ctx->d.terms != 0 && (interior || final_step) &&
-                 batch_replicas_on();
-      for (int r = 0; batching && r < nrep; ++r) {
-        const Replica &rp = ctx->rep[r];
-        const double *box = d->box_host + 3 * r;
-        const PairConsts<R> c = make_consts<R>(ctx, box);
-        BondedArgs<R> A;
-        std::memset(&A, 0, sizeof(A));
-        batching = rp.have_list && box[0] == rp.box[0] && box[1] == rp.box[1] && box[2] == rp.box[2] && !owed[r] && !finalized[r] &&
-                   fused_step_possible<R>(ctx, rp, c) && rp.lg.lpa == ctx->rep[0].lg.lpa;
-        if (batching) {
-          const int bm = tmd::bonded_inline_args(ctx, box, A);
-          batching = bm >= 0 && (r == 0 || bm == batch_bonded);
-          batch_bonded = bm;
-        }
+    R *f = (R *)d->forces_dev;
+    const PairConsts<R> c = make_consts<R>(ctx, d->box_host);
+    a.pos_in = a.pos_out = bcur;
+    a.vel = (R *)d->vel_dev;
+    a.f = f;
+    a.f_zero = (first && ctx->d.terms != 0) ? f : nullptr;  // saves the zero-fill launch of the all-pairs path
+    a.row0 = 0;
+    BondedArgs<R> A;
+    if (bowed) {
+      // (second && first) the bonded force of step it-1 is evaluated inside the integrator kernel from
+      // the undrifted positions in bcur; the drifted ones go to the other buffer
+      const bool ok = tmd::bonded_inline_args(ctx, d->box_host, A) == 1;
+      const R *boxes = (const R *)tmd::set_boxes(ctx, d->box_host, st);
+      if (!ok || !boxes) return fail("tmdhip_md_run: inline bonded state lost");
+      R *other = bcur == home_all ? ctx->pos_alt_all.as<R>() : home_all;
+      a.pos_out = other;
+      launch_md_step_bonded<R>(a, c, A, langevin, false, boxes, nrep, st);
+      bcur = other;
+      bowed = false;
+    } else {
+      launch_step(c, false, nrep);
+    }
+    TMD_HIP(hipGetLastError());
+    if (!first) return 0;
+    R *pos = bcur;
+    int flags_c = TMDHIP_WANT_FORCES;
+    double *en = nullptr;
+    if (wants_energy()) {
+      flags_c |= TMDHIP_WANT_ENERGY;
+      en = d->energies_dev;
+    }
+    const int bmode = tmd::bonded_inline_args(ctx, d->box_host, A);  // 0 none, 1 light, 2 heavy topology
+    bool bonded_done = bmode == 0;
+    if (ctx->d.terms != 0) {
+      for (auto &rp : ctx->rep) rp.n_compute++;
+      // heavy topologies, few atoms in total (launch-bound): the bonded terms ride on the all-pairs launch
+      // (one wave per atom).  Measured: alanine dipeptide x1 39 -> 32 us/step, but x16 replicas 84 -> 94.
+      const bool ride = bmode == 2 && (size_t)n * nrep <= kRideMaxAtoms;
+      TMD_TRY(launch_allpairs<R>(ctx, pos, d->box_host, f, en, flags_c | TMDHIP_OVERWRITE_FORCES | kForcesZeroed,
+                                 nullptr, st, nrep, ride ? &A : nullptr));
+      for (int r = 0; r < nrep && ctx->pme; ++r)  // reciprocal-space part of every replica (pme.hip)
+        TMD_TRY(pme_hook(ctx, r, pos + r * stride, d->box_host + 3 * r, f + r * stride, en ? en + (size_t)r * TMDHIP_NENERGY : nullptr,
+                         flags_c, st));
+      bonded_done = bonded_done || ride;
+    } else {
+      TMD_HIP(hipMemsetAsync(f, 0, sizeof(R) * stride * nrep, st));
+    }
+    if (bonded_done) return 0;
+    if (it + 1 < d->niter && bmode == 1 && !ctx->cons) {
+      TMD_TRY(ctx->pos_alt_all.ensure(sizeof(R) * stride * nrep));
+      bowed = true;  // the next integrator kernel evaluates this step's bonded force itself
+    } else {
+      TMD_TRY(tmdhip_compute_bonded(ctx, TMDHIP_ALL_REPLICAS, pos, d->box_host, f, en, flags_c, st));
+    }
+    return 0;
+  }
+
+  // The replicas of a cell-list context in ONE pair + step launch (round 6): when every replica of this iteration would make a
+  // fused launch of its own, the walk over the replicas does the per-replica part (pacing, the first half step of a call, the
+  // rebuild chain) and the launch follows behind it (finish_batch).  Beyond can_fuse: nothing owed or finalized, and one kernel
+  // shape (lanes per atom, bonded mode) for all.
+  void plan_batch() {
+    batching = kF32 && first && nrep >= batch_min && list_context() && fusable_step(wants_energy(), true);
+    batch_bonded = 0;
+    for (int r = 0; batching && r < nrep; ++r) {
+      const Replica &rp = ctx->rep[r];
+      const double *box = d->box_host + 3 * r;
+      BondedArgs<R> A;
+      std::memset(&A, 0, sizeof(A));
+      batching = can_fuse(rp, box, make_consts<R>(ctx, box)) && !owed[r] && !finalized[r] && rp.lg.lpa == ctx->rep[0].lg.lpa;
+      if (batching) {
+        const int bm = tmd::bonded_inline_args(ctx, box, A);
+        batching = bm >= 0 && (r == 0 || bm == batch_bonded);
+        batch_bonded = bm;
       }
-      if (batching) batch_items.resize(nrep);
+    }
+    if (batching) batch_items.resize(nrep);
+  }
+
+  RepStep<R> begin_replica(int r) {
+    Replica &rp = ctx->rep[r];
+    const double *box = d->box_host + 3 * r;
+    R *f = (R *)d->forces_dev + r * stride;
+    const bool list = list_context();
+    a.vel = (R *)d->vel_dev + r * stride;
+    a.f = f;
+    a.f_zero = (first && !list && ctx->d.terms != 0) ? f : nullptr;
+    a.row0 = (uint64_t)r * (uint64_t)n;
+    rp.skin_vel = a.vel;  // a rebuild in this step sizes the skins from the current velocities
+    a.chk = make_check<R>(ctx, rp);
+    // the displacement test can ride on the integrator kernel when a list exists for this box
+    return {r, rp, box, (R *)d->pos_dev + r * stride, f, make_consts<R>(ctx, box), list, first && list && list_matches_box(rp, box),
+            a.f_zero != nullptr};
+  }
+
+  // Chain skipping (ListCheck): on large lists the host stays one step behind the device — it waits until the
+  // pair kernel of the previous step has started (45 us of kernel time are then still ahead of it) — and
+  // leaves the rebuild chain out when no atom was near its limit in that step.  On the first step of a call only
+  // if the caller says that nothing has moved since the previous one (tmdhip_md_desc::continuation; the report is
+  // then the previous call's last), never in the repetition of a rewound batch.
+  int pace(RepStep<R> &s) {
+    s.pace = s.check && chain_skip_on && (int64_t)n * s.rp.lg.maxn >= chain_min_entries;
+    if (s.pace) return pace_behind_device<R>(s.rp, a.chk, it > 0 || d->continuation != 0, chain_near, pace_timed_out, s.skip_chain);
+    // (the final kick of a call — it == niter, no drift, no test — leaves the report of the call's last step valid:
+    // that is what the next call's first step looks at when the caller vouches for a continuation.  Round 4: this
+    // branch used to clear it for every iteration without pacing, which made the hint a no-op.)
+    if (first) s.rp.seq_valid = false;
+    s.rp.pub_ptr = nullptr;
+    return 0;
+  }
+
+  // this iteration's kicks and drift of the replica, by whoever makes them
+  int integrate(RepStep<R> &s) {
+    Replica &rp = s.rp;
+    const int r = s.r;
+    a.sorted = rp.sorted.as<R4>();
+    a.inv = rp.inv.as<int>();
+    a.pos_in = a.pos_out = cur[r];
+    s.was_stepped = stepped[r] != 0;
+    stepped[r] = 0;
+    if (finalized[r]) {
+      // (it == niter: the final kick was made by the step blocks of the last pair launch)
+    } else if (s.was_stepped) {
+      // kicks, drift, displacement test and cell-sorted records of this iteration: done by the previous pair
+      // launch's epilogue (cur[r] and rp.sorted already point at its output)
+    } else if (owed[r]) {
+      // second && first always holds here: the bonded force of step it-1 is evaluated from the
+      // undrifted positions in cur[r], the drifted ones go to the other buffer
+      BondedArgs<R> A;
+      std::memset(&A, 0, sizeof(A));
+      if (tmd::bonded_inline_args(ctx, s.box, A) != 1) return fail("tmdhip_md_run: inline bonded state lost");
+      R *other = cur[r] == s.home ? rp.pos_alt.as<R>() : s.home;
+      a.pos_out = other;
+      launch_md_step_bonded<R>(a, s.c, A, langevin, s.check, nullptr, 1, st);
+      cur[r] = other;
+      owed[r] = 0;
+    } else if (first && !second) {
+      // Every fused step moves the positions to the other buffer; with an odd number of them ahead (all interior
+      // steps of the call, if the first one can be fused) the drift of this first step goes to the second buffer,
+      // so that the call ends in the caller's tensor without a copy.  (Whatever the call's last step does: no look at `en`.)
+      if (s.check && cur[r] == s.home && d->niter >= 2 && ((d->niter - 1) & 1) && can_fuse(rp, s.box, s.c)) {
+        TMD_TRY(rp.pos_alt.ensure(sizeof(R) * stride));
+        a.pos_out = rp.pos_alt.as<R>();
+        cur[r] = a.pos_out;
+      }
+      if (ctx->snap_pending && s.check && nrep == 1) {  // (tmdhip_md_run left the snapshot of the entry state to this kernel)
+        const size_t padded = (sizeof(R) * stride + 15) / 16 * 16;
+        a.snap_pos = ctx->snap.as<R>();
+        a.snap_vel = (R *)(ctx->snap.as<char>() + padded);
+        a.snap_f = (R *)(ctx->snap.as<char>() + 2 * padded);
+        a.zero = ctx->snap_zero;
+        a.nzero = ctx->snap_nzero;
+        ctx->snap_pending = false;
+      }
+      launch_step(s.c, s.check, 1);
+      a.snap_pos = a.snap_vel = a.snap_f = nullptr;
+      a.zero = nullptr;
+    } else {
+      launch_step(s.c, s.check, 1);
+    }
+    TMD_HIP(hipGetLastError());
+    return 0;
+  }
+
+  // The pair launch of the replica makes a step itself (FusedStepT) where it can: `fuse`, with the launch's arguments in `fl`.
+  int fused_launch_args(const RepStep<R> &s, R *pos, double *en, FusedLaunchT<R> &fl, bool &fuse) {
+    Replica &rp = s.rp;
+    BondedArgs<R> A;
+    std::memset(&A, 0, sizeof(A));
+    // (the call's last step: FINAL step blocks need the fold kernel of one replica, or of the batch)
+    const int bm = (s.check && fusable_step(en != nullptr, (nrep == 1 || batching) && kF32) && can_fuse(rp, s.box, s.c))
+                       ? tmd::bonded_inline_args(ctx, s.box, A) : -1;
+    fuse = bm >= 0;
+    if (!fuse) return 0;
+    if (bm == 2) {
+      // heavy topology: the bonded force depends on the positions only — it is evaluated in front of the
+      // pair launch into a buffer of its own and the step blocks add it (same values, same order as the
+      // separate kernels: pair force stored, bonded force added, divided by the mass)
+      // (the final step: with its energies, which the bonded kernel folds into the call's buffer itself)
+      TMD_TRY(rp.fbond.ensure(sizeof(R) * stride));
+      TMD_TRY(tmdhip_compute_bonded(ctx, s.r, pos, s.box, rp.fbond.p, en,
+                                    TMDHIP_WANT_FORCES | TMDHIP_OVERWRITE_FORCES | (en ? TMDHIP_WANT_ENERGY : 0), st));
+    }
+    FusedStaticT<R> now;
+    fused_static_common<R>(now, n, a.vel, a.mass, a.vcoeff, d->dt, a.gamma, a.seed, a.row0, a.qs, a.inv, a.chk, chain_near);
+    if (bm == 1) std::memcpy(&now.A, &A, sizeof(A));
+    now.has_bonded = bm;
+    now.fbond = bm == 2 ? rp.fbond.as<R>() : nullptr;
+    now.nactive = 0x7fffffff;
+    TMD_TRY(rp.pos_alt.ensure(sizeof(R) * stride));
+    TMD_TRY(upload_fused_static(rp, now, st));
+    fl.fst = rp.fused_dev.as<FusedStaticT<R>>();
+    fl.langevin = langevin;
+    fl.step.pos_in = pos;
+    fl.step.pos_out = pos == s.home ? rp.pos_alt.as<R>() : s.home;
+    fl.step.sorted_out = rp.sorted_alt.as<R4>();
+    fl.step.noise_step = d->step0 + (uint64_t)it;
+    fl.step.bonded = bm;
+    if (s.pace) {  // the next iteration's sequence number (see pace_behind_device)
+      fl.step.seq = next_seq(rp.seq);
+      fl.step.near_host = rp.hostpub + 1 + (fl.step.seq & 1u);
+    }
+    return 0;
+  }
+
+  // forces of step `it` (forces.py:122-319): nonbonded stores (list path) or accumulates into zeros
+  int forces(RepStep<R> &s) {
+    Replica &rp = s.rp;
+    const int r = s.r;
+    R *pos = cur[r];
+    int flags_c = TMDHIP_WANT_FORCES;
+    double *en = nullptr;
+    if (wants_energy()) {
+      flags_c |= TMDHIP_WANT_ENERGY;
+      en = d->energies_dev + (size_t)r * TMDHIP_NENERGY;
+    }
+    BondedArgs<R> A;
+    std::memset(&A, 0, sizeof(A));
+    if (ctx->d.terms != 0) {
+      rp.n_compute++;
+      if (s.list) {
+        bool complete = false;
+        TMD_TRY(list_forces(s, pos, flags_c, en, complete));
+        if (complete) return 0;
+      }
+      if (!s.list) {
+        // heavy topology, small system: bonded terms in the same launch
+        const bool ride = tmd::bonded_inline_args(ctx, s.box, A) == 2 && (size_t)n <= kRideMaxAtoms;
+        TMD_TRY(launch_allpairs<R>(ctx, pos, s.box, s.f, en, flags_c | TMDHIP_OVERWRITE_FORCES | (s.zeroed ? kForcesZeroed : 0), nullptr,
+                                   st, 1, ride ? &A : nullptr));
+        TMD_TRY(pme_hook(ctx, r, pos, s.box, s.f, en, flags_c, st));
+        if (ride) return 0;  // forces (and energies) of this step are complete
+      }
+    } else {
+      TMD_HIP(hipMemsetAsync(s.f, 0, sizeof(R) * stride, st));
+    }
+    // interior step: the next integrator kernel evaluates this step's bonded force itself
+    // (md_step_bonded_kernel); `forces` holds the pair part until then.  (All-pairs contexts with several
+    // replicas take step_all_replicas_together from the next iteration on.)
+    if (((s.list && rp.have_list) || (!s.list && nrep == 1)) && it + 1 < d->niter && !ctx->cons &&
+        tmd::bonded_inline_args(ctx, s.box, A) == 1) {
+      TMD_TRY(rp.pos_alt.ensure(sizeof(R) * stride));
+      owed[r] = 1;
+    } else {
+      TMD_TRY(tmdhip_compute_bonded(ctx, r, pos, s.box, s.f, en, flags_c, st));
+    }
+    return 0;
+  }
+
+  // The list launch of the replica and its outcomes.  `complete`: nothing is left to do for this step — the launch was FINAL,
+  // or made the next step (its forces never reach `forces`), or the replica's blocks are in the batched launch behind the
+  // walk.  Otherwise the bonded part follows, behind an all-pairs launch if the box turned out too small for cells (s.list).
+  int list_forces(RepStep<R> &s, R *pos, int flags_c, double *en, bool &complete) {
+    Replica &rp = s.rp;
+    const int r = s.r;
+    FusedLaunchT<R> fl{};
+    bool fuse = false;
+    TMD_TRY(fused_launch_args(s, pos, en, fl, fuse));
+    const int flags_l = flags_c | TMDHIP_OVERWRITE_FORCES | (s.check ? kPrechecked : 0) | (s.skip_chain ? kSkipChain : 0) |
+                        (s.skip_chain && s.was_stepped ? kViolationCheck : 0);
+    complete = true;
+    if constexpr (kF32) {
+      if (batching) {  // list bookkeeping of this replica now, its blocks in the launch behind the walk
+        if (!fuse) return fail("tmdhip_md_run: a replica of the batch cannot make a fused launch");
+        BatchItem &bi = batch_items[r];
+        bi.fl = fl;
+        bi.pos = pos;
+        bi.home = s.home;
+        bi.f = s.f;
+        for (int k = 0; k < 3; ++k) bi.box[k] = s.box[k];
+        bi.lo = ListOnlyOut{};
+        TMD_TRY(compute_list<R>(ctx, rp, pos, s.box, s.f, en, flags_l | kListOnly | kDeferChain, st, &fl, &bi.lo));
+        bi.pub_ptr = rp.pub_ptr;
+        bi.pub_val = rp.pub_val;
+        rp.pub_ptr = nullptr;
+        return 0;
+      }
+    }
+    BondedArgs<R> A;
+    const int rc = compute_list<R>(ctx, rp, pos, s.box, s.f, en,
+                                   flags_l | (en && !fuse && rp.have_list && tmd::bonded_inline_args(ctx, s.box, A) != 0 ? kDeferFold : 0),
+                                   st, fuse ? &fl : nullptr);
+    rp.pub_ptr = nullptr;
+    if (fuse && rc == 0 && en) {
+      // the call's last step: forces (pair + bonded) are in `forces`, velocities kicked, the energy rows (pair,
+      // bonded, kinetic) folded here — into the call's energy buffer and the context's kinetic-energy word
+      TMD_TRY(ctx->obs_ke.ensure(sizeof(double) * ctx->rep.size()));
+      if (nrep == 1) {  // ... and reported to the host in the same launch (tmdhip_md_observe then only waits for the word)
+        TMD_TRY(publish_final_step(ctx, rp, en, st));
+      } else {
+        hipLaunchKernelGGL(final_fold_kernel, dim3(1), dim3(kEnergySlots), 0, st, ctx->escratch.as<double>(), en,
+                           ctx->obs_ke.as<double>());
+        TMD_HIP(hipGetLastError());
+      }
+      note_final_step();
+      finalized[r] = 1;
+    } else if (fuse && rc == 0) {
+      cur[r] = fl.step.pos_out;
+      std::swap(rp.sorted, rp.sorted_alt);
+      stepped[r] = 1;
+      rp.steps_in_pair_launch++;
+    } else if (rc == kFallbackAllPairs) {
+      ctx->algorithm = TMDHIP_ALGO_ALLPAIRS;
+      s.list = complete = false;
+    } else if (rc != 0) {
+      return rc;
+    } else {
+      complete = false;
+      TMD_TRY(pme_hook(ctx, r, pos, s.box, s.f, en, flags_c, st));
+    }
+    return 0;
+  }
+
+  // FINAL step blocks have summed the kinetic energy of the call's last velocities (tmdhip_md_observe need not)
+  void note_final_step() {
+    ctx->ke_from_run = d->vel_dev;
+    ctx->ke_from_run_mass = d->mass_dev;
+    ctx->final_steps_in_pair_launch++;
+  }
+
+  int finish_batch() {
+    const bool want_e = wants_energy();
+    {  // the rebuild chains the host has not left out: one launch per kernel for all of them
+      std::vector<int> reps, par;
+      std::vector<const float *> ps;
+      std::vector<const double *> bx;
+      bool any_chain = false;
+      for (int r = 0; r < nrep; ++r) any_chain = any_chain || batch_items[r].lo.chain;
+      const bool everybody = any_chain && rebuilds_together;
+      for (int r = 0; r < nrep; ++r)
+        if (batch_items[r].lo.chain || everybody) {
+          reps.push_back(r);
+          // (a replica whose chain the host had left out: compute_list has counted the step already)
+          par.push_back(batch_items[r].lo.chain ? batch_items[r].lo.chain_parity : (int)((ctx->rep[r].step - 1) & 1));
+          ps.push_back(batch_items[r].pos);
+          bx.push_back(batch_items[r].box);
+        }
+      if (!reps.empty()) TMD_TRY(enqueue_chain_batch<float>(ctx, (int)reps.size(), reps.data(), ps.data(), par.data(), bx.data(), st));
+    }
+    TMD_TRY(launch_replica_batch(ctx, batch_items, batch_bonded, d->step0 + (uint64_t)it, want_e, langevin, st));
+    if (want_e) {
+      // the call's last step: forces (pair + bonded) in `forces`, velocities kicked; one fold block per replica adds its
+      // scratch rows (pair, bonded, kinetic) into the call's energy buffer and the context's kinetic-energy words
+      TMD_TRY(ctx->obs_ke.ensure(sizeof(double) * ctx->rep.size()));
+      hipLaunchKernelGGL(final_fold_kernel, dim3(nrep), dim3(kEnergySlots), 0, st, ctx->escratch.as<double>(), d->energies_dev,
+                         ctx->obs_ke.as<double>());
+      TMD_HIP(hipGetLastError());
+      for (int r = 0; r < nrep; ++r) finalized[r] = 1;
+      note_final_step();
+      return 0;
     }
     for (int r = 0; r < nrep; ++r) {
       Replica &rp = ctx->rep[r];
-      const double *box = d->box_host + 3 * r;
-      R *home = (R *)d->pos_dev + r * stride, *f = (R *)d->forces_dev + r * stride;
-      const PairConsts<R> c = make_consts<R>(ctx, box);
-      bool list = ctx->algorithm == TMDHIP_ALGO_CELLLIST && ctx->d.terms != 0;
-      // the displacement test can ride on the integrator kernel when a list exists for this box
-      const bool check = first && list && rp.have_list && box[0] == rp.box[0] && box[1] == rp.box[1] && box[2] == rp.box[2];
-      a.vel = (R *)d->vel_dev + r * stride;
-      a.f = f;
-      a.f_zero = (first && !list && ctx->d.terms != 0) ? f : nullptr;
-      const bool zeroed = a.f_zero != nullptr;
-      a.row0 = (uint64_t)r * (uint64_t)n;
-      rp.skin_vel = a.vel;  // a rebuild in this step sizes the skins from the current velocities
-      a.chk = make_check<R>(ctx, rp);
-      // Chain skipping (ListCheck): on large lists the host stays one step behind the device — it waits until the
-      // pair kernel of the previous step has started (45 us of kernel time are then still ahead of it) — and
-      // leaves the rebuild chain out when no atom was near its limit in that step.  On the first step of a call only
-      // if the caller says that nothing has moved since the previous one (tmdhip_md_desc::continuation; the report is
-      // then the previous call's last), never in the repetition of a rewound batch.
-      bool skip_chain = false;
-      const bool pace = check && chain_skip_on && (int64_t)n * rp.lg.maxn >= chain_min_entries;
-      if (pace) {
-        if (!rp.hostpub) {
-          TMD_HIP(hipHostMalloc((void **)&rp.hostpub, 8 * sizeof(unsigned), hipHostMallocMapped));
-          for (int w = 0; w < 8; ++w) rp.hostpub[w] = 0u;
-          rp.seq = 0;
-          rp.seq_valid = false;
-        }
-        volatile unsigned *hp = rp.hostpub;
-        // (the first step of a call: only when the caller vouches that nothing has moved since the previous call)
-        const bool follows = it > 0 || d->continuation != 0;
-        if (rp.seq_valid && follows && !pace_timed_out && !wait_published(hp, rp.seq)) pace_timed_out = true;
-        if (rp.seq_valid && follows && !pace_timed_out) {
-          // no chain when nobody was near its limit in the previous step — or when that step rebuilt the list
-          // (with its chain in place: every displacement is one step old now)
-          const bool near = hp[1 + (rp.seq & 1u)] == rp.seq, rebuilt = hp[3 + (rp.seq & 1u)] == rp.seq;
-          skip_chain = !near || (rebuilt && !rp.prev_skipped);
-        }
-        rp.prev_skipped = skip_chain;
-        rp.seq += 1;
-        if (rp.seq == 0) rp.seq = 1;  // 0 = nothing published yet
-        a.chk.near_host = rp.hostpub + 1 + (rp.seq & 1u);
-        a.chk.seq = rp.seq;
-        a.chk.near_frac2 = (R)(chain_near * chain_near);
-        a.chk.skipped = skip_chain ? 1 : 0;
-        rp.seq_valid = true;
-        rp.pub_ptr = rp.hostpub;
-        rp.pub_val = rp.seq;
-      } else {
-        // (the final kick of a call — it == niter, no drift, no test — leaves the report of the call's last step valid:
-        // that is what the next call's first step looks at when the caller vouches for a continuation.  Round 4: this
-        // branch used to clear it for every iteration without pacing, which made the hint a no-op.)
-        if (first) rp.seq_valid = false;
-        rp.pub_ptr = nullptr;
-      }
-      a.sorted = rp.sorted.as<R4>();
-      a.inv = rp.inv.as<int>();
-      a.pos_in = a.pos_out = cur[r];
-      BondedArgs<R> A;
-      std::memset(&A, 0, sizeof(A));
-      const bool was_stepped = stepped[r] != 0;
-      stepped[r] = 0;
-      if (finalized[r]) {
-        // (it == niter: the final kick was made by the step blocks of the last pair launch)
-      } else if (was_stepped) {
-        // kicks, drift, displacement test and cell-sorted records of this iteration: done by the previous pair
-        // launch's epilogue (cur[r] and rp.sorted already point at its output)
-      } else if (owed[r]) {
-        // second && first always holds here: the bonded force of step it-1 is evaluated from the
-        // undrifted positions in cur[r], the drifted ones go to the other buffer
-        if (tmd::bonded_inline_args(ctx, box, A) != 1) return fail("tmdhip_md_run: inline bonded state lost");
-        R *other = cur[r] == home ? rp.pos_alt.as<R>() : home;
-        a.pos_out = other;
-        launch_md_step_bonded<R>(a, c, A, langevin, check, nullptr, 1, st);
-        cur[r] = other;
-        owed[r] = 0;
-      } else if (second && first) {
-        if (langevin) launch_step<R, true, true, true>(ctx, a, c, check, st);
-        else launch_step<R, true, false, true>(ctx, a, c, check, st);
-      } else if (first) {
-        // Every fused step moves the positions to the other buffer; with an odd number of them ahead (all interior
-        // steps of the call, if the first one can be fused) the drift of this first step goes to the second buffer,
-        // so that the call ends in the caller's tensor without a copy.
-        if (check && list && cur[r] == home && d->niter >= 2 && ((d->niter - 1) & 1) && !ctx->cons && fused_step_possible<R>(ctx, rp, c)) {
-          TMD_TRY(rp.pos_alt.ensure(sizeof(R) * stride));
-          a.pos_out = rp.pos_alt.as<R>();
-          cur[r] = a.pos_out;
-        }
-        if (ctx->snap_pending && check && nrep == 1) {  // (tmdhip_md_run left the snapshot of the entry state to this kernel)
-          const size_t padded = (sizeof(R) * stride + 15) / 16 * 16;
-          a.snap_pos = ctx->snap.as<R>();
-          a.snap_vel = (R *)(ctx->snap.as<char>() + padded);
-          a.snap_f = (R *)(ctx->snap.as<char>() + 2 * padded);
-          a.zero = ctx->snap_zero;
-          a.nzero = ctx->snap_nzero;
-          ctx->snap_pending = false;
-        }
-        launch_step<R, false, false, true>(ctx, a, c, check, st);
-        a.snap_pos = a.snap_vel = a.snap_f = nullptr;
-        a.zero = nullptr;
-      } else {
-        if (langevin) launch_step<R, true, true, false>(ctx, a, c, check, st);
-        else launch_step<R, true, false, false>(ctx, a, c, check, st);
-      }
-      TMD_HIP(hipGetLastError());
-      if (!first) continue;
-      R *pos = cur[r];
-      // forces of step `it` (forces.py:122-319): nonbonded stores (list path) or accumulates into zeros
-      int flags_c = TMDHIP_WANT_FORCES;
-      double *en = nullptr;
-      if (it == d->niter - 1 && d->energies_dev) {
-        flags_c |= TMDHIP_WANT_ENERGY;
-        en = d->energies_dev + (size_t)r * TMDHIP_NENERGY;
-      }
-      if (ctx->d.terms != 0) {
-        rp.n_compute++;
-        if (list) {
-          // interior step on a lean kernel: the pair launch makes the next step itself (FusedStepT)
-          FusedLaunchT<R> fl{};
-          bool fuse = false;
-          {
-            // interior steps: the launch makes the next step; the last step of a call that wants energies (one replica):
-            // the launch makes the final kick, the bonded force + energies and the kinetic energy (FINAL step blocks)
-            const bool interior = it + 1 < d->niter && !en;
-            const bool final_step = it + 1 == d->niter && en && (nrep == 1 || batching) && final_on && std::is_same<R, float>::value;
-            // (constraints: the unfused kernels only — a step block owns 64 cell-sorted atoms, a water's atoms straddle them)
-            const int bm = (check && (interior || final_step) && !ctx->cons && fused_step_possible<R>(ctx, rp, c))
-                               ? tmd::bonded_inline_args(ctx, box, A) : -1;
-            if (bm >= 0) {
-              if (bm == 2) {
-                // heavy topology: the bonded force depends on the positions only — it is evaluated in front of the
-                // pair launch into a buffer of its own and the step blocks add it (same values, same order as the
-                // separate kernels: pair force stored, bonded force added, divided by the mass)
-                // (the final step: with its energies, which the bonded kernel folds into the call's buffer itself)
-                TMD_TRY(rp.fbond.ensure(sizeof(R) * stride));
-                TMD_TRY(tmdhip_compute_bonded(ctx, r, pos, box, rp.fbond.p, en,
-                                              TMDHIP_WANT_FORCES | TMDHIP_OVERWRITE_FORCES | (en ? TMDHIP_WANT_ENERGY : 0), st));
-              }
-              FusedStaticT<R> now;
-              std::memset(&now, 0, sizeof(now));
-              now.s.n = n;
-              now.s.vel = a.vel;
-              now.s.mass = a.mass;
-              now.s.vcoeff = a.vcoeff;
-              now.s.dt = a.dt;
-              now.s.half_dt = a.half_dt;
-              now.s.gamma = a.gamma;
-              now.s.seed = a.seed;
-              now.s.row0 = a.row0;
-              now.s.qs = a.qs;
-              now.s.inv = a.inv;
-              now.s.chk.ref = a.chk.ref;
-              now.s.chk.hard2 = a.chk.hard2;
-              now.s.chk.hs2 = a.chk.hs2;
-              now.s.chk.flags = a.chk.flags;
-              now.s.chk.near_frac2 = (R)(chain_near * chain_near);
-              now.s.chk.ext = a.chk.ext;
-              if (bm == 1) std::memcpy(&now.A, &A, sizeof(A));
-              now.has_bonded = bm;
-              now.fbond = bm == 2 ? rp.fbond.as<R>() : nullptr;
-              now.nactive = 0x7fffffff;
-              TMD_TRY(rp.pos_alt.ensure(sizeof(R) * stride));
-              TMD_TRY(upload_fused_static(rp, now, st));
-              fl.fst = rp.fused_dev.as<FusedStaticT<R>>();
-              fl.langevin = langevin;
-              fl.step.pos_in = pos;
-              fl.step.pos_out = pos == home ? rp.pos_alt.as<R>() : home;
-              fl.step.sorted_out = rp.sorted_alt.as<R4>();
-              fl.step.noise_step = d->step0 + (uint64_t)it;
-              fl.step.bonded = bm;
-              if (pace) {  // the next iteration's sequence number (see the pacing above)
-                unsigned nseq = rp.seq + 1;
-                if (nseq == 0) nseq = 1;
-                fl.step.seq = nseq;
-                fl.step.near_host = rp.hostpub + 1 + (nseq & 1u);
-              }
-              fuse = true;
-            }
-          }
-          if constexpr (std::is_same<R, float>::value) {
-            if (batching) {  // list bookkeeping of this replica now, its blocks in the launch behind the loop
-              if (!fuse) return fail("tmdhip_md_run: a replica of the batch cannot make a fused launch");
-              BatchItem &bi = batch_items[r];
-              bi.fl = fl;
-              bi.pos = pos;
-              bi.home = home;
-              bi.f = f;
-              for (int k = 0; k < 3; ++k) bi.box[k] = box[k];
-              bi.lo.chain = 0;
-              TMD_TRY(compute_list<R>(ctx, rp, pos, box, f, en,
-                                      flags_c | TMDHIP_OVERWRITE_FORCES | kListOnly | kDeferChain | (check ? kPrechecked : 0) | (skip_chain ? kSkipChain : 0) |
-                                          (skip_chain && was_stepped ? kViolationCheck : 0),
-                                      st, &fl, &bi.lo));
-              bi.pub_ptr = rp.pub_ptr;
-              bi.pub_val = rp.pub_val;
-              rp.pub_ptr = nullptr;
-              continue;
-            }
-          }
-          const int rc = compute_list<R>(ctx, rp, pos, box, f, en,
-                                         flags_c | TMDHIP_OVERWRITE_FORCES | (check ? kPrechecked : 0) |
-                                             (skip_chain ? kSkipChain : 0) |
-                                             (skip_chain && was_stepped ? kViolationCheck : 0) |
-                                             (en && !fuse && rp.have_list && tmd::bonded_inline_args(ctx, box, A) != 0 ? kDeferFold : 0),
-                                         st, fuse ? &fl : nullptr);
-          rp.pub_ptr = nullptr;
-          if (fuse && rc == 0 && en) {
-            // the call's last step: forces (pair + bonded) are in `forces`, velocities kicked, the energy rows (pair,
-            // bonded, kinetic) folded here — into the call's energy buffer and the context's kinetic-energy word
-            TMD_TRY(ctx->obs_ke.ensure(sizeof(double) * ctx->rep.size()));
-            if (nrep == 1) {  // ... and reported to the host in the same launch (tmdhip_md_observe then only waits for the word)
-              ObsHost z;
-              TMD_TRY(obs_host_zone(ctx, z));
-              if (++ctx->obs_seq == 0) ctx->obs_seq = 1;
-              hipLaunchKernelGGL(final_fold_publish_kernel, dim3(1), dim3(kEnergySlots), 0, st, ctx->escratch.as<double>(), en,
-                                 ctx->obs_ke.as<double>(), rp.flags.as<int>(), z.e, z.ke, z.flags, const_cast<unsigned *>(z.seq),
-                                 ctx->obs_seq, 1);
-              ctx->run_published_seq = ctx->obs_seq;
-              ctx->run_published_energies = en;
-            } else {
-              hipLaunchKernelGGL(final_fold_kernel, dim3(1), dim3(kEnergySlots), 0, st, ctx->escratch.as<double>(), en,
-                                 ctx->obs_ke.as<double>());
-            }
-            TMD_HIP(hipGetLastError());
-            finalized[r] = 1;
-            ctx->ke_from_run = d->vel_dev;
-            ctx->ke_from_run_mass = d->mass_dev;
-            ctx->final_steps_in_pair_launch++;
-            continue;
-          }
-          if (fuse && rc == 0) {
-            cur[r] = fl.step.pos_out;
-            std::swap(rp.sorted, rp.sorted_alt);
-            stepped[r] = 1;
-            rp.steps_in_pair_launch++;
-            continue;  // forces of this step never reach `forces`
-          }
-          if (rc == kFallbackAllPairs) {
-            ctx->algorithm = TMDHIP_ALGO_ALLPAIRS;
-            list = false;
-          } else if (rc != 0) {
-            return rc;
-          } else {
-            TMD_TRY(pme_hook(ctx, r, pos, box, f, en, flags_c, st));
-          }
-        }
-        if (!list) {
-          // heavy topology, small system: bonded terms in the same launch
-          const bool ride = tmd::bonded_inline_args(ctx, box, A) == 2 && (size_t)n <= kRideMaxAtoms;
-          TMD_TRY(launch_allpairs<R>(ctx, pos, box, f, en,
-                                     flags_c | TMDHIP_OVERWRITE_FORCES | (zeroed ? kForcesZeroed : 0), nullptr, st, 1,
-                                     ride ? &A : nullptr));
-          TMD_TRY(pme_hook(ctx, r, pos, box, f, en, flags_c, st));
-          if (ride) continue;  // forces (and energies) of this step are complete
-        }
-      } else {
-        TMD_HIP(hipMemsetAsync(f, 0, sizeof(R) * stride, st));
-      }
-      // interior step: the next integrator kernel evaluates this step's bonded force itself
-      // (md_step_bonded_kernel); `forces` holds the pair part until then.  (All-pairs contexts with several
-      // replicas take the batched branch above from the next iteration on.)
-      if (((list && rp.have_list) || (!list && nrep == 1)) && it + 1 < d->niter && !ctx->cons &&
-          tmd::bonded_inline_args(ctx, box, A) == 1) {
-        TMD_TRY(rp.pos_alt.ensure(sizeof(R) * stride));
-        owed[r] = 1;
-      } else {
-        TMD_TRY(tmdhip_compute_bonded(ctx, r, pos, box, f, en, flags_c, st));
-      }
+      cur[r] = batch_items[r].fl.step.pos_out;
+      std::swap(rp.sorted, rp.sorted_alt);
+      stepped[r] = 1;
+      rp.steps_in_pair_launch++;
     }
-    if constexpr (std::is_same<R, float>::value) {
-      if (batching) {
-        const bool want_e = it == d->niter - 1 && d->energies_dev;
-        {  // the rebuild chains the host has not left out: one launch per kernel for all of them
-          std::vector<int> reps, par;
-          std::vector<const float *> ps;
-          std::vector<const double *> bx;
-          // (TMDHIP_REPLICA_REBUILDS=together, list_build.hip: chain_any — every replica is in the launch as soon as one is)
-          const char *e_tog = std::getenv("TMDHIP_REPLICA_REBUILDS");
-          bool any_chain = false;
-          for (int r = 0; r < nrep; ++r) any_chain = any_chain || batch_items[r].lo.chain;
-          const bool everybody = any_chain && e_tog && std::strcmp(e_tog, "together") == 0;
-          for (int r = 0; r < nrep; ++r)
-            if (batch_items[r].lo.chain || everybody) {
-              reps.push_back(r);
-              // (a replica whose chain the host had left out: compute_list has counted the step already)
-              par.push_back(batch_items[r].lo.chain ? batch_items[r].lo.chain_parity : (int)((ctx->rep[r].step - 1) & 1));
-              ps.push_back(batch_items[r].pos);
-              bx.push_back(batch_items[r].box);
-            }
-          if (!reps.empty()) TMD_TRY(enqueue_chain_batch<float>(ctx, (int)reps.size(), reps.data(), ps.data(), par.data(), bx.data(), st));
-        }
-        TMD_TRY(launch_replica_batch(ctx, batch_items, batch_bonded, d->step0 + (uint64_t)it, want_e, langevin, st));
-        if (want_e) {
-          // the call's last step: forces (pair + bonded) in `forces`, velocities kicked; one fold block per replica adds its
-          // scratch rows (pair, bonded, kinetic) into the call's energy buffer and the context's kinetic-energy words
-          TMD_TRY(ctx->obs_ke.ensure(sizeof(double) * ctx->rep.size()));
-          hipLaunchKernelGGL(final_fold_kernel, dim3(nrep), dim3(kEnergySlots), 0, st, ctx->escratch.as<double>(), d->energies_dev,
-                             ctx->obs_ke.as<double>());
-          TMD_HIP(hipGetLastError());
-          for (int r = 0; r < nrep; ++r) finalized[r] = 1;
-          ctx->ke_from_run = d->vel_dev;
-          ctx->ke_from_run_mass = d->mass_dev;
-          ctx->final_steps_in_pair_launch++;
-        } else {
-          for (int r = 0; r < nrep; ++r) {
-            Replica &rp = ctx->rep[r];
-            cur[r] = batch_items[r].fl.step.pos_out;
-            std::swap(rp.sorted, rp.sorted_alt);
-            stepped[r] = 1;
-            rp.steps_in_pair_launch++;
-          }
-        }
-      }
+    return 0;
+  }
+
+  int copy_home() {
+    if (bcur != home_all) TMD_HIP(hipMemcpyAsync(home_all, bcur, sizeof(R) * stride * nrep, hipMemcpyDeviceToDevice, st));
+    for (int r = 0; r < nrep; ++r) {
+      R *home = (R *)d->pos_dev + r * stride;
+      if (cur[r] != home) TMD_HIP(hipMemcpyAsync(home, cur[r], sizeof(R) * stride, hipMemcpyDeviceToDevice, st));
     }
+    return 0;
   }
-  if (bcur != home_all)
-    TMD_HIP(hipMemcpyAsync(home_all, bcur, sizeof(R) * stride * nrep, hipMemcpyDeviceToDevice, st));
-  for (int r = 0; r < nrep; ++r) {
-    R *home = (R *)d->pos_dev + r * stride;
-    if (cur[r] != home) TMD_HIP(hipMemcpyAsync(home, cur[r], sizeof(R) * stride, hipMemcpyDeviceToDevice, st));
-  }
-  return 0;
+};
+
+template <typename R>
+int md_run(tmdhip_ctx *ctx, const tmdhip_md_desc *d, hipStream_t st) {
+  return MdRun<R>(ctx, d, st).run();
 }
 
 template bool fused_step_possible<float>(const tmdhip_ctx *, const Replica &, const PairConsts<float> &);
@@ -1298,7 +928,7 @@ int tmdhip_md_run(tmdhip_ctx *ctx, const tmdhip_md_desc *desc, void *stream) {
   if (!desc->pos_dev || !desc->vel_dev || !desc->forces_dev || !desc->mass_dev || !desc->box_host)
     return fail("tmdhip_md_run: null buffer");
   if (desc->niter == 0) return 0;
-  if (ctx->vsites && !(ctx->cons && ((const ConsState *)ctx->cons)->has_sites))
+  if (ctx->vsites && !cons_has_sites(ctx))
     return fail("tmdhip_md_run: a context with virtual sites steps them with their rigid waters: set the constraints "
                 "(tmdhip_set_constraints after tmdhip_set_vsites)");
   hipStream_t st = (hipStream_t)stream;
@@ -1343,176 +973,8 @@ int tmdhip_md_run(tmdhip_ctx *ctx, const tmdhip_md_desc *desc, void *stream) {
     return fail("tmdhip_md_run: the state at entry was not saved (internal error)");
   }
   ctx->snap_pending = false;
-  // A call that returns energies is followed by tmdhip_md_observe (what Integrator.step does).  Its two launches — kinetic energy,
-  // report to the host — are enqueued HERE, behind the run's last kernel with no host round trip between them (small systems: the
-  // device idled ~20 us per call between the two C calls); tmdhip_md_observe(TMDHIP_OBSERVE_AFTER_RUN) then only waits for the
-  // sequence word.  (One replica on the lean fp32 kernel: the FINAL launch's fold kernel has reported already.)
-  const char *e_rep = std::getenv("TMDHIP_RUN_REPORTS");  // (0: tmdhip_md_observe launches them itself; A/B)
-  if (rc == 0 && desc->energies_dev && ctx->run_published_seq == 0 && ctx->rep.size() <= 16 && !(e_rep && std::atoi(e_rep) == 0)) {
-    ObsHost z;
-    TMD_TRY(obs_host_zone(ctx, z));
-    TMD_TRY(ctx->obs_ke.ensure(sizeof(double) * ctx->rep.size()));
-    if (ctx->ke_from_run != desc->vel_dev || ctx->ke_from_run_mass != desc->mass_dev) {
-      TMD_TRY(tmdhip_kinetic_energy(ctx->d.dtype, (int64_t)ctx->rep.size(), ctx->d.natoms, desc->vel_dev, desc->mass_dev,
-                                    ctx->obs_ke.as<double>(), stream));
-      ctx->ke_from_run = desc->vel_dev;
-      ctx->ke_from_run_mass = desc->mass_dev;
-    }
-    TMD_TRY(launch_publish(ctx, desc->energies_dev, ctx->obs_ke.as<double>(), ctx->algorithm == TMDHIP_ALGO_CELLLIST, z.e, z.ke, z.flags,
-                           z.seq, st));
-    ctx->run_published_seq = ctx->obs_seq;
-    ctx->run_published_energies = desc->energies_dev;
-  }
+  if (rc == 0) TMD_TRY(enqueue_run_report(ctx, desc, st));
   return rc;
-}
-
-int tmdhip_md_observe(tmdhip_ctx *ctx, const void *vel_dev, const void *mass_dev, const double *energies_dev,
-                      double *out_host, int flags, void *stream) {
-  if (!ctx || !vel_dev || !mass_dev || !out_host) return fail("tmdhip_md_observe: null argument");
-  hipStream_t st = (hipStream_t)stream;
-  const size_t nrep = ctx->rep.size();
-  const size_t ebytes = sizeof(double) * TMDHIP_NENERGY * nrep, kbytes = sizeof(double) * nrep;
-  TMD_TRY(ctx->obs_ke.ensure(kbytes));
-  ObsHost z;
-  TMD_TRY(obs_host_zone(ctx, z));
-  double *he = z.e, *hk = z.ke;
-  int *hf = z.flags;
-  volatile unsigned *hseq = z.seq;
-  const bool after_run = (flags & TMDHIP_OBSERVE_AFTER_RUN) && ctx->ke_from_run == vel_dev && ctx->ke_from_run_mass == mass_dev;
-  const bool published = after_run && ctx->run_published_seq != 0 && ctx->run_published_energies == energies_dev;
-  const unsigned published_seq = ctx->run_published_seq;
-  ctx->run_published_seq = 0;
-  if (after_run) {
-    // (the FINAL step blocks of the run that just ended have summed the kinetic energy of these velocities — every replica's —
-    // and the caller vouches that nothing has written them since)
-  } else {
-    TMD_TRY(tmdhip_kinetic_energy(ctx->d.dtype, (int64_t)nrep, ctx->d.natoms, vel_dev, mass_dev, ctx->obs_ke.as<double>(), stream));
-  }
-  ctx->ke_from_run = nullptr;
-  const bool lists = ctx->algorithm == TMDHIP_ALGO_CELLLIST;
-  if (published) {  // the run's last kernel has reported already: nothing to launch
-    TMD_TRY(wait_observed(hseq, published_seq, st));
-  } else if (nrep <= 16) {
-    TMD_TRY(publish_observables(ctx, energies_dev, ctx->obs_ke.as<double>(), lists, he, hk, hf, hseq, st));
-  } else {
-    if (energies_dev) TMD_HIP(hipMemcpyAsync(he, energies_dev, ebytes, hipMemcpyDeviceToHost, st));
-    else std::memset(he, 0, ebytes);
-    TMD_HIP(hipMemcpyAsync(hk, ctx->obs_ke.p, kbytes, hipMemcpyDeviceToHost, st));
-    if (lists)
-      for (size_t r = 0; r < nrep; ++r)
-        TMD_HIP(hipMemcpyAsync(hf + r * F_COUNT, ctx->rep[r].flags.p, sizeof(int) * F_COUNT, hipMemcpyDeviceToHost, st));
-    TMD_HIP(hipStreamSynchronize(st));
-  }
-  TMD_TRY(cons_verdict(ctx));  // (every kernel of the run has finished: its report has arrived)
-  int verdict = 0;
-  if (lists && ctx->algorithm == TMDHIP_ALGO_CELLLIST)
-    for (size_t r = 0; r < nrep; ++r)
-      if (ctx->rep[r].have_list) {
-        const int rc = judge_flags(ctx, ctx->rep[r], hf + r * F_COUNT, st);
-        if (rc < 0) return rc;
-        verdict |= rc;
-      }
-  for (size_t r = 0; r < nrep; ++r) {
-    for (int k = 0; k < TMDHIP_NENERGY; ++k) out_host[r * (TMDHIP_NENERGY + 1) + k] = energies_dev ? he[r * TMDHIP_NENERGY + k] : 0.0;
-    out_host[r * (TMDHIP_NENERGY + 1) + TMDHIP_NENERGY] = hk[r];
-  }
-  return verdict;
-}
-
-int tmdhip_set_constraints(tmdhip_ctx *ctx, const tmdhip_constraint_desc *desc) {
-  if (!ctx || !desc) return fail("tmdhip_set_constraints: null argument");
-  if (desc->struct_size != (int32_t)sizeof(tmdhip_constraint_desc))
-    return fail("tmdhip_set_constraints: tmdhip_constraint_desc size mismatch (ABI)");
-  cons_release(ctx);
-  if (!desc->enable || (desc->nwaters <= 0 && desc->nclusters <= 0)) return 0;
-  const int n = ctx->d.natoms, nw = std::max(desc->nwaters, 0), nc = std::max(desc->nclusters, 0);
-  if ((nw && (!desc->water_host || !desc->water_dist_host)) ||
-      (nc && (!desc->cluster_offsets_host || !desc->cluster_atoms_host || !desc->cluster_dist_host)))
-    return fail("tmdhip_set_constraints: null array");
-  if (!(desc->tolerance > 0) || desc->max_iter < 1) return fail("tmdhip_set_constraints: tolerance must be > 0 and max_iter >= 1");
-  // units ordered by their first atom: neighbouring threads touch neighbouring atoms
-  std::vector<int> owner(n, -1);
-  std::vector<std::pair<int, int2>> units;
-  auto take = [&](int i, int tag) {
-    if (i < 0 || i >= n) return fail("tmdhip_set_constraints: atom index out of range");
-    if (owner[i] >= 0) return fail("tmdhip_set_constraints: atom " + std::to_string(i) + " is in two constraint units");
-    owner[i] = tag;
-    return 0;
-  };
-  for (int w = 0; w < nw; ++w) {
-    const int32_t *a = desc->water_host + 3 * w;
-    const double doh = desc->water_dist_host[2 * w], dhh = desc->water_dist_host[2 * w + 1];
-    if (!(doh > 0) || !(dhh > 0) || !(dhh < 2 * doh)) return fail("tmdhip_set_constraints: water distances must satisfy 0 < d_HH < 2 d_OH");
-    for (int j = 0; j < 3; ++j) TMD_TRY(take(a[j], 1));
-    units.push_back({std::min({a[0], a[1], a[2]}), make_int2(kConsWater, w)});
-  }
-  const int32_t *off = desc->cluster_offsets_host;
-  if (nc && off[0] != 0) return fail("tmdhip_set_constraints: cluster offsets must start at 0");
-  for (int q = 0; q < nc; ++q) {
-    const int na = off[q + 1] - off[q];
-    if (na < 2 || na > 5) return fail("tmdhip_set_constraints: a cluster has 2 .. 5 atoms (1 .. 4 constraints)");
-    int lo = n;
-    for (int j = off[q]; j < off[q + 1]; ++j) {
-      TMD_TRY(take(desc->cluster_atoms_host[j], 2));
-      if (j > off[q] && !(desc->cluster_dist_host[j] > 0)) return fail("tmdhip_set_constraints: bond lengths must be positive");
-      lo = std::min(lo, (int)desc->cluster_atoms_host[j]);
-    }
-    units.push_back({lo, make_int2(kConsCluster, q)});
-  }
-  // virtual sites: each belongs to the water whose O, H1, H2 are its parents (in this order), and is no unit of its own
-  const VsiteState *V = (const VsiteState *)ctx->vsites;
-  std::vector<int32_t> wsite;
-  std::vector<double> wweight;
-  if (V) {
-    std::vector<int> water_of(n, -1);
-    for (int w = 0; w < nw; ++w) water_of[desc->water_host[3 * w]] = w;
-    wsite.assign(nw, -1);
-    wweight.assign(3 * (size_t)nw, 0.0);
-    for (int s = 0; s < V->nsites; ++s) {
-      const int32_t *pa = V->parent_h.data() + 3 * (size_t)s;
-      const int w = (pa[0] >= 0 && pa[0] < n) ? water_of[pa[0]] : -1;
-      if (w < 0 || wsite[w] >= 0 || pa[1] != desc->water_host[3 * w + 1] || pa[2] != desc->water_host[3 * w + 2])
-        return fail("tmdhip_set_constraints: the parents of virtual site " + std::to_string(V->site_h[s]) +
-                    " are not the O, H1, H2 (in this order) of one rigid water");
-      TMD_TRY(take(V->site_h[s], 3));
-      wsite[w] = V->site_h[s];
-      for (int k = 0; k < 3; ++k) wweight[3 * (size_t)w + k] = V->weight_h[3 * (size_t)s + k];
-    }
-  }
-  for (int i = 0; i < n; ++i)
-    if (owner[i] < 0) units.push_back({i, make_int2(kConsAtom, i)});
-  std::sort(units.begin(), units.end(), [](const std::pair<int, int2> &x, const std::pair<int, int2> &y) { return x.first < y.first; });
-  std::vector<int2> u(units.size());
-  for (size_t j = 0; j < units.size(); ++j) u[j] = units[j].second;
-  auto *S = new ConsState();
-  ctx->cons = S;
-  auto up = [&](DevBuf &b, const void *src, size_t bytes) {
-    TMD_TRY(b.ensure(std::max<size_t>(bytes, 16)));
-    if (bytes) TMD_HIP(hipMemcpy(b.p, src, bytes, hipMemcpyHostToDevice));
-    return 0;
-  };
-  const int ncat = nc ? off[nc] : 0;
-  int rc = up(S->units, u.data(), sizeof(int2) * u.size());
-  if (!rc) rc = up(S->water, desc->water_host, sizeof(int32_t) * 3 * nw);
-  if (!rc) rc = up(S->wdist, desc->water_dist_host, sizeof(double) * 2 * nw);
-  if (!rc) rc = up(S->coff, desc->cluster_offsets_host, nc ? sizeof(int32_t) * (nc + 1) : 0);
-  if (!rc) rc = up(S->catom, desc->cluster_atoms_host, sizeof(int32_t) * ncat);
-  if (!rc) rc = up(S->cdist, desc->cluster_dist_host, sizeof(double) * ncat);
-  if (!rc && V && nw) {
-    rc = up(S->wsite, wsite.data(), sizeof(int32_t) * nw);
-    if (!rc) rc = up(S->wweight, wweight.data(), sizeof(double) * 3 * nw);
-    S->has_sites = !rc;
-  }
-  if (!rc && hipHostMalloc((void **)&S->fail_host, 64, hipHostMallocMapped) != hipSuccess) rc = fail("tmdhip_set_constraints: hipHostMalloc failed");
-  if (rc) {
-    cons_release(ctx);
-    return rc;
-  }
-  *(volatile int *)S->fail_host = 0;
-  S->nunits = (int)u.size();
-  S->tol = desc->tolerance;
-  S->max_iter = desc->max_iter;
-  return 0;
 }
 
 int tmdhip_md_restore(tmdhip_ctx *ctx, const tmdhip_md_desc *desc, void *stream) {

@@ -302,4 +302,15 @@ __device__ __forceinline__ void fused_step_blocks(const FusedStaticT<R> *__restr
   }
 }
 
+// The five phases of an MD-loop iteration as template arguments: f(SECOND, LANGEVIN, FIRST) with std::bool_constant values.
+// (The first half step alone draws no noise; the last iteration is the final kick alone.)
+template <typename F>
+inline void for_md_phase(bool second, bool langevin, bool first, F &&f) {
+  constexpr std::true_type T{};
+  constexpr std::false_type N{};
+  if (second && first) langevin ? f(T, T, T) : f(T, N, T);
+  else if (first) f(N, N, T);
+  else langevin ? f(T, T, N) : f(T, N, N);
+}
+
 }  // namespace tmd
