@@ -1112,6 +1112,63 @@ def test_replica_batch_recovers_like_the_loop(trouble, monkeypatch):
     assert all(100.0 < t < 3000.0 for t in ob[2])  # (jittered lattice starts are hot)
 
 
+@pytest.mark.parametrize("env", [{"TMDHIP_BATCH_PREP_SMALL": "1"}, {"TMDHIP_BIN2": "0"}, {"TMDHIP_BIN2": "0", "TMDHIP_PREP_SMALL": "0"}],
+                         ids=["batched_one_launch", "no_two_launch", "own_chains"])
+def test_replica_batch_chains_from_one_plan_match_the_loop(env, monkeypatch):
+    """The rebuild chains of a replica batch are planned once (list_build.hip: plan_chain) and launched batched or lone from the
+    same plans; three replicas of the 5 184-atom box, 24 steps, as `eighteen_replicas` above.  TMDHIP_BATCH_PREP_SMALL=1: the
+    batched chain bins in one launch instead of two.  TMDHIP_BIN2=0: no member arrays, so the two-launch binning does not apply
+    and a batched row bins in one launch as well.  With TMDHIP_PREP_SMALL=0 on top no batched binning is left: every replica gets
+    a lone four-launch chain from its batch plan.  Each time positions, velocities and forces are bit-identical to the replica
+    loop (TMDHIP_BATCH_REPLICAS=0) with as many replays, and the pair + step launches stay batched."""
+    import numpy as np
+
+    from torchmd_amd.builders import tip3p_box, water_forcefield
+    from torchmd_amd.forces import Forces
+    from torchmd_amd.integrator import Integrator, maxwell_boltzmann
+    from torchmd_amd.parameters import Parameters
+    from torchmd_amd.systems import System
+
+    dev, dt = torch.device("cuda:0"), torch.float32
+    terms = ["lj", "electrostatics", "bonds", "angles"]
+    monkeypatch.setenv("TMDHIP_DEBUG_CHAIN_MIN_ENTRIES", "1")
+    for var in ("TMDHIP_BATCH_PREP_SMALL", "TMDHIP_PREP_SMALL", "TMDHIP_BIN2"):
+        monkeypatch.delenv(var, raising=False)
+    for var, val in env.items():
+        monkeypatch.setenv(var, val)
+    mol, pos, box = tip3p_box(12, seed=6)
+    R, steps = 3, 24
+    par = Parameters(water_forcefield(mol), mol, terms, precision=dt)
+    rng = np.random.default_rng(9)
+    starts = np.stack([pos + 0.03 * (r % 4) * rng.standard_normal(pos.shape) for r in range(R)], axis=2)
+
+    def run(batch):
+        monkeypatch.setenv("TMDHIP_BATCH_REPLICAS", "1" if batch else "0")
+        s = System(mol.numAtoms, R, dt, dev)
+        s.set_positions(starts)
+        s.set_box(box)
+        torch.manual_seed(5)
+        s.set_velocities(maxwell_boltzmann(par.masses, 300.0, R))
+        f = Forces(par, terms=terms, cutoff=9.0, rfa=True, algorithm="celllist")
+        f.compute(s.pos, s.box, s.forces)
+        torch.manual_seed(6)
+        integ = Integrator(s, f, 1.0, dev, gamma=1.0, T=300.0)
+        integ.step(steps)
+        sts = [f.stats(s.pos, r) for r in range(R)]
+        res = (s.pos.clone(), s.vel.clone(), s.forces.clone(), sts, integ.replays)
+        f.close()
+        return res
+
+    pb, vb, fb, stb, replays = run(True)
+    ps, vs, fs, sts, replays_loop = run(False)
+    assert stb[0]["batched_launches"] > 0 and sts[0]["batched_launches"] == 0
+    assert all(st["overflow"] == 0 for st in stb) and sum(st["n_rebuilds"] for st in stb) > R  # (rebuilds inside the run)
+    assert [st["n_rebuilds"] for st in stb] == [st["n_rebuilds"] for st in sts]
+    assert replays == replays_loop
+    assert torch.isfinite(pb).all()
+    assert torch.equal(pb, ps) and torch.equal(vb, vs) and torch.equal(fb, fs)
+
+
 def test_replicas_rebuilding_together_is_an_opt_in_with_valid_lists(monkeypatch):
     """TMDHIP_REPLICA_REBUILDS=together (opt-in): every replica whose chain is in a batched launch rebuilds as soon as one of them
     has to — builds of several replicas cost what one costs.  The lists are as complete as lists built on time, but their entries

@@ -777,6 +777,44 @@ def test_two_launch_binning_and_its_cell_overflow_fallback(prec, monkeypatch):
     assert abs(e[0]["electrostatics"] - po[0]["electrostatics"]) <= ERTOL[prec] * EFAC * max(1.0, abs(po[0]["electrostatics"]))
 
 
+@pytest.mark.parametrize("prec", ["f32", "f64"])
+def test_the_three_binnings_build_the_same_list(prec, monkeypatch):
+    """A lone rebuild chain bins in one launch (the default at 5 184 atoms / 343 cells), in two (TMDHIP_PREP_SMALL=0) or in four
+    (+ TMDHIP_BIN2=0) — chain_plan.h: choose_binning; the knobs are read at every enqueue.  Each orders the atoms of a cell by
+    original index, so the cell order and with it the lists are the same: one evaluation with a fresh context per binning gives
+    the same pair count and bit-identical forces, energies held like test_two_launch_binning_and_its_cell_overflow_fallback's
+    (bit equality is what the library showed before the chain was planned once, each binning in a process of its own)."""
+    from torchmd_amd.builders import tip3p_box, water_forcefield
+    from torchmd_amd.forces import Forces
+    from torchmd_amd.parameters import Parameters
+
+    dev, dt = _dev(), PREC[prec]
+    mol, pos, box = tip3p_box(12, seed=31)
+    terms = ["lj", "electrostatics"]
+    par = Parameters(water_forcefield(mol), mol, terms + ["bonds", "angles"], precision=dt)
+    pd, bd = pos_tensor(pos, 1, dt, dev), box_tensor(box, 1, dt, dev)
+    settings = {"one": {}, "two": {"TMDHIP_PREP_SMALL": "0"}, "four": {"TMDHIP_PREP_SMALL": "0", "TMDHIP_BIN2": "0"}}
+    out = {}
+    for name, env in settings.items():
+        for var in ("TMDHIP_PREP_SMALL", "TMDHIP_BIN2"):
+            monkeypatch.delenv(var, raising=False)
+        for var, val in env.items():
+            monkeypatch.setenv(var, val)
+        f = Forces(par, terms=terms, cutoff=9.0, rfa=True, algorithm="celllist")
+        F = torch.zeros_like(pd)
+        e = f.compute(pd, bd, F, returnDetails=True)
+        out[name] = (e[0], F.clone().cpu(), f.count_pairs(pd, bd))
+        f.close()
+    assert out["one"][2][0] > 0 and torch.isfinite(out["one"][1]).all()
+    for name in ("two", "four"):
+        assert out[name][2] == out["one"][2], name
+        print(name, prec, "max |dF| vs one launch:", (out[name][1] - out["one"][1]).abs().max().item(),
+              {t: out[name][0][t] - out["one"][0][t] for t in terms})
+        assert torch.equal(out[name][1], out["one"][1]), name
+        for t in terms:  # (fp64 energies are folded with atomics: the order of the terms shows in the last bits)
+            assert abs(out[name][0][t] - out["one"][0][t]) <= (0.0 if prec == "f32" else 1e-12 * abs(out["one"][0][t])), (name, t)
+
+
 def test_streamed_list_reads_are_bit_identical(monkeypatch):
     """Lists that cannot live in the Infinity Cache are read with the non-temporal hint (kLmStream: a run-time choice
     between two load instructions in the lean fp32 kernel; by size, or TMDHIP_LIST_STREAM=0 / 1).  A cache hint must not

@@ -221,114 +221,141 @@ int alloc_replica(tmdhip_ctx *ctx, Replica &rp, int maxn) {
   return 0;
 }
 
+// (Re)plans the replica's grid and buffers for `box` — host-synchronising, taken on the first call and when the box changes.
+// The caller forces a rebuild behind it.  kFallbackAllPairs: the box is too small for cells and the algorithm is AUTO.
+template <typename R>
+static int replan(tmdhip_ctx *ctx, Replica &rp, const R *pos, const double *box, hipStream_t st) {
+  const int n = ctx->d.natoms;
+  double lo[3] = {0, 0, 0}, hi[3] = {0, 0, 0};
+  const bool periodic = !(box[0] == 0 && box[1] == 0 && box[2] == 0);
+  if (!periodic && ctx->open_bounds_valid) {
+    for (int k = 0; k < 3; ++k) lo[k] = ctx->open_lo[k], hi[k] = ctx->open_hi[k];
+    ctx->open_bounds_valid = false;
+  } else if (!periodic) {
+    std::vector<R> h(3 * (size_t)n);
+    TMD_HIP(hipMemcpyAsync(h.data(), pos, sizeof(R) * 3 * n, hipMemcpyDeviceToHost, st));
+    TMD_HIP(hipStreamSynchronize(st));
+    for (int k = 0; k < 3; ++k) lo[k] = 1e300, hi[k] = -1e300;
+    for (int i = 0; i < n; ++i)
+      for (int k = 0; k < 3; ++k) {
+        lo[k] = std::min(lo[k], (double)h[3 * i + k]);
+        hi[k] = std::max(hi[k], (double)h[3 * i + k]);
+      }
+    for (int k = 0; k < 3; ++k) lo[k] -= 1e-3, hi[k] += 1e-3;
+  }
+  const double volume = periodic ? box[0] * box[1] * box[2]
+                                 : std::max(hi[0] - lo[0], ctx->rlist) * std::max(hi[1] - lo[1], ctx->rlist) * std::max(hi[2] - lo[2], ctx->rlist);
+  if (!plan_grid(ctx, box, lo, hi, rp.grid)) {
+    if (ctx->d.algorithm == TMDHIP_ALGO_AUTO) return kFallbackAllPairs;  // caller switches the context over
+    return fail("cell list cannot be used for this box (fewer than 3 cells of cutoff+skin per edge); use TMDHIP_ALGO_ALLPAIRS");
+  }
+  rp.ncell = rp.grid.nc[0] * rp.grid.nc[1] * rp.grid.nc[2];
+  // new list, new extent (the forced rebuild notes every position again)
+  TMD_HIP(hipMemcpyAsync(rp.extent.p, kExtentEmpty, sizeof(kExtentEmpty), hipMemcpyHostToDevice, st));
+  TMD_TRY(rp.count.ensure(sizeof(int) * (size_t)rp.ncell));
+  TMD_TRY(rp.cell_start.ensure(sizeof(int) * ((size_t)rp.ncell + 1)));
+  TMD_HIP(hipMemsetAsync(rp.count.p, 0, sizeof(int) * (size_t)rp.ncell, st));
+  if (const char *e = std::getenv("TMDHIP_BIN2"))  // (A/B, tests: 0 = the four-launch binning; read at every re-plan)
+    if (std::atoi(e) == 0) rp.cell_cap_fallback = true;
+  if (rp.ncell <= kScanPlaceMaxCells && !rp.cell_cap_fallback)  // two-launch binning: the cells' member arrays
+    TMD_TRY(rp.members.ensure(sizeof(int) * (size_t)rp.ncell * kCellCap));
+  if (!rp.have_list) {
+    const double dens = n / volume;
+    int est = (int)(dens * 4.18879 * ctx->rlist * ctx->rlist * ctx->rlist * 1.3) + 32;
+    est = std::min(std::max(est, rp.maxn_keep), std::max(n - 1, 1));
+    TMD_TRY(alloc_replica<R>(ctx, rp, est));
+  }
+  for (int k = 0; k < 3; ++k) rp.box[k] = box[k];
+  rp.pad_rows = plan_pad_rows(ctx, box);
+  return 0;
+}
+
+// A forced build is host-visible: its verdict on the flag words `h`.  done: the list stands, with headroom (density fluctuations) for
+// later device-side rebuilds; else the caller builds again — with the four launches after a cell overflowed the two-launch binning's
+// member array, or in the list geometry re-sized here from the observed maximum.
+template <typename R>
+static int size_forced_build(tmdhip_ctx *ctx, Replica &rp, const int *h, hipStream_t st, bool &done) {
+  done = false;
+  if (h[F_CELLCAP]) {
+    TMD_HIP(hipMemsetAsync(rp.flags.as<int>() + F_CELLCAP, 0, sizeof(int), st));
+    rp.cell_cap_fallback = true;
+    return 0;
+  }
+  int want = (int)(h[F_MAXN] * 1.2) + 8;
+  if (const char *e = std::getenv("TMDHIP_DEBUG_LIST_SLACK")) {
+    // test knob: size the list for the observed maximum + N entries only, so that a later device-side
+    // rebuild overflows and the replay path (tmdhip_md_restore) gets exercised
+    want = h[F_MAXN] + std::max(std::atoi(e), 0);
+    const int tight = (want + 4 * rp.lg.lpa - 1) / (4 * rp.lg.lpa) * (4 * rp.lg.lpa);
+    if (!rp.have_list && h[F_MAXN] <= rp.lg.maxn && rp.lg.maxn > tight) return alloc_replica<R>(ctx, rp, tight);  // rebuild in the tighter geometry
+  }
+  done = h[F_MAXN] <= rp.lg.maxn && (rp.have_list || want <= rp.lg.maxn);
+  rp.have_list = true;
+  return done ? 0 : alloc_replica<R>(ctx, rp, std::max(want, rp.lg.maxn));
+}
+
+// list duties of the pair launch's first thread (kLm*), after the step's list bookkeeping: rp.step counts the NEXT step by now
+static int list_mode(const tmdhip_ctx *ctx, const Replica &rp, int flags) {
+  return ((flags & kViolationCheck) ? kLmViolation : 0) | (((rp.step - 1) & 1) ? kLmParity : 0) | (rp.pad_rows ? kLmPadded : 0) |
+         (list_streams(ctx, rp) ? kLmStream : 0);
+}
+
+// every `timing_stride`-th launch is bracketed by events: an event pair costs ~3 us of stream time,
+// so timing every launch would slow down the very loop being measured
+static int timing_events(tmdhip_ctx *ctx, int flags, hipEvent_t &e0, hipEvent_t &e1) {
+  const bool timeable = ctx->timing && !(ctx->timing_interior_only && (flags & TMDHIP_WANT_ENERGY));
+  const int64_t seen = timeable ? ctx->timing_seen++ : -1;
+  const bool timed = timeable && seen >= 0 && (seen % ctx->timing_stride) == 0 &&
+                     (ctx->timing_limit == 0 || ctx->timing_taken < ctx->timing_limit);
+  if (!timed) return 0;
+  ctx->timing_taken++;
+  if (ctx->events_used >= 4096) TMD_TRY(tmdhip_timing_read(ctx, nullptr, nullptr, 0));
+  if (ctx->events_used == ctx->events.size()) {
+    hipEvent_t a, b;
+    TMD_HIP(hipEventCreateWithFlags(&a, kTimingEventFlags));
+    TMD_HIP(hipEventCreateWithFlags(&b, kTimingEventFlags));
+    ctx->events.emplace_back(a, b);
+  }
+  e0 = ctx->events[ctx->events_used].first, e1 = ctx->events[ctx->events_used].second;
+  ctx->events_used++;
+  return 0;
+}
+
 template <typename R>
 int compute_list(tmdhip_ctx *ctx, Replica &rp, const void *pos_v, const double *box, void *forces,
                  double *energies, int flags, hipStream_t st, const FusedLaunchT<R> *fused, ListOnlyOut *list_only) {
-  const int n = ctx->d.natoms;
   const R *pos = (const R *)pos_v;
   const PairConsts<R> c = make_consts<R>(ctx, box);
-  const bool box_changed = box[0] != rp.box[0] || box[1] != rp.box[1] || box[2] != rp.box[2];
   int force = 0;
-  if (!rp.have_list || box_changed) {
-    // (re)plan the grid — host-synchronising path, taken on the first call and when the box changes
-    double lo[3] = {0, 0, 0}, hi[3] = {0, 0, 0};
-    const bool periodic = !(box[0] == 0 && box[1] == 0 && box[2] == 0);
-    double volume;
-    if (!periodic && ctx->open_bounds_valid) {
-      for (int k = 0; k < 3; ++k) lo[k] = ctx->open_lo[k], hi[k] = ctx->open_hi[k];
-      ctx->open_bounds_valid = false;
-      volume = std::max(hi[0] - lo[0], ctx->rlist) * std::max(hi[1] - lo[1], ctx->rlist) *
-               std::max(hi[2] - lo[2], ctx->rlist);
-    } else if (!periodic) {
-      std::vector<R> h(3 * (size_t)n);
-      TMD_HIP(hipMemcpyAsync(h.data(), pos, sizeof(R) * 3 * n, hipMemcpyDeviceToHost, st));
-      TMD_HIP(hipStreamSynchronize(st));
-      for (int k = 0; k < 3; ++k) lo[k] = 1e300, hi[k] = -1e300;
-      for (int i = 0; i < n; ++i)
-        for (int k = 0; k < 3; ++k) {
-          lo[k] = std::min(lo[k], (double)h[3 * i + k]);
-          hi[k] = std::max(hi[k], (double)h[3 * i + k]);
-        }
-      for (int k = 0; k < 3; ++k) lo[k] -= 1e-3, hi[k] += 1e-3;
-      volume = std::max(hi[0] - lo[0], ctx->rlist) * std::max(hi[1] - lo[1], ctx->rlist) *
-               std::max(hi[2] - lo[2], ctx->rlist);
-    } else {
-      volume = box[0] * box[1] * box[2];
-    }
-    if (!plan_grid(ctx, box, lo, hi, rp.grid)) {
-      if (ctx->d.algorithm == TMDHIP_ALGO_AUTO) return kFallbackAllPairs;  // caller switches the context over
-      return fail("cell list cannot be used for this box (fewer than 3 cells of cutoff+skin per edge); use "
-                  "TMDHIP_ALGO_ALLPAIRS");
-    }
-    rp.ncell = rp.grid.nc[0] * rp.grid.nc[1] * rp.grid.nc[2];
-    // new list, new extent (the forced rebuild below notes every position again)
-    TMD_HIP(hipMemcpyAsync(rp.extent.p, kExtentEmpty, sizeof(kExtentEmpty), hipMemcpyHostToDevice, st));
-    TMD_TRY(rp.count.ensure(sizeof(int) * (size_t)rp.ncell));
-    TMD_TRY(rp.cell_start.ensure(sizeof(int) * ((size_t)rp.ncell + 1)));
-    TMD_HIP(hipMemsetAsync(rp.count.p, 0, sizeof(int) * (size_t)rp.ncell, st));
-    if (const char *e = std::getenv("TMDHIP_BIN2"))  // (A/B, tests: 0 = the four-launch binning; read at every re-plan)
-      if (std::atoi(e) == 0) rp.cell_cap_fallback = true;
-    if (rp.ncell <= kScanPlaceMaxCells && !rp.cell_cap_fallback)  // two-launch binning: the cells' member arrays
-      TMD_TRY(rp.members.ensure(sizeof(int) * (size_t)rp.ncell * kCellCap));
-    if (!rp.have_list) {
-      const double dens = n / volume;
-      int est = (int)(dens * 4.18879 * ctx->rlist * ctx->rlist * ctx->rlist * 1.3) + 32;
-      est = std::max(est, rp.maxn_keep);
-      est = std::min(est, std::max(n - 1, 1));
-      TMD_TRY(alloc_replica<R>(ctx, rp, est));
-    }
-    for (int k = 0; k < 3; ++k) rp.box[k] = box[k];
-    rp.pad_rows = plan_pad_rows(ctx, box);
+  if (!rp.have_list || box[0] != rp.box[0] || box[1] != rp.box[1] || box[2] != rp.box[2]) {
+    if (const int rc = replan<R>(ctx, rp, pos, box, st)) return rc;  // (kFallbackAllPairs too: no message)
     force = 1;
   }
   for (int attempt = 0; attempt < 8; ++attempt) {
     if (!force && (flags & kSkipChain)) {  // (the integrator kernel has run this step's test with `skipped` set)
-      rp.step++;
-      rp.chains_skipped++;
+      rp.step++, rp.chains_skipped++;
       break;
     }
     if (!force && (flags & kDeferChain) && (flags & kPrechecked) && list_only) {  // (the caller enqueues the chain, with other replicas')
-      list_only->chain = 1;
-      list_only->chain_parity = (int)(rp.step & 1);
+      list_only->chain = 1, list_only->chain_parity = (int)(rp.step & 1);
       rp.step++;
       break;
     }
     TMD_TRY(enqueue_list_update<R>(ctx, rp, pos, c, force, st, !force && (flags & kPrechecked), (flags & kSpecChain) != 0));
     rp.step++;
     if (!force) break;
-    // forced builds are host-visible: size the list from the observed maximum so that later
-    // device-side rebuilds have headroom (density fluctuations) without host involvement
     int h[F_COUNT];
     TMD_HIP(hipMemcpyAsync(h, rp.flags.p, sizeof(h), hipMemcpyDeviceToHost, st));
     TMD_HIP(hipStreamSynchronize(st));
     rp.host_rebuilds++;
-    if (h[F_CELLCAP]) {  // a cell overflowed the member array of the two-launch binning: build again with the four launches
-      TMD_HIP(hipMemsetAsync(rp.flags.as<int>() + F_CELLCAP, 0, sizeof(int), st));
-      rp.cell_cap_fallback = true;
-      continue;
-    }
-    int want = (int)(h[F_MAXN] * 1.2) + 8;
-    if (const char *e = std::getenv("TMDHIP_DEBUG_LIST_SLACK")) {
-      // test knob: size the list for the observed maximum + N entries only, so that a later device-side
-      // rebuild overflows and the replay path (tmdhip_md_restore) gets exercised
-      want = h[F_MAXN] + std::max(std::atoi(e), 0);
-      const int tight = (want + 4 * rp.lg.lpa - 1) / (4 * rp.lg.lpa) * (4 * rp.lg.lpa);
-      if (!rp.have_list && h[F_MAXN] <= rp.lg.maxn && rp.lg.maxn > tight) {
-        TMD_TRY(alloc_replica<R>(ctx, rp, tight));
-        continue;  // rebuild in the tighter geometry
-      }
-    }
-    if (h[F_MAXN] <= rp.lg.maxn && (rp.have_list || want <= rp.lg.maxn)) {
-      rp.have_list = true;
-      break;
-    }
-    rp.have_list = true;
-    TMD_TRY(alloc_replica<R>(ctx, rp, std::max(want, rp.lg.maxn)));
+    bool done;
+    TMD_TRY(size_forced_build<R>(ctx, rp, h, st, done));
+    if (done) break;
   }
-  if (flags & kListOnly) {  // the caller launches (md_run's replica batch): rp.step counts the NEXT step by now
+  const int lmode = list_mode(ctx, rp, flags);
+  if (flags & kListOnly) {  // the caller launches (md_run's replica batch)
     if (!list_only) return fail("compute_list: kListOnly without an output block");
-    list_only->lmode = ((flags & kViolationCheck) ? kLmViolation : 0) | (((rp.step - 1) & 1) ? kLmParity : 0) |
-                       (rp.pad_rows ? kLmPadded : 0) | (list_streams(ctx, rp) ? kLmStream : 0);
+    list_only->lmode = lmode;
     list_only->next_parity = (int)(rp.step & 1);
     return 0;
   }
@@ -339,29 +366,8 @@ int compute_list(tmdhip_ctx *ctx, Replica &rp, const void *pos_v, const double *
     TMD_HIP(hipMemsetAsync(pc, 0, sizeof(unsigned long long), st));
   }
   hipEvent_t e0 = nullptr, e1 = nullptr;
-  // every `timing_stride`-th launch is bracketed by events: an event pair costs ~3 us of stream time,
-  // so timing every launch would slow down the very loop being measured
-  const bool timeable = ctx->timing && !(ctx->timing_interior_only && (flags & TMDHIP_WANT_ENERGY));
-  const int64_t seen = timeable ? ctx->timing_seen++ : -1;
-  const bool timed = timeable && seen >= 0 && (seen % ctx->timing_stride) == 0 &&
-                     (ctx->timing_limit == 0 || ctx->timing_taken < ctx->timing_limit);
-  if (timed) ctx->timing_taken++;
-  if (timed) {
-    if (ctx->events_used >= 4096) TMD_TRY(tmdhip_timing_read(ctx, nullptr, nullptr, 0));
-    if (ctx->events_used == ctx->events.size()) {
-      hipEvent_t a, b;
-      TMD_HIP(hipEventCreateWithFlags(&a, kTimingEventFlags));
-      TMD_HIP(hipEventCreateWithFlags(&b, kTimingEventFlags));
-      ctx->events.emplace_back(a, b);
-    }
-    e0 = ctx->events[ctx->events_used].first;
-    e1 = ctx->events[ctx->events_used].second;
-    ctx->events_used++;
-  }
+  TMD_TRY(timing_events(ctx, flags, e0, e1));
   const int overwrite = (flags & TMDHIP_OVERWRITE_FORCES) ? 1 : 0;
-  // list duties of the pair launch's first thread: rp.step counts the NEXT step by now
-  const int lmode = ((flags & kViolationCheck) ? kLmViolation : 0) | (((rp.step - 1) & 1) ? kLmParity : 0) |
-                    (rp.pad_rows ? kLmPadded : 0) | (list_streams(ctx, rp) ? kLmStream : 0);
   FusedLaunchT<R> fl{};
   if (fused) {
     fl = *fused;

@@ -46,6 +46,7 @@
 #include "pair_math.h"
 #include "bonded_math.h"
 #include "pacing.h"
+#include "chain_plan.h"
 #include "rng.h"
 
 namespace tmd {
@@ -104,7 +105,6 @@ enum { F_REBUILD0 = 0, F_REBUILD1 = 1, F_MAXN = 2, F_NREBUILD = 3, F_VIOLATION =
 // guarantees, the pair kernel applies the exact cutoff in the context's precision.
 constexpr double kBuildMarginF64 = 2.0e-4;
 constexpr int kCellCap = 64;             // members per cell of the two-launch binning
-constexpr int kScanPlaceMaxCells = 12288;  // cells whose prefix a block of scan_place_kernel can hold in LDS (48 KB)
 
 // Displacement test that drives the rebuilds: the list (cutoff + skin) is valid while no atom has moved
 // further than skin/2 from `ref`; the test runs on the device (in the fused integrator kernel, or in

@@ -299,9 +299,7 @@ __global__ void place_sorted_kernel(int n, PlaceArgs<R> P, const int *flag) {
 // bin_count / scan_cells / fill_cells / place_sorted.  On the ~10 of 11 steps without a rebuild the chain then costs
 // two early-exit launches instead of five (~1.7 us each).  A rebuild on one CU is slower than the four parallel
 // launches, which sets the size limit — measured, water boxes, us per MD step without / with: 5 184 atoms 27.2 / 23.8,
-// 12 288 atoms 34.6 / 36.1, 41 472 atoms 41.8 / 67.1.
-constexpr int kPrepSmallMaxCells = 4096;
-constexpr int kPrepSmallMaxAtoms = 8192;
+// 12 288 atoms 34.6 / 36.1, 41 472 atoms 41.8 / 67.1 (kPrepSmallMaxCells / kPrepSmallMaxAtoms, chain_plan.h).
 template <typename R>
 __device__ __forceinline__ void prep_small_body(int n, const R *__restrict__ pos, const Grid &g, int ncell, int *cell_of,
                                                 int *__restrict__ slot, int *cell_start, int *order_tmp, const PlaceArgs<R> &P,
@@ -894,7 +892,7 @@ unsigned long long *debug_timeline_buffer(int blocks) {
 // The replicas of a cell-list context rebuild on their own steps, each behind its own flag; enqueued one after the other, R
 // chains are 2-3 R launches on every step on which somebody is near a limit, and a small box's rebuild runs on a fraction of
 // the chip while the others wait.  Here blockIdx.y picks the replica: its arguments come from a device table (ChainRepT: what
-// enqueue_chain would have passed by value, uploaded when an entry changes), what alternates from step to step — positions,
+// launch_chain would have passed by value, uploaded when an entry changes), what alternates from step to step — positions,
 // flag word, target copy — as a kernel argument (ChainSelT).  Same bodies, same per-replica results.
 template <typename R>
 struct ChainRepT {
@@ -910,7 +908,7 @@ struct ChainRepT {
   int *count_zero;
   float rlist2, rcut;
   int ncell, nactive, type_in_entry, split, build_blocks;
-  int mode;  // 0: prep_small + build, 1: bin_members + scan_place + build
+  Binning mode;  // (chain_plan.h; rows of a batched launch: OneLaunch or TwoLaunch)
   int wskin, lpas3;
 };
 template <typename R>
@@ -979,12 +977,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(7, 8))) void
                                          A.count_zero);
 }
 
-// the buffers a rebuild chain reads and writes (the replica's own)
-struct ListTarget {
-  DevBuf *cell_of, *slot, *order_tmp, *count, *cell_start, *order, *inv, *stype, *ref, *sorted_hs, *hs2_dyn, *nlist, *nneigh, *sorted, *members;
-};
-
-// The rebuild chain: cell binning (one launch for small systems, two or four otherwise) and the list build, all on `st`.
+// The rebuild chain: cell binning (one launch for small systems, two or four otherwise) and the list build, all on one stream.
 // Every kernel returns at once unless *flag != 0.
 // INVARIANT: build_list_kernel is never launched without the placement kernels of the SAME chain in front of it — it reads
 // the atoms through bsorted / binfo, which only they write (wrapped positions and half skins of THIS build); a path that
@@ -994,268 +987,202 @@ struct ListTarget {
 // the LJ class above it.
 static_assert(kInfoIndexMask == (1 << kEntryTypeShift) - 1, "binfo: original index below the LJ class field");
 static_assert((kEntryOffMask >> 4) == (1u << 23) - 1u, "list entries carry 23-bit slots: seg_start packs a start < 2^23 below its image code (bit 24 up)");
-// `plan`: fill the replica's entry of the batched chain's table instead of launching (enqueue_chain_batch)
+
+// The plan's binning and build cut (chain_plan.h), as a row of the batched chain or as a lone chain.  Whether the build clears
+// the cell counts follows from the binning alone: a disagreement would leave stale counts under the next two-launch binning.
 template <typename R>
-static int enqueue_chain(tmdhip_ctx *ctx, Replica &rp, const R *pos, const PairConsts<R> &c, const int *flag, hipStream_t st,
-                         ChainRepT<R> *plan = nullptr) {
-  const ListTarget T = {&rp.cell_of, &rp.slot, &rp.order_tmp, &rp.count, &rp.cell_start, &rp.order, &rp.inv, &rp.stype, &rp.ref,
-                        &rp.sorted_hs, &rp.hs2_dyn, &rp.nlist, &rp.nneigh, &rp.sorted, &rp.members};
-  const hipStream_t st_build = st;
+static void choose_chain(ChainRepT<R> &A, const Replica &rp, int n, const ChainKnobs &knobs, bool batched) {
+  A.mode = choose_binning(n, rp.ncell, rp.cell_cap_fallback, rp.members.bytes >= sizeof(int) * (size_t)rp.ncell * kCellCap, knobs, batched);
+  const BuildCut cut = choose_build(rp.ncell, knobs, batched);
+  A.split = cut.split, A.build_blocks = cut.blocks;
+  A.count_zero = clears_counts(A.mode) ? A.count : nullptr;
+}
+
+// Plans one replica's chain into A: every argument of its kernels except what alternates from step to step (positions, target
+// copy, flag word — launch_chain's arguments, ChainSelT in a batch).  The only place that assembles them; launches nothing.
+template <typename R>
+static void plan_chain(tmdhip_ctx *ctx, Replica &rp, const PairConsts<R> &c, const ChainKnobs &knobs, bool batched, ChainRepT<R> &A) {
   using R4 = typename Vec<R>::T4;
   const int n = ctx->d.natoms;
-  int *flags = rp.flags.as<int>();
-  const int nb = (n + 255) / 256;
-  PlaceArgs<R> P;
-  std::memset(&P, 0, sizeof(P));  // (padding bytes too: the batched chain compares table entries with memcmp)
-  P.cell_of = T.cell_of->as<int>();
-  P.cell_start = T.cell_start->as<int>();
-  P.order_tmp = T.order_tmp->as<int>();
-  P.pos = pos;
-  P.qs = ctx->qs.as<R>();
-  P.types = ctx->types.as<int>();
-  P.order = T.order->as<int>();
-  P.inv = T.inv->as<int>();
-  P.sorted = T.sorted->as<R4>();
-  P.stype = T.stype->as<int>();
-  P.ref = T.ref->as<R>();
-  P.half_skin = ctx->half_skin.as<R>();
-  P.sorted_hs = T.sorted_hs->as<R>();
+  std::memset(&A, 0, sizeof(A));  // (padding bytes too: the batched chain compares table entries with memcmp)
+  PlaceArgs<R> &P = A.P;  // (pos and sorted stay null: per launch)
+  A.g = rp.grid, A.lg = rp.lg, A.ncell = rp.ncell, A.nactive = ctx->nactive;
+  A.cell_of = rp.cell_of.as<int>(), A.slot = rp.slot.as<int>(), A.cell_start = rp.cell_start.as<int>(), A.order_tmp = rp.order_tmp.as<int>();
+  A.count = rp.count.as<int>(), A.members = rp.members.as<int>(), A.flags = rp.flags.as<int>();
+  A.nlist = rp.nlist.as<unsigned>(), A.nneigh = rp.nneigh.as<int>();
+  A.bsorted = P.bsorted = rp.bsorted.as<float4>(), A.binfo = P.binfo = rp.binfo.as<int>();
+  A.type_in_entry = P.type_in_entry = ctx->d.ntypes <= kEntryTypes;
+  A.wskin = ctx->half_skin.p != nullptr, A.lpas3 = rp.lg.lpa_shift == 3;
+  P.cell_of = A.cell_of, P.cell_start = A.cell_start, P.order_tmp = A.order_tmp;
+  P.qs = ctx->qs.as<R>(), P.types = ctx->types.as<int>();
+  P.order = rp.order.as<int>(), P.inv = rp.inv.as<int>(), P.stype = rp.stype.as<int>(), P.ref = rp.ref.as<R>(), P.ext = rp.extent.as<int>();
+  P.half_skin = ctx->half_skin.as<R>(), P.sorted_hs = rp.sorted_hs.as<R>(), P.hs2_dyn = rp.hs2_dyn.as<R>();
   P.vel = ctx->vskin_time > 0 ? (const R *)rp.skin_vel : nullptr;
-  P.vs_floor = (R)ctx->vskin_floor;
-  P.vs_time = (R)ctx->vskin_time;
-  P.vs_cap = (R)ctx->vskin_cap_len;
-  P.hs2_dyn = T.hs2_dyn->as<R>();
-  P.ext = rp.extent.as<int>();
-  P.bsorted = rp.bsorted.as<float4>();
-  P.binfo = rp.binfo.as<int>();
+  P.vs_floor = (R)ctx->vskin_floor, P.vs_time = (R)ctx->vskin_time, P.vs_cap = (R)ctx->vskin_cap_len;
+  if (rp.pad_rows) {  // both copies get the dummy records, in address order: the row does not change when the copies swap
+    R4 *a = rp.sorted.as<R4>() + n, *b = rp.sorted_alt.p ? rp.sorted_alt.as<R4>() + n : nullptr;
+    P.dummy_a = (b && b < a) ? b : a, P.dummy_b = (b && b < a) ? a : b;
+  }
   // the build's own constants: fp32 in either precision, every pair radius widened by kBuildMarginF64 in fp64 contexts
   const double bmargin = std::is_same<R, double>::value ? kBuildMarginF64 : 0.0;
-  PairConsts<float> cb;
-  std::memset(&cb, 0, sizeof(cb));
+  const float rlb = (float)(ctx->rlist + bmargin);
+  A.rlist2 = rlb * rlb, A.rcut = (float)(ctx->d.cutoff + bmargin);
   for (int k = 0; k < 3; ++k) {
-    cb.box[k] = (float)c.box[k];
-    cb.invbox[k] = (float)c.invbox[k];
-  }
-  const float rlb = (float)(ctx->rlist + bmargin), rcb = (float)(ctx->d.cutoff + bmargin);
-  for (int k = 0; k < 3; ++k) {
-    P.box[k] = c.box[k];
-    P.invbox[k] = c.invbox[k];
-  }
-  P.type_in_entry = ctx->d.ntypes <= kEntryTypes;
-  P.dummy_a = P.dummy_b = nullptr;
-  if (rp.pad_rows) {
-    P.dummy_a = T.sorted->as<R4>() + n;
-    if (rp.sorted_alt.p) P.dummy_b = rp.sorted_alt.as<R4>() + n;
-    for (int k = 0; k < 3; ++k) {  // (pad_dummy_positions' values)
+    P.box[k] = c.box[k], P.invbox[k] = c.invbox[k];
+    A.c.box[k] = (float)c.box[k], A.c.invbox[k] = (float)c.invbox[k];
+    if (rp.pad_rows) {  // (pad_dummy_positions' values)
       const bool open = !(c.box[k] > R(0));
       P.dummy_pos[0][k] = open ? R(1.0e6) : R(0.25) * c.box[k];
       P.dummy_pos[1][k] = open ? R(1.0e6) : R(0.75) * c.box[k];
     }
   }
-  static const bool prep_small_on = !(std::getenv("TMDHIP_PREP_SMALL") && std::atoi(std::getenv("TMDHIP_PREP_SMALL")) == 0);
-  const bool bin2 = !rp.cell_cap_fallback && rp.ncell <= kScanPlaceMaxCells &&
-                    T.members->bytes >= sizeof(int) * (size_t)rp.ncell * kCellCap;
-  const bool prep_small = prep_small_on && n <= kPrepSmallMaxAtoms && rp.ncell <= kPrepSmallMaxCells;
-  if (plan) {
-    // (the batched kernels run the one-launch and the two-launch binning; a replica on the four launches, or with more cells
-    // than one block per cell covers, keeps a chain of its own: mode -1)
-    constexpr int kMaxBlocks = 16384;
-    // (blocks per cell as for a lone replica.  Cutting small grids finer because the chip idles behind a batched chain was
-    // measured and is slower — 12 288 atoms x 8 / 5 184 atoms x 16, us per step at 2 / 4 / 8 blocks per cell: 92.7 / 97.7 /
-    // 105.8 and 98.5 / 99.9 / 110.2, profiles/r06_replica_batch.txt; TMDHIP_BATCH_BUILD_SPLIT overrides)
-    int split = 1;
-    if (const char *e = std::getenv("TMDHIP_BUILD_SPLIT")) split = std::max(1, std::min(std::atoi(e), 8));
-    else if (const char *e2 = std::getenv("TMDHIP_BATCH_BUILD_SPLIT")) split = std::max(1, std::min(std::atoi(e2), 8));
-    else if (rp.ncell <= 1100) split = 2;
-    if (rp.ncell * split > kMaxBlocks) split = 1;
-    std::memset(plan, 0, sizeof(*plan));
-    // (the one-block binning of small systems is a saving of launches for a lone replica — it takes 44 us on its one CU at 5 184
-    // atoms; a batch shares its launches among the replicas and bins in parallel: two-launch binning wherever it applies)
-    static const bool batch_prep_small = std::getenv("TMDHIP_BATCH_PREP_SMALL") && std::atoi(std::getenv("TMDHIP_BATCH_PREP_SMALL")) != 0;
-    plan->mode = (rp.ncell > kMaxBlocks) ? -1 : (bin2 && !(prep_small && batch_prep_small)) ? 1 : prep_small ? 0 : -1;
-    plan->g = rp.grid;
-    plan->P = P;
-    plan->P.pos = nullptr;     // (per launch: ChainSelT)
-    plan->P.sorted = nullptr;
-    if (rp.pad_rows) {         // both copies get the dummy records, whichever is current
-      R4 *a = rp.sorted.as<R4>() + n, *b = rp.sorted_alt.p ? rp.sorted_alt.as<R4>() + n : nullptr;
-      plan->P.dummy_a = (b && b < a) ? b : a;
-      plan->P.dummy_b = (b && b < a) ? a : b;
-    }
-    plan->c = cb;
-    plan->lg = rp.lg;
-    plan->cell_of = T.cell_of->as<int>();
-    plan->count = T.count->as<int>();
-    plan->members = T.members->as<int>();
-    plan->flags = flags;
-    plan->slot = T.slot->as<int>();
-    plan->cell_start = T.cell_start->as<int>();
-    plan->order_tmp = T.order_tmp->as<int>();
-    plan->bsorted = rp.bsorted.as<float4>();
-    plan->binfo = rp.binfo.as<int>();
-    plan->nlist = T.nlist->as<unsigned>();
-    plan->nneigh = T.nneigh->as<int>();
-    plan->count_zero = plan->mode == 1 ? T.count->as<int>() : nullptr;
-    plan->rlist2 = rlb * rlb;
-    plan->rcut = rcb;
-    plan->ncell = rp.ncell;
-    plan->nactive = ctx->nactive;
-    plan->type_in_entry = ctx->d.ntypes <= kEntryTypes;
-    plan->split = split;
-    plan->build_blocks = rp.ncell * split;
-    plan->wskin = ctx->half_skin.p != nullptr;
-    plan->lpas3 = rp.lg.lpa_shift == 3;
-    return 0;
-  }
-  if (prep_small) {
-    hipLaunchKernelGGL((prep_small_kernel<R>), dim3(1), dim3(1024), 0, st, n, pos, rp.grid, rp.ncell, T.cell_of->as<int>(),
-                       T.slot->as<int>(), T.cell_start->as<int>(), T.order_tmp->as<int>(), P, flag);
-  } else if (bin2) {
-    hipLaunchKernelGGL((bin_members_kernel<R>), dim3(nb), dim3(256), 0, st, n, pos, rp.grid, T.cell_of->as<int>(), T.count->as<int>(),
-                       T.members->as<int>(), flags, flag);
-    hipLaunchKernelGGL((scan_place_kernel<R>), dim3(nb), dim3(256), sizeof(int) * ((size_t)rp.ncell + 1), st, n, rp.ncell,
-                       T.count->as<int>(), T.members->as<int>(), T.cell_start->as<int>(), P, flag);
+  choose_chain(A, rp, n, knobs, batched);
+}
+
+// The build kernel's variant — per-atom skins, eight lanes per atom or the generic row layout — as two constants for f.
+template <typename F>
+static void with_build_variant(bool wskin, bool lpas3, F &&f) {
+  const auto with_lanes = [&](auto W) { lpas3 ? f(W, std::integral_constant<int, 3>{}) : f(W, std::integral_constant<int, -1>{}); };
+  wskin ? with_lanes(std::true_type{}) : with_lanes(std::false_type{});
+}
+
+// Launches a lone chain from its plan (choose_chain(.., batched = false)) on `st`, behind *flag.
+template <typename R>
+static int launch_chain(tmdhip_ctx *ctx, const ChainRepT<R> &A, const R *pos, typename Vec<R>::T4 *sorted, const int *flag, hipStream_t st) {
+  const int n = ctx->d.natoms, nb = (n + 255) / 256;
+  PlaceArgs<R> P = A.P;
+  P.pos = pos, P.sorted = sorted;
+  if (P.dummy_b == sorted + n) std::swap(P.dummy_a, P.dummy_b);  // (a lone chain names the target copy first)
+  if (A.mode == Binning::OneLaunch) {
+    hipLaunchKernelGGL((prep_small_kernel<R>), dim3(1), dim3(1024), 0, st, n, pos, A.g, A.ncell, A.cell_of, A.slot, A.cell_start, A.order_tmp, P, flag);
+  } else if (A.mode == Binning::TwoLaunch) {
+    hipLaunchKernelGGL((bin_members_kernel<R>), dim3(nb), dim3(256), 0, st, n, pos, A.g, A.cell_of, A.count, A.members, A.flags, flag);
+    hipLaunchKernelGGL((scan_place_kernel<R>), dim3(nb), dim3(256), sizeof(int) * ((size_t)A.ncell + 1), st, n, A.ncell, A.count, A.members,
+                       A.cell_start, P, flag);
   } else {
-    hipLaunchKernelGGL((bin_count_kernel<R>), dim3(nb), dim3(256), 0, st, n, pos, rp.grid, T.cell_of->as<int>(),
-                       T.slot->as<int>(), T.count->as<int>(), flag);
-    hipLaunchKernelGGL(scan_cells_kernel, dim3(1), dim3(1024), 0, st, rp.ncell, T.count->as<int>(),
-                       T.cell_start->as<int>(), flag);
-    hipLaunchKernelGGL(fill_cells_kernel, dim3(nb), dim3(256), 0, st, n, T.cell_of->as<int>(), T.slot->as<int>(),
-                       T.cell_start->as<int>(), T.order_tmp->as<int>(), flag);
+    hipLaunchKernelGGL((bin_count_kernel<R>), dim3(nb), dim3(256), 0, st, n, pos, A.g, A.cell_of, A.slot, A.count, flag);
+    hipLaunchKernelGGL(scan_cells_kernel, dim3(1), dim3(1024), 0, st, A.ncell, A.count, A.cell_start, flag);
+    hipLaunchKernelGGL(fill_cells_kernel, dim3(nb), dim3(256), 0, st, n, A.cell_of, A.slot, A.cell_start, A.order_tmp, flag);
     hipLaunchKernelGGL((place_sorted_kernel<R>), dim3(nb), dim3(256), 0, st, n, P, flag);
   }
-  constexpr int kMaxBuildBlocks = 16384;
-  const bool wskin = ctx->half_skin.p != nullptr;
-  // few cells: several blocks per cell (see build_list_kernel), so that ~2 000 waves are in flight
-  int split = 1;
-  if (const char *e = std::getenv("TMDHIP_BUILD_SPLIT")) split = std::max(1, std::min(std::atoi(e), 8));
-  else if (rp.ncell <= 1100) split = 2;  // measured (water boxes of 5 184 / 12 288 / 41 472 atoms = 343 / 729 / 2 197 cells, us per
-                                         // MD step at split 1, 2, 4): 29.7 27.7 (28-37) / 37.8 35.5 35.0 / 43.0 44.6 48.3
-  if (rp.ncell > kMaxBuildBlocks) split = 1;
-  auto launch_build = [&](auto kernel, int blocks) {
-    hipLaunchKernelGGL(kernel, dim3(blocks), dim3(64), 0, st_build, n, rp.bsorted.as<float4>(), rp.binfo.as<int>(),
-                       T.cell_start->as<int>(), rp.grid, cb, rlb * rlb,
-                       rcb, ctx->excl_off.as<int>(), ctx->excl_idx.as<int>(), rp.lg, T.nlist->as<unsigned>(),
-                       T.nneigh->as<int>(), flags + F_MAXN, flag, rp.ncell, ctx->nactive, ctx->d.ntypes <= kEntryTypes,
-                       debug_timeline_buffer(blocks), split,
-                       (bin2 && !(prep_small_on && n <= kPrepSmallMaxAtoms && rp.ncell <= kPrepSmallMaxCells)) ? T.count->as<int>() : nullptr);
+  auto launch_build = [&](auto kernel) {
+    hipLaunchKernelGGL(kernel, dim3(A.build_blocks), dim3(64), 0, st, n, A.bsorted, A.binfo, A.cell_start, A.g, A.c, A.rlist2, A.rcut,
+                       ctx->excl_off.as<int>(), ctx->excl_idx.as<int>(), A.lg, A.nlist, A.nneigh, A.flags + F_MAXN, flag, A.ncell, A.nactive,
+                       A.type_in_entry, debug_timeline_buffer(A.build_blocks), A.split, A.count_zero);
   };
-#define TMD_BUILD(LOOPED, BLOCKS)                                                                   \
-  if (rp.lg.lpa_shift == 3) {                                                                      \
-    if (wskin) launch_build(build_list_kernel<float, LOOPED, true, 3>, BLOCKS);                    \
-    else launch_build(build_list_kernel<float, LOOPED, false, 3>, BLOCKS);                         \
-  } else {                                                                                         \
-    if (wskin) launch_build(build_list_kernel<float, LOOPED, true, -1>, BLOCKS);                   \
-    else launch_build(build_list_kernel<float, LOOPED, false, -1>, BLOCKS);                        \
-  }
-  if (rp.ncell <= kMaxBuildBlocks) {
-    TMD_BUILD(false, rp.ncell * split)
-  } else {
-    TMD_BUILD(true, kMaxBuildBlocks)
-  }
-#undef TMD_BUILD
+  with_build_variant(A.wskin, A.lpas3, [&](auto W, auto L) {
+    if (A.build_blocks < A.ncell) launch_build(build_list_kernel<float, true, decltype(W)::value, decltype(L)::value>);  // (BuildCut::looped)
+    else launch_build(build_list_kernel<float, false, decltype(W)::value, decltype(L)::value>);
+  });
   TMD_HIP(hipGetLastError());
   return 0;
 }
-
 
 template <typename R>
 __global__ void chain_upload_kernel(ChainRepT<R> v, ChainRepT<R> *dst) {
   if (threadIdx.x == 0 && blockIdx.x == 0) *dst = v;
 }
 
-// The rebuild chains of the replicas reps[0 .. nsel) in one launch per kernel (see ChainRepT).  pos[k] / parity[k] / box[k]: what
-// enqueue_list_update would have been given for replica reps[k] (its displacement test has run already).  Replicas the batched
-// kernels do not cover (four-launch binning, more than 16 384 cells) or that differ in kernel variant get chains of their own.
+// Brings the device table's rows of reps[0 .. nsel) up to date with their plans: a row is uploaded when its bytes change.
 template <typename R>
-int enqueue_chain_batch(tmdhip_ctx *ctx, int nsel, const int *reps, const R *const *pos, const int *parity, const double *const *box,
-                        hipStream_t st) {
-  using R4 = typename Vec<R>::T4;
-  const int n = ctx->d.natoms, nrep = (int)ctx->rep.size();
-  std::vector<ChainRepT<R>> plan(nsel);
-  std::vector<PairConsts<R>> cs(nsel);
-  bool uniform = nsel > 1;
-  for (int k = 0; k < nsel; ++k) {
-    Replica &rp = ctx->rep[reps[k]];
-    cs[k] = make_consts<R>(ctx, box[k]);
-    TMD_TRY(enqueue_chain<R>(ctx, rp, pos[k], cs[k], rp.flags.as<int>() + F_REBUILD0 + parity[k], st, &plan[k]));
-    uniform = uniform && plan[k].mode >= 0 && plan[k].mode == plan[0].mode && plan[k].wskin == plan[0].wskin && plan[k].lpas3 == plan[0].lpas3;
-  }
-  if (!uniform) {
-    for (int k = 0; k < nsel; ++k) {
-      Replica &rp = ctx->rep[reps[k]];
-      TMD_TRY(enqueue_chain<R>(ctx, rp, pos[k], cs[k], rp.flags.as<int>() + F_REBUILD0 + parity[k], st));
-    }
-    return 0;
-  }
-  {
-    // Many replicas in one launch (always so with TMDHIP_REPLICA_REBUILDS=together): the chip is as full as under one big box —
-    // where ONE block per cell is the fastest cut (T = 54 us x blocks per cell + 111 us at C3's 6 859 cells,
-    // profiles/r06_build_experiments.txt); the two blocks per cell of a small grid are for a replica that rebuilds alone.
-    // (Which block builds an atom's row does not change the row: the lists are the same entry for entry.)
-    long cells = 0;
-    for (int k = 0; k < nsel; ++k) cells += plan[k].ncell;
-    if (cells >= 3000 && !std::getenv("TMDHIP_BUILD_SPLIT") && !std::getenv("TMDHIP_BATCH_BUILD_SPLIT"))
-      for (int k = 0; k < nsel; ++k) {
-        plan[k].split = 1;
-        plan[k].build_blocks = plan[k].ncell;
-      }
-  }
-  const size_t row = sizeof(ChainRepT<R>);
-  TMD_TRY(ctx->chain_tab.ensure(row * (size_t)nrep));
-  if (ctx->chain_host.size() != row * (size_t)nrep) ctx->chain_host.assign(row * (size_t)nrep, 0xA5);  // (matches nothing)
-  ChainRepT<R> *tab = ctx->chain_tab.as<ChainRepT<R>>();
+static int upload_chain_rows(tmdhip_ctx *ctx, int nsel, const int *reps, const ChainRepT<R> *plan, hipStream_t st) {
+  const size_t row = sizeof(ChainRepT<R>), nrep = ctx->rep.size();
+  TMD_TRY(ctx->chain_tab.ensure(row * nrep));
+  if (ctx->chain_host.size() != row * nrep) ctx->chain_host.assign(row * nrep, 0xA5);  // (matches nothing)
   for (int k = 0; k < nsel; ++k) {
     unsigned char *have = ctx->chain_host.data() + row * (size_t)reps[k];
     if (std::memcmp(have, &plan[k], row) != 0) {
-      hipLaunchKernelGGL((chain_upload_kernel<R>), dim3(1), dim3(64), 0, st, plan[k], tab + reps[k]);
+      hipLaunchKernelGGL((chain_upload_kernel<R>), dim3(1), dim3(64), 0, st, plan[k], ctx->chain_tab.as<ChainRepT<R>>() + reps[k]);
       TMD_HIP(hipGetLastError());
       std::memcpy(have, &plan[k], row);
     }
   }
-  for (int g0 = 0; g0 < nsel; g0 += kBatchMax) {
-    const int gn = std::min(kBatchMax, nsel - g0);
-    ChainSelT<R> sel;
-    std::memset(&sel, 0, sizeof(sel));
-    sel.nsel = gn;
-    {
-      const char *e = std::getenv("TMDHIP_REPLICA_REBUILDS");  // ("together": see chain_any; read per call)
-      sel.together = (e && std::strcmp(e, "together") == 0) ? 1 : 0;
-    }
-    int max_cells = 0, max_blocks = 0;
-    for (int k = 0; k < gn; ++k) {
-      Replica &rp = ctx->rep[reps[g0 + k]];
-      sel.rep[k] = reps[g0 + k];
-      sel.pos[k] = pos[g0 + k];
-      sel.flag[k] = rp.flags.as<int>() + F_REBUILD0 + parity[g0 + k];
-      sel.sorted[k] = rp.sorted.as<R4>();
-      max_cells = std::max(max_cells, plan[g0 + k].ncell);
-      max_blocks = std::max(max_blocks, plan[g0 + k].build_blocks);
-    }
-    const int nb = (n + 255) / 256;
-    if (plan[0].mode == 0) {
-      hipLaunchKernelGGL((prep_small_batch_kernel<R>), dim3(1, gn), dim3(1024), 0, st, n, tab, sel);
-    } else {
-      hipLaunchKernelGGL((bin_members_batch_kernel<R>), dim3(nb, gn), dim3(256), 0, st, n, tab, sel);
-      hipLaunchKernelGGL((scan_place_batch_kernel<R>), dim3(nb, gn), dim3(256), sizeof(int) * ((size_t)max_cells + 1), st, n, tab, sel);
-    }
-    const dim3 bgrid(max_blocks, gn);
-#define TMD_BB(W, L) \
-  hipLaunchKernelGGL((build_list_batch_kernel<R, W, L>), bgrid, dim3(64), 0, st, n, ctx->excl_off.as<int>(), ctx->excl_idx.as<int>(), tab, sel)
-    if (plan[0].lpas3) {
-      if (plan[0].wskin) TMD_BB(true, 3);
-      else TMD_BB(false, 3);
-    } else {
-      if (plan[0].wskin) TMD_BB(true, -1);
-      else TMD_BB(false, -1);
-    }
-#undef TMD_BB
-    TMD_HIP(hipGetLastError());
-    ctx->batched_chains++;
+  return 0;
+}
+
+// One batched chain for the gn <= kBatchMax replicas reps[0 .. gn), all of plan[0]'s binning and kernel variant.
+template <typename R>
+static int launch_chain_batch(tmdhip_ctx *ctx, int gn, const int *reps, const ChainRepT<R> *plan, const R *const *pos, const int *parity,
+                              bool together, hipStream_t st) {
+  using R4 = typename Vec<R>::T4;
+  const int n = ctx->d.natoms, nb = (n + 255) / 256;
+  const ChainRepT<R> *tab = ctx->chain_tab.as<ChainRepT<R>>();
+  ChainSelT<R> sel;
+  std::memset(&sel, 0, sizeof(sel));
+  sel.nsel = gn, sel.together = together ? 1 : 0;
+  int max_cells = 0, max_blocks = 0;
+  for (int k = 0; k < gn; ++k) {
+    Replica &rp = ctx->rep[reps[k]];
+    sel.rep[k] = reps[k], sel.pos[k] = pos[k];
+    sel.flag[k] = rp.flags.as<int>() + F_REBUILD0 + parity[k];
+    sel.sorted[k] = rp.sorted.as<R4>();
+    max_cells = std::max(max_cells, plan[k].ncell);
+    max_blocks = std::max(max_blocks, plan[k].build_blocks);
   }
+  if (plan[0].mode == Binning::OneLaunch) {
+    hipLaunchKernelGGL((prep_small_batch_kernel<R>), dim3(1, gn), dim3(1024), 0, st, n, tab, sel);
+  } else {
+    hipLaunchKernelGGL((bin_members_batch_kernel<R>), dim3(nb, gn), dim3(256), 0, st, n, tab, sel);
+    hipLaunchKernelGGL((scan_place_batch_kernel<R>), dim3(nb, gn), dim3(256), sizeof(int) * ((size_t)max_cells + 1), st, n, tab, sel);
+  }
+  with_build_variant(plan[0].wskin, plan[0].lpas3, [&](auto W, auto L) {
+    hipLaunchKernelGGL((build_list_batch_kernel<R, decltype(W)::value, decltype(L)::value>), dim3(max_blocks, gn), dim3(64), 0, st, n,
+                       ctx->excl_off.as<int>(), ctx->excl_idx.as<int>(), tab, sel);
+  });
+  TMD_HIP(hipGetLastError());
+  ctx->batched_chains++;
+  return 0;
+}
+
+// The rebuild chains of the replicas reps[0 .. nsel) in one launch per kernel (see ChainRepT).  pos[k] / parity[k] / box[k]: what
+// enqueue_list_update would have been given for replica reps[k] (its displacement test has run already).  Planned once, as rows of
+// the batched chain; a single replica, or replicas that batch_covers refuses, get lone chains from the same plans, cut by the lone rules.
+template <typename R>
+int enqueue_chain_batch(tmdhip_ctx *ctx, int nsel, const int *reps, const R *const *pos, const int *parity, const double *const *box,
+                        hipStream_t st) {
+  using R4 = typename Vec<R>::T4;
+  const ChainKnobs knobs = read_chain_knobs();
+  std::vector<ChainRepT<R>> plan(nsel);
+  for (int k = 0; k < nsel; ++k) plan_chain<R>(ctx, ctx->rep[reps[k]], make_consts<R>(ctx, box[k]), knobs, true, plan[k]);
+  if (!batch_covers(plan.data(), nsel)) {
+    for (int k = 0; k < nsel; ++k) {
+      Replica &rp = ctx->rep[reps[k]];
+      choose_chain(plan[k], rp, ctx->d.natoms, knobs, false);
+      TMD_TRY(launch_chain<R>(ctx, plan[k], pos[k], rp.sorted.as<R4>(), rp.flags.as<int>() + F_REBUILD0 + parity[k], st));
+    }
+    return 0;
+  }
+  long cells = 0;
+  for (int k = 0; k < nsel; ++k) cells += plan[k].ncell;
+  if (batch_single_block_per_cell(cells, knobs))
+    for (int k = 0; k < nsel; ++k) plan[k].split = 1, plan[k].build_blocks = plan[k].ncell;
+  TMD_TRY(upload_chain_rows<R>(ctx, nsel, reps, plan.data(), st));
+  for (int g0 = 0; g0 < nsel; g0 += kBatchMax)
+    TMD_TRY(launch_chain_batch<R>(ctx, std::min(kBatchMax, nsel - g0), reps + g0, plan.data() + g0, pos + g0, parity + g0, knobs.together, st));
   return 0;
 }
 template int enqueue_chain_batch<float>(tmdhip_ctx *, int, const int *, const float *const *, const int *, const double *const *, hipStream_t);
+
+// Speculation of a plain evaluation (enqueue_list_update): reads the previous evaluation's report from the replica's host-mapped
+// words, numbers this evaluation and points its displacement test `k` at them.  skip: this evaluation's chain is left out.
+template <typename R>
+static int speculate_chain(Replica &rp, ListCheck<R> &k, bool &skip) {
+  if (!rp.hostpub) {
+    TMD_HIP(hipHostMalloc((void **)&rp.hostpub, 8 * sizeof(unsigned), hipHostMallocMapped));
+    for (int w = 0; w < 8; ++w) rp.hostpub[w] = 0u;
+    rp.seq = 0;
+  }
+  volatile unsigned *hp = rp.hostpub;
+  // (the previous evaluation's report: its call synchronised with the device before it returned)
+  if (rp.spec_valid && rp.spec_backoff == 0) skip = hp[1 + (rp.seq & 1u)] != rp.seq;
+  if (rp.spec_backoff > 0) rp.spec_backoff--;
+  if (++rp.seq == 0) rp.seq = 1;
+  k.near_host = rp.hostpub + 1 + (rp.seq & 1u), k.seq = rp.seq;
+  k.near_frac2 = (R)(0.75 * 0.75), k.skipped = skip ? 1 : 0;
+  rp.spec_valid = true;
+  rp.seq_valid = false;  // (the MD loop's pacing must not read a plain evaluation's report as its own)
+  return 0;
+}
 
 // Enqueue: displacement check -> conditional rebuild chain.  `force` forces a rebuild.
 // `prechecked`: the fused MD-step kernel already ran the displacement test of this step.
@@ -1264,49 +1191,30 @@ template int enqueue_chain_batch<float>(tmdhip_ctx *, int, const int *, const fl
 // a ~100-us evaluation.  The displacement test reports to host-mapped words like the MD loop's (ListCheck::near_host); when the
 // PREVIOUS evaluation found no atom beyond 75 % of its limit the chain is left out, and an atom that crosses its limit all the
 // same raises F_VIOLATION: tmdhip_compute reads the flags back before it returns, reports "repeat", and the repetition re-plans
-// and rebuilds (judge_flags); the next 16 evaluations keep their chain.
+// and rebuilds (judge_flags); the next 16 evaluations keep their chain.  TMDHIP_SPEC_CHAIN=0 switches it off (read per call).
 template <typename R>
 int enqueue_list_update(tmdhip_ctx *ctx, Replica &rp, const R *pos, const PairConsts<R> &c, int force,
                         hipStream_t st, bool prechecked, bool speculate) {
   using R4 = typename Vec<R>::T4;
   const int n = ctx->d.natoms;
-  const int parity = (int)(rp.step & 1);
-  const int *flag = rp.flags.as<int>() + F_REBUILD0 + parity;
+  const int *flag = rp.flags.as<int>() + F_REBUILD0 + (int)(rp.step & 1);
+  const char *e_spec = std::getenv("TMDHIP_SPEC_CHAIN");
+  const bool spec = !prechecked && speculate && !force && !(e_spec && std::atoi(e_spec) == 0);
   bool skip = false;
+  if (!spec) rp.spec_valid = false;
   if (!prechecked) {
     ListCheck<R> k = make_check<R>(ctx, rp);
-    const char *e_spec = std::getenv("TMDHIP_SPEC_CHAIN");  // (0 switches it off; read per call: tests toggle it)
-    const bool spec_on = !(e_spec && std::atoi(e_spec) == 0);
-    if (speculate && spec_on && !force) {
-      if (!rp.hostpub) {
-        TMD_HIP(hipHostMalloc((void **)&rp.hostpub, 8 * sizeof(unsigned), hipHostMallocMapped));
-        for (int w = 0; w < 8; ++w) rp.hostpub[w] = 0u;
-        rp.seq = 0;
-      }
-      volatile unsigned *hp = rp.hostpub;
-      // (the previous evaluation's report: its call synchronised with the device before it returned)
-      if (rp.spec_valid && rp.spec_backoff == 0) skip = hp[1 + (rp.seq & 1u)] != rp.seq;
-      if (rp.spec_backoff > 0) rp.spec_backoff--;
-      if (++rp.seq == 0) rp.seq = 1;
-      k.near_host = rp.hostpub + 1 + (rp.seq & 1u);
-      k.seq = rp.seq;
-      k.near_frac2 = (R)(0.75 * 0.75);
-      k.skipped = skip ? 1 : 0;
-      rp.spec_valid = true;
-      rp.seq_valid = false;  // (the MD loop's pacing must not read a plain evaluation's report as its own)
-    } else {
-      rp.spec_valid = false;
-    }
+    if (spec) TMD_TRY(speculate_chain<R>(rp, k, skip));
     hipLaunchKernelGGL((check_displacement_kernel<R>), dim3((n + 255) / 256), dim3(256), 0, st, n, pos, k, c,
                        force, rp.inv.as<int>(), ctx->qs.as<R>(), rp.sorted.as<R4>());
-  } else {
-    rp.spec_valid = false;
   }
   if (skip) {
     rp.chains_skipped++;
     return 0;
   }
-  return enqueue_chain<R>(ctx, rp, pos, c, flag, st);
+  ChainRepT<R> plan;
+  plan_chain<R>(ctx, rp, c, read_chain_knobs(), false, plan);
+  return launch_chain<R>(ctx, plan, pos, rp.sorted.as<R4>(), flag, st);
 }
 
 template int enqueue_list_update<float>(tmdhip_ctx *, Replica &, const float *, const PairConsts<float> &, int, hipStream_t, bool, bool);

@@ -440,13 +440,13 @@ struct MdRun {
         langevin(d_->vcoeff_dev != nullptr), cur(nrep), owed(nrep, 0), stepped(nrep, 0), finalized(nrep, 0),
         home_all((R *)d_->pos_dev), bcur((R *)d_->pos_dev) {
     const char *e_min = std::getenv("TMDHIP_DEBUG_CHAIN_MIN_ENTRIES"), *e_near = std::getenv("TMDHIP_DEBUG_CHAIN_NEAR"),
-               *e_batch = std::getenv("TMDHIP_BATCH_REPLICAS"), *e_tog = std::getenv("TMDHIP_REPLICA_REBUILDS");
+               *e_batch = std::getenv("TMDHIP_BATCH_REPLICAS");
     chain_skip_on = !env_is_zero("TMDHIP_CHAIN_SKIP") && !ctx->no_chain_skip_once;
     chain_min_entries = e_min ? std::atoll(e_min) : kChainSkipMinEntries;
     chain_near = e_near ? std::atof(e_near) : kChainSkipNear;
     final_on = !env_is_zero("TMDHIP_FUSED_FINAL");
     batch_min = !e_batch ? 2 : std::atoi(e_batch) == 0 ? std::numeric_limits<int>::max() : std::atoi(e_batch) == 2 ? 1 : 2;
-    rebuilds_together = e_tog && std::strcmp(e_tog, "together") == 0;
+    rebuilds_together = read_chain_knobs().together;
     ctx->no_chain_skip_once = false;
     ctx->fused_off_call = ctx->no_fused_once;
     ctx->no_fused_once = false;
