@@ -401,6 +401,28 @@ int tmdhip_fire_init(int64_t nreplicas, double *state_dev, const tmdhip_fire_par
 int tmdhip_fire_step(int dtype, int64_t nreplicas, int64_t natoms, void *pos_dev, void *vel_dev, const void *forces_dev,
                      const void *mass_dev, double *state_dev, double *partials_dev, const tmdhip_fire_params *params,
                      int64_t iteration, void *stream);
+/* Stochastic velocity rescaling (Bussi, Donadio & Parrinello, JCP 126, 014101, 2007) with one target per replica, and
+ * centre-of-mass motion removal, stateless (added to ABI 11): one application to velocities that are in vel_dev [R][natoms][3].
+ * The per-replica arrays are HOST arrays of nreplicas entries, read before the call returns (they travel as kernel arguments,
+ * 16 replicas per pair of launches): kbar = N_f k_B T / 2 (energy units of m v^2), ndof = N_f, c = exp(-dt / tau) in [0, 1],
+ * r1 a standard normal, s a chi-squared variate with N_f - 1 degrees of freedom, active (may be NULL: all) != 0 for the
+ * replicas to treat.  For an active replica, all sums over the rows with mass > 0 (rows with mass == 0 are neither read nor
+ * written):
+ *   V_cm = sum m v / sum m if remove_com, else 0;  K = (1/2) sum m v^2 - (1/2) (sum m) V_cm^2;
+ *   alpha^2 = c + (1 - c) kbar (r1^2 + s) / (ndof K) + 2 r1 sqrt(c (1 - c) kbar / (ndof K)), alpha = sqrt(max(alpha^2, 0)),
+ *   alpha = 1 if K = 0;  v <- alpha (v - V_cm)   (not written at all when c == 1 and remove_com == 0).
+ * record_dev is double [R][TMDHIP_THERMOSTAT_RECORD_DOUBLES]: {K_before, alpha, K_after = alpha^2 K, |V_cm|, heat, applications,
+ * 0, 0}; `heat` (the sum of K_after - K_before) and `applications` accumulate, so the caller zeroes the record once before the
+ * first application.  An inactive replica's velocities and record are not touched.  partials_dev is scratch, double
+ * [R][TMDHIP_THERMOSTAT_MAX_BLOCKS][5]; tmdhip_thermostat_workspace returns both sizes in doubles.  Two launches per 16
+ * replicas, sums and state arithmetic in double in both precisions, no atomics: two runs give the same bits. */
+#define TMDHIP_THERMOSTAT_RECORD_DOUBLES 8
+#define TMDHIP_THERMOSTAT_MAX_BLOCKS 256
+int tmdhip_thermostat_workspace(int64_t nreplicas, int64_t *record_doubles, int64_t *partials_doubles);
+int tmdhip_thermostat_apply(int dtype, int64_t nreplicas, int64_t natoms, void *vel_dev, const void *mass_dev,
+                            const double *kbar_host, const double *ndof_host, const double *c_host, const double *r1_host,
+                            const double *s_host, const int32_t *active_host, int32_t remove_com, double *record_dev,
+                            double *partials_dev, void *stream);
 /* Fill `out_dev` (real [n]) with the N(0,1) stream used by tmdhip_langevin_second_vv (for tests). */
 int tmdhip_normal_fill(int dtype, int64_t n, void *out_dev, uint64_t seed, uint64_t step, void *stream);
 

@@ -3,7 +3,8 @@
 Public surface mirrors the reference package for this path:
     torchmd_amd.forces.Forces, torchmd_amd.integrator.Integrator, torchmd_amd.systems.System,
     torchmd_amd.parameters.Parameters, torchmd_amd.forcefields.ForceField
-plus `torchmd_amd.MonteCarloBarostat` (constant pressure; imported on first use only)
+plus `torchmd_amd.MonteCarloBarostat` (constant pressure) and `torchmd_amd.VelocityRescale` (stochastic velocity
+rescaling, one target temperature per replica); both imported on first use only,
 backed by hand-written HIP kernels in `torchmd_amd/lib/libtmdhip.so` (C ABI: include/tmdhip.h).
 """
 
@@ -15,11 +16,15 @@ from .systems import System
 
 
 def __getattr__(name):
-    # the barostat module is loaded on first use: a run without it never imports it
+    # the barostat and thermostat modules are loaded on first use: a run without them never imports them
     if name == "MonteCarloBarostat":
         from .barostat import MonteCarloBarostat
 
         return MonteCarloBarostat
+    if name == "VelocityRescale":
+        from .thermostat import VelocityRescale
+
+        return VelocityRescale
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 
@@ -29,6 +34,7 @@ __all__ = [
     "MonteCarloBarostat",
     "Parameters",
     "System",
+    "VelocityRescale",
     "kinetic_energy",
     "kinetic_to_temp",
     "maxwell_boltzmann",

@@ -264,6 +264,10 @@ class FireParams(C.Structure):
 FIRE_STATE_DOUBLES, FIRE_MAX_BLOCKS = 8, 256  # TMDHIP_FIRE_STATE_DOUBLES, TMDHIP_FIRE_MAX_BLOCKS
 FIRE_DT, FIRE_ALPHA, FIRE_NPOS, FIRE_DONE, FIRE_ITERATIONS, FIRE_FMAX, FIRE_NUPHILL = range(7)  # fields of a state slot
 
+THERMOSTAT_RECORD_DOUBLES, THERMOSTAT_MAX_BLOCKS = 8, 256  # TMDHIP_THERMOSTAT_RECORD_DOUBLES, TMDHIP_THERMOSTAT_MAX_BLOCKS
+# fields of a thermostat record
+THERMOSTAT_K_BEFORE, THERMOSTAT_ALPHA, THERMOSTAT_K_AFTER, THERMOSTAT_VCM, THERMOSTAT_HEAT, THERMOSTAT_COUNT = range(6)
+
 # name -> (restype, argtypes): every symbol include/tmdhip.h declares
 SIGNATURES = {
     "tmdhip_abi_version": (C.c_int, []),
@@ -344,6 +348,12 @@ SIGNATURES = {
         C.c_int,
         [C.c_int, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
          C.POINTER(FireParams), C.c_int64, C.c_void_p],
+    ),
+    "tmdhip_thermostat_workspace": (C.c_int, [C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "tmdhip_thermostat_apply": (
+        C.c_int,
+        [C.c_int, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double),
+         C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int32), C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p],
     ),
     "tmdhip_normal_fill": (C.c_int, [C.c_int, C.c_int64, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p]),
     "tmdhip_dd_step": (

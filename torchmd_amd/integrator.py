@@ -4,7 +4,9 @@ Mirror of the reference module (`torchmd/integrator.py`): same constants, helper
 `Integrator(systems, forces, timestep, device, gamma=None, T=None, batch=None)` constructor and
 `step(niter) -> (Ekin, pot, T)` contract, plus an opt-in `constraints` keyword ("water": rigid waters by SETTLE;
 "hbonds": also every X-H bond by SHAKE/RATTLE) and an opt-in `barostat` keyword (a
-`barostat.MonteCarloBarostat`: constant pressure) that this package adds.  Each iteration is
+`barostat.MonteCarloBarostat`: constant pressure) and an opt-in `thermostat` keyword (a
+`thermostat.VelocityRescale`: stochastic velocity rescaling between batches of steps, one target temperature per replica,
+DESIGN §14) that this package adds.  Each iteration is
 
     tmdhip_first_vv  ->  forces.compute  ->  tmdhip_langevin_second_vv | tmdhip_second_vv
 
@@ -109,8 +111,25 @@ def cut_segments(nstep, niter, frequency):
     return out
 
 
+def cut_schedules(nstep, niter, frequencies):
+    """`cut_segments` for several things with a frequency each: [(n, (hit, ...)), ...] with sum(n) == niter, cut at the union
+    of the schedules; hit[k] says that the segment ends on a multiple of frequencies[k]."""
+    ends = {}
+    for k, f in enumerate(frequencies):
+        done = 0
+        for n, hit in cut_segments(nstep, niter, f):
+            done += n
+            ends.setdefault(done, [False] * len(frequencies))[k] = hit
+    out, prev = [], 0
+    for end in sorted(ends):
+        out.append((end - prev, tuple(ends[end])))
+        prev = end
+    return out
+
+
 class Integrator:
-    def __init__(self, systems, forces, timestep, device, gamma=None, T=None, batch=None, constraints=None, barostat=None):
+    def __init__(self, systems, forces, timestep, device, gamma=None, T=None, batch=None, constraints=None, barostat=None,
+                 thermostat=None):
         self.dt = timestep / TIMEFACTOR
         self.systems = systems
         self.forces = forces
@@ -150,8 +169,29 @@ class Integrator:
             self._init_constraints(constraints)
         self.replays = 0  # batches that were rewound and repeated (list validity failure / step-block time-out)
         self.barostat = barostat  # barostat.MonteCarloBarostat
+        self.thermostat = thermostat  # thermostat.VelocityRescale
+        if thermostat is not None:
+            self._init_thermostat(thermostat)
         if barostat is not None:
-            barostat.check(systems, forces, temperature=T if T else 0)
+            barostat.check(systems, forces, temperature=(thermostat.temperature if thermostat is not None else T) or 0)
+
+    def _init_thermostat(self, th):
+        """What is refused (ValueError): a second thermostat (Langevin), atom groups, a ladder of the wrong length, a ladder
+        under a barostat (which knows one temperature).  The thermostat's N_f is this integrator's count of degrees of
+        freedom minus 3 when it removes the centre-of-mass motion; `_temperature` keeps dividing by the full count."""
+        if self.T or self.gamma is not None:
+            raise ValueError("thermostat= and a Langevin T / gamma are two thermostats: give one of them")
+        if self.batch is not None:
+            raise ValueError("thermostat= does not support atom groups (batch=): its scale factor is per replica")
+        th.targets(self.systems.pos.shape[0])
+        if self.barostat is not None and th.temperature is None:
+            raise ValueError("a temperature ladder cannot run under barostat=: the barostat holds one temperature")
+        if self.constraints is not None:
+            ndof = int(self._ndof)
+        else:
+            ndof = 3 * int((self.masses > 0).sum().item())
+        th.degrees_of_freedom(ndof)
+        self._thermostat_ndof = ndof
 
     def _init_constraints(self, mode):
         from .constraints import find_constraints
@@ -217,6 +257,8 @@ class Integrator:
         with torch.cuda.device(dev):
             if self.constraints is not None and not self._projected:
                 self._project_start()
+            if self.thermostat is not None and niter > 0:
+                return self._step_thermostat(lib, s, dev, code, R, N, fast, niter)
             if self.barostat is not None and niter > 0:
                 return self._step_npt(lib, s, dev, code, R, N, fast, niter)
             return self._step_body(lib, s, dev, code, R, N, fast, fused, niter, replay=False)
@@ -233,6 +275,30 @@ class Integrator:
                 rec = self.barostat.attempt(s, self.forces, out[1])
                 pot = [float(un if ok else u) for u, un, ok in zip(rec["U"], rec["U_new"], rec["accepted"])]
                 out = (out[0], pot, out[2])
+        return out
+
+    def _step_thermostat(self, lib, s, dev, code, R, N, fast, niter):
+        """`step(niter)` under a rescaling thermostat (and possibly a barostat): segments cut at the union of both schedules,
+        each run as `step` runs it (rewind and replay included); the thermostat is applied after a segment that ended on a
+        multiple of its frequency has returned, before the volume move where both fall on one step.  The kinetic energy
+        returned is that of the velocities as they are left: `K_after` of the record when the call ends on an application."""
+        th, baro = self.thermostat, self.barostat
+        freqs = (th.frequency,) + ((baro.frequency,) if baro is not None else ())
+        out, rescaled = None, False
+        for n, hit in cut_schedules(self._nstep, niter, freqs):
+            fused = fast and not self.forces.external
+            out = self._step_body(lib, s, dev, code, R, N, fast, fused, n, replay=False)
+            rescaled = hit[0]
+            if hit[0]:
+                th.apply(s, self.masses, self.dt, self._thermostat_ndof)
+            if baro is not None and hit[1]:
+                rec = baro.attempt(s, self.forces, out[1])
+                pot = [float(un if ok else u) for u, un, ok in zip(rec["U"], rec["U_new"], rec["accepted"])]
+                out = (out[0], pot, out[2])
+        if rescaled:
+            Ekin = th.last[:, L.THERMOSTAT_K_AFTER].cpu().numpy()
+            Ekin = Ekin.astype(np.dtype("float32") if s.pos.dtype == torch.float32 else np.float64)
+            out = (Ekin, out[1], self._temperature(Ekin))
         return out
 
     def _step_body(self, lib, s, dev, code, R, N, fast, fused, niter, replay):

@@ -46,6 +46,11 @@ DEFAULTS = dict(
     barostat_pressure=None,  # bar; None: constant volume.  Monte Carlo barostat at langevin_temperature: DESIGN §11
     barostat_frequency=25,  # steps between two volume moves
     minimizer="bfgs",  # what `minimize: N` runs: "bfgs" (scipy L-BFGS-B, one replica) or "fire" (on the device, every replica): DESIGN §13
+    thermostat=None,  # None or "csvr": stochastic velocity rescaling between batches of steps (instead of Langevin): DESIGN §14
+    thermostat_tau=0.1,  # ps; 0 resamples the kinetic energy at every application
+    thermostat_frequency=10,  # steps between two applications
+    thermostat_temperature=None,  # K: a number, or a list with one target per replica; None: `temperature`
+    remove_com=True,  # the thermostat also takes out the centre-of-mass motion
     virtual_sites=None,  # None or "tip4p": four-site waters O,H1,H2,M; geometry from the force field's `virtual_sites` section: DESIGN §12
 )
 
@@ -93,6 +98,26 @@ def get_args(arguments=None):
     args.barostat_frequency = int(args.barostat_frequency)
     if args.barostat_frequency < 1:
         raise ValueError(f"barostat_frequency must be a positive number of steps, got {args.barostat_frequency}")
+    if isinstance(args.thermostat, str) and args.thermostat.lower() in ("none", "null", ""):
+        args.thermostat = None
+    if args.thermostat is not None:
+        args.thermostat = str(args.thermostat).lower()
+        if args.thermostat != "csvr":
+            raise ValueError(f"thermostat must be None or 'csvr', got {args.thermostat!r}")
+        if args.langevin_temperature:
+            raise ValueError("thermostat: csvr replaces the Langevin thermostat: leave langevin_temperature at 0")
+    args.thermostat_tau = float(args.thermostat_tau)
+    args.thermostat_frequency = int(args.thermostat_frequency)
+    if isinstance(args.thermostat_temperature, str):
+        tt = [float(v) for v in args.thermostat_temperature.replace(",", " ").split()]
+        args.thermostat_temperature = tt[0] if len(tt) == 1 else tt
+    elif isinstance(args.thermostat_temperature, (list, tuple)):
+        args.thermostat_temperature = [float(v) for v in args.thermostat_temperature]
+    elif args.thermostat_temperature is not None:
+        args.thermostat_temperature = float(args.thermostat_temperature)
+    if isinstance(args.remove_com, str):
+        args.remove_com = args.remove_com.lower() not in ("false", "0", "no", "off")
+    args.remove_com = bool(args.remove_com)
     if args.pme_grid is not None:
         args.pme_grid = tuple(int(v) for v in args.pme_grid)
     for k in ("steps", "output_period", "save_period", "replicas", "seed", "pme_order"):
@@ -252,16 +277,27 @@ class FrameStager:
 def dynamics(args, mol, system, forces):
     torch.manual_seed(args.seed)
     device = torch.device(args.device)
-    barostat = None
+    barostat = thermostat = None
+    if args.thermostat is not None:
+        from .thermostat import VelocityRescale
+
+        target = args.thermostat_temperature if args.thermostat_temperature is not None else args.temperature
+        thermostat = VelocityRescale(target, tau=args.thermostat_tau, frequency=args.thermostat_frequency,
+                                     remove_com=args.remove_com)
     if args.barostat_pressure is not None:
         from .barostat import MonteCarloBarostat
 
-        if not args.langevin_temperature:
-            raise ValueError("barostat_pressure needs a thermostat: set langevin_temperature")
-        barostat = MonteCarloBarostat(args.barostat_pressure, args.langevin_temperature, args.barostat_frequency)
+        bath = thermostat.temperature if thermostat is not None else args.langevin_temperature
+        if not bath:
+            raise ValueError("barostat_pressure needs a thermostat at one temperature: set langevin_temperature, or "
+                             "thermostat: csvr with a single thermostat_temperature")
+        barostat = MonteCarloBarostat(args.barostat_pressure, bath, args.barostat_frequency)
     extra = {} if barostat is None else {"barostat": barostat}
-    integrator = Integrator(system, forces, args.timestep, device, gamma=args.langevin_gamma,
-                            T=args.langevin_temperature, constraints=args.constraints, **extra)
+    if thermostat is not None:
+        integrator = Integrator(system, forces, args.timestep, device, constraints=args.constraints, thermostat=thermostat, **extra)
+    else:
+        integrator = Integrator(system, forces, args.timestep, device, gamma=args.langevin_gamma,
+                                T=args.langevin_temperature, constraints=args.constraints, **extra)
     wrapper = Wrapper(mol.numAtoms, mol.bonds if len(mol.bonds) else None, device)
     nper = args.steps // args.output_period
     stager = FrameStager(system, nper)
