@@ -80,71 +80,18 @@ int pick_lpa(int64_t n, int capacity) {  // n: atoms whose waves share a launch 
   return std::max(lpa, by_len);
 }
 
-// choose grid for the current box; returns false if the cell path cannot be used
+// choose grid for the current box; returns false if the cell path cannot be used (the arithmetic: grid_plan.h)
 bool plan_grid(const tmdhip_ctx *ctx, const double *box, const double *lo, const double *hi, Grid &g) {
-  const bool periodic = !(box[0] == 0 && box[1] == 0 && box[2] == 0);
-  g.periodic = periodic ? 1 : 0;
-  double len[3];
-  for (int k = 0; k < 3; ++k) {
-    if (periodic) {
-      if (!(box[k] > 0)) return false;
-      len[k] = box[k];
-      g.origin[k] = 0;
-    } else {
-      len[k] = std::max(hi[k] - lo[k], 1e-3);
-      g.origin[k] = lo[k];
-    }
+  GridPlan p;
+  std::memcpy(p.zreach, g.zreach, sizeof(p.zreach));  // (entries outside the stencil stay what they were)
+  if (!plan_grid_host(ctx->d.natoms, ctx->rlist, box, lo, hi, read_stencil_knob(), p)) {
+    g.periodic = p.periodic;
+    return false;
   }
-  // stencil half-width m: cell edge >= rlist/m.  m=3 (measured at C3: 29^3 cells of ~4 atoms) halves the
-  // candidate volume but the build takes 345 us instead of 200: a build wave works on one cell and its
-  // fixed costs (stencil set-up, staging the cell's atoms and exclusions, one candidate load per chunk)
-  // are then amortised over 4 atoms instead of 14.  The kernel supports it (zreach), the planner stops at 2.
-  int mmax = 2;
-  if (const char *e = std::getenv("TMDHIP_STENCIL")) {  // tuning override: largest stencil half-width tried
-    const int v = std::atoi(e);
-    if (v >= 1 && v <= 3) mmax = v;
-  }
-  for (int m = mmax; m >= 1; --m) {
-    bool ok = true;
-    int nc[3];
-    for (int k = 0; k < 3; ++k) {
-      nc[k] = (int)std::floor(len[k] / (ctx->rlist / m));
-      if (nc[k] < 1) nc[k] = 1;
-      if (periodic && nc[k] < 2 * m + 1) ok = false;
-      if (nc[k] > 1024) nc[k] = 1024;
-    }
-    if (!ok) continue;
-    // a build wave works on one cell: at gas/liquid-argon densities half-width 2 leaves ~3 atoms per cell
-    // (343k cells for the 10^6-atom LJ box) and the coarser grid is faster overall (179 vs 185 us/step)
-    const double per_cell = (double)ctx->d.natoms / ((double)nc[0] * nc[1] * nc[2]);
-    if (m == 3 && per_cell < 2.0) continue;
-    if (m == 2 && per_cell < 4.0 && !std::getenv("TMDHIP_STENCIL")) {
-      bool coarse_ok = true;
-      for (int k = 0; k < 3; ++k) coarse_ok = coarse_ok && (!periodic || (int)std::floor(len[k] / ctx->rlist) >= 3);
-      if (coarse_ok) continue;
-    }
-    g.m = m;
-    double edge[3];
-    for (int k = 0; k < 3; ++k) {
-      g.nc[k] = nc[k];
-      g.inv_edge[k] = nc[k] / len[k];
-      edge[k] = len[k] / nc[k];
-    }
-    for (int ox = -3; ox <= 3; ++ox)
-      for (int oy = -3; oy <= 3; ++oy) {
-        int zr = -1;
-        if (std::abs(ox) <= m && std::abs(oy) <= m) {
-          const double gx = std::max(std::abs(ox) - 1, 0) * edge[0], gy = std::max(std::abs(oy) - 1, 0) * edge[1];
-          for (int oz = 0; oz <= m; ++oz) {
-            const double gz = std::max(oz - 1, 0) * edge[2];
-            if (gx * gx + gy * gy + gz * gz <= ctx->rlist * ctx->rlist) zr = oz;
-          }
-          g.zreach[ox + m][oy + m] = (signed char)zr;
-        }
-      }
-    return true;
-  }
-  return false;
+  g.m = p.m, g.periodic = p.periodic;
+  for (int k = 0; k < 3; ++k) g.nc[k] = p.nc[k], g.origin[k] = p.origin[k], g.inv_edge[k] = p.inv_edge[k];
+  std::memcpy(g.zreach, p.zreach, sizeof(g.zreach));
+  return true;
 }
 
 // Padded list rows (engine.h: pad_entry_for; the pair waves write the padding, pair_fast_f32.hip): fp32 contexts whose entries can address the two dummy records with bits 20..22

@@ -47,6 +47,7 @@
 #include "bonded_math.h"
 #include "pacing.h"
 #include "chain_plan.h"
+#include "grid_plan.h"
 #include "rng.h"
 
 namespace tmd {
