@@ -1121,7 +1121,9 @@ def test_lean_kernel_switching_variants(mode, lpa, monkeypatch):
 def test_tiny_systems_and_odd_sizes():
     """Edge sizes: 1 atom (no pair at all), 2 atoms (one pair: analytic LJ), 3 water atoms (every pair
     excluded), 63 / 65 / 129 argon atoms (partial tiles of the all-pairs kernel) against the oracle, and
-    several such replicas batched in one launch."""
+    several such replicas batched in one launch.  (The 2-atom case is one distance, LJ only, fp64, the all-pairs kernel:
+    tests/test_gpu_pair_resolved.py holds every pair kernel to a long-double reference pair by pair, over the whole range
+    of r, every term set and both precisions.)"""
     from oracle import torchmd_oracle as orc
     from torchmd_amd.builders import argon_forcefield, lj_box, tip3p_box, water_forcefield
     from torchmd_amd.forces import Forces
