@@ -423,6 +423,22 @@ int tmdhip_thermostat_apply(int dtype, int64_t nreplicas, int64_t natoms, void *
                             const double *kbar_host, const double *ndof_host, const double *c_host, const double *r1_host,
                             const double *s_host, const int32_t *active_host, int32_t remove_com, double *record_dev,
                             double *partials_dev, void *stream);
+/* Velocity rescaling by one given factor per replica, with its energy book-keeping, stateless (added to ABI 11): the device
+ * half of temperature replica exchange, where replica slots that trade rungs of a temperature ladder have their velocities in
+ * vel_dev [R][natoms][3] scaled by sqrt(T_new / T_old).  factor_host is a HOST array of nreplicas finite factors > 0, read
+ * before the call returns (they travel as kernel arguments, 16 replicas per pair of launches).  For every replica, over the
+ * rows with mass > 0 (rows with mass == 0 are neither read nor written):
+ *   K = (1/2) sum m v^2 (no centre-of-mass term);  v <- factor v, one product in double and one rounding on the store
+ *   (not written at all when factor == 1.0: such a replica is reduced and recorded only).
+ * record_dev is double [R][TMDHIP_EXCHANGE_RECORD_DOUBLES]: {K_before, factor, K_after = factor^2 K, work, applications};
+ * `work` (the sum of K_after - K_before) and `applications` accumulate, so the caller zeroes the record once before the first
+ * application.  partials_dev is scratch, double [R][TMDHIP_EXCHANGE_MAX_BLOCKS]; tmdhip_velocity_rescale_workspace returns
+ * both sizes in doubles.  Sums and record arithmetic in double in both precisions, no atomics: two runs give the same bits. */
+#define TMDHIP_EXCHANGE_RECORD_DOUBLES 5
+#define TMDHIP_EXCHANGE_MAX_BLOCKS 256
+int tmdhip_velocity_rescale_workspace(int64_t nreplicas, int64_t *record_doubles, int64_t *partials_doubles);
+int tmdhip_velocity_rescale(int dtype, int64_t nreplicas, int64_t natoms, void *vel_dev, const void *mass_dev,
+                            const double *factor_host, double *record_dev, double *partials_dev, void *stream);
 /* Fill `out_dev` (real [n]) with the N(0,1) stream used by tmdhip_langevin_second_vv (for tests). */
 int tmdhip_normal_fill(int dtype, int64_t n, void *out_dev, uint64_t seed, uint64_t step, void *stream);
 

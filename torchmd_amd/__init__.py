@@ -4,7 +4,8 @@ Public surface mirrors the reference package for this path:
     torchmd_amd.forces.Forces, torchmd_amd.integrator.Integrator, torchmd_amd.systems.System,
     torchmd_amd.parameters.Parameters, torchmd_amd.forcefields.ForceField
 plus `torchmd_amd.MonteCarloBarostat` (constant pressure) and `torchmd_amd.VelocityRescale` (stochastic velocity
-rescaling, one target temperature per replica); both imported on first use only,
+rescaling, one target temperature per replica) and `torchmd_amd.ReplicaExchange` / `torchmd_amd.temperature_ladder`
+(temperature replica exchange on that thermostat's ladder); all imported on first use only,
 backed by hand-written HIP kernels in `torchmd_amd/lib/libtmdhip.so` (C ABI: include/tmdhip.h).
 """
 
@@ -25,6 +26,10 @@ def __getattr__(name):
         from .thermostat import VelocityRescale
 
         return VelocityRescale
+    if name in ("ReplicaExchange", "temperature_ladder"):
+        from . import exchange
+
+        return getattr(exchange, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 
@@ -33,10 +38,12 @@ __all__ = [
     "Integrator",
     "MonteCarloBarostat",
     "Parameters",
+    "ReplicaExchange",
     "System",
     "VelocityRescale",
     "kinetic_energy",
     "kinetic_to_temp",
     "maxwell_boltzmann",
+    "temperature_ladder",
 ]
 __version__ = "0.1.0"

@@ -268,6 +268,10 @@ THERMOSTAT_RECORD_DOUBLES, THERMOSTAT_MAX_BLOCKS = 8, 256  # TMDHIP_THERMOSTAT_R
 # fields of a thermostat record
 THERMOSTAT_K_BEFORE, THERMOSTAT_ALPHA, THERMOSTAT_K_AFTER, THERMOSTAT_VCM, THERMOSTAT_HEAT, THERMOSTAT_COUNT = range(6)
 
+EXCHANGE_RECORD_DOUBLES, EXCHANGE_MAX_BLOCKS = 5, 256  # TMDHIP_EXCHANGE_RECORD_DOUBLES, TMDHIP_EXCHANGE_MAX_BLOCKS
+# fields of a velocity-rescale (replica exchange) record
+EXCHANGE_K_BEFORE, EXCHANGE_FACTOR, EXCHANGE_K_AFTER, EXCHANGE_WORK, EXCHANGE_COUNT = range(5)
+
 # name -> (restype, argtypes): every symbol include/tmdhip.h declares
 SIGNATURES = {
     "tmdhip_abi_version": (C.c_int, []),
@@ -354,6 +358,11 @@ SIGNATURES = {
         C.c_int,
         [C.c_int, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double),
          C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int32), C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p],
+    ),
+    "tmdhip_velocity_rescale_workspace": (C.c_int, [C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "tmdhip_velocity_rescale": (
+        C.c_int,
+        [C.c_int, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.POINTER(C.c_double), C.c_void_p, C.c_void_p, C.c_void_p],
     ),
     "tmdhip_normal_fill": (C.c_int, [C.c_int, C.c_int64, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p]),
     "tmdhip_dd_step": (

@@ -6,7 +6,8 @@ Mirror of the reference module (`torchmd/integrator.py`): same constants, helper
 "hbonds": also every X-H bond by SHAKE/RATTLE) and an opt-in `barostat` keyword (a
 `barostat.MonteCarloBarostat`: constant pressure) and an opt-in `thermostat` keyword (a
 `thermostat.VelocityRescale`: stochastic velocity rescaling between batches of steps, one target temperature per replica,
-DESIGN §14) that this package adds.  Each iteration is
+DESIGN §14) and an opt-in `exchange` keyword (an `exchange.ReplicaExchange`: temperature replica exchange on the thermostat's
+ladder) that this package adds.  Each iteration is
 
     tmdhip_first_vv  ->  forces.compute  ->  tmdhip_langevin_second_vv | tmdhip_second_vv
 
@@ -129,7 +130,7 @@ def cut_schedules(nstep, niter, frequencies):
 
 class Integrator:
     def __init__(self, systems, forces, timestep, device, gamma=None, T=None, batch=None, constraints=None, barostat=None,
-                 thermostat=None):
+                 thermostat=None, exchange=None):
         self.dt = timestep / TIMEFACTOR
         self.systems = systems
         self.forces = forces
@@ -174,6 +175,9 @@ class Integrator:
             self._init_thermostat(thermostat)
         if barostat is not None:
             barostat.check(systems, forces, temperature=(thermostat.temperature if thermostat is not None else T) or 0)
+        self.exchange = exchange  # exchange.ReplicaExchange
+        if exchange is not None:
+            self._init_exchange(exchange)
 
     def _init_thermostat(self, th):
         """What is refused (ValueError): a second thermostat (Langevin), atom groups, a ladder of the wrong length, a ladder
@@ -192,6 +196,17 @@ class Integrator:
             ndof = 3 * int((self.masses > 0).sum().item())
         th.degrees_of_freedom(ndof)
         self._thermostat_ndof = ndof
+
+    def _init_exchange(self, ex):
+        """What is refused (ValueError): exchange without a `VelocityRescale` that holds a sequence of temperatures (one per
+        replica, strictly increasing), atom groups, a barostat (which knows one temperature)."""
+        if self.batch is not None:
+            raise ValueError("exchange= does not support atom groups (batch=): a replica slot is rescaled as a whole")
+        if self.barostat is not None:
+            raise ValueError("exchange= cannot run under barostat=: the barostat holds one temperature")
+        if int(ex.frequency) != ex.frequency or ex.frequency < 1:
+            raise ValueError("the exchange frequency must be a positive whole number of steps")
+        ex.check(self.thermostat, self.systems.pos.shape[0])
 
     def _init_constraints(self, mode):
         from .constraints import find_constraints
@@ -278,11 +293,14 @@ class Integrator:
         return out
 
     def _step_thermostat(self, lib, s, dev, code, R, N, fast, niter):
-        """`step(niter)` under a rescaling thermostat (and possibly a barostat): segments cut at the union of both schedules,
-        each run as `step` runs it (rewind and replay included); the thermostat is applied after a segment that ended on a
-        multiple of its frequency has returned, before the volume move where both fall on one step.  The kinetic energy
-        returned is that of the velocities as they are left: `K_after` of the record when the call ends on an application."""
+        """`step(niter)` under a rescaling thermostat (and possibly a barostat, or replica exchange): segments cut at the
+        union of the schedules, each run as `step` runs it (rewind and replay included); the thermostat is applied after a
+        segment that ended on a multiple of its frequency has returned, before the volume move or the exchange attempt where
+        both fall on one step.  The kinetic energy returned is that of the velocities as they are left: `K_after` of the
+        record of whatever rescaled them last when the call ends on an application or an attempt."""
         th, baro = self.thermostat, self.barostat
+        if self.exchange is not None:
+            return self._step_exchange(lib, s, dev, code, R, N, fast, niter)
         freqs = (th.frequency,) + ((baro.frequency,) if baro is not None else ())
         out, rescaled = None, False
         for n, hit in cut_schedules(self._nstep, niter, freqs):
@@ -297,6 +315,28 @@ class Integrator:
                 out = (out[0], pot, out[2])
         if rescaled:
             Ekin = th.last[:, L.THERMOSTAT_K_AFTER].cpu().numpy()
+            Ekin = Ekin.astype(np.dtype("float32") if s.pos.dtype == torch.float32 else np.float64)
+            out = (Ekin, out[1], self._temperature(Ekin))
+        return out
+
+    def _step_exchange(self, lib, s, dev, code, R, N, fast, niter):
+        """`_step_thermostat` with replica exchange as one more schedule (no barostat: refused).  Where both fall on one step
+        the thermostat is applied first, then the exchange is attempted with the potential energies the segment returned
+        (positions have not moved since).  A call that ends on an attempt returns the exchange record's `K_after`."""
+        th, ex = self.thermostat, self.exchange
+        out, last = None, None
+        for n, hit in cut_schedules(self._nstep, niter, (th.frequency, ex.frequency)):
+            fused = fast and not self.forces.external
+            out = self._step_body(lib, s, dev, code, R, N, fast, fused, n, replay=False)
+            last = None
+            if hit[0]:
+                th.apply(s, self.masses, self.dt, self._thermostat_ndof)
+                last = th.last[:, L.THERMOSTAT_K_AFTER]
+            if hit[1]:
+                ex.attempt(s, self.masses, th, out[1])
+                last = ex.last[:, L.EXCHANGE_K_AFTER]
+        if last is not None:
+            Ekin = last.cpu().numpy()
             Ekin = Ekin.astype(np.dtype("float32") if s.pos.dtype == torch.float32 else np.float64)
             out = (Ekin, out[1], self._temperature(Ekin))
         return out

@@ -9,13 +9,16 @@ Outputs like the reference (`run.py:230-291`): `monitor_{k}.csv` (iter, ns, epot
 `{output}_{k}.npy` trajectory `[N,3,frames]`, `input.yaml` echo.  Frames are staged through a pinned
 host ring with asynchronous copies instead of a blocking `.cpu()` per period.
 With `barostat_pressure` set (constant pressure) the box edges of every frame are saved as
-`{output}_box_{k}.npy` `[frames,3]` and the monitor file gains a `volume` column.
+`{output}_box_{k}.npy` `[frames,3]` and the monitor file gains a `volume` column.  With `exchange_frequency` set (temperature
+replica exchange on the ladder of `thermostat: csvr`) every monitor file gains a `rung` column — the rung of the
+ladder the replica slot holds at that row — and the acceptance counts are written to `exchange.json` at the end.
 """
 
 from __future__ import annotations
 
 import argparse
 import csv
+import json
 import os
 import time
 
@@ -51,6 +54,8 @@ DEFAULTS = dict(
     thermostat_frequency=10,  # steps between two applications
     thermostat_temperature=None,  # K: a number, or a list with one target per replica; None: `temperature`
     remove_com=True,  # the thermostat also takes out the centre-of-mass motion
+    exchange_frequency=None,  # steps between two replica-exchange attempts; None: none.  Needs thermostat: csvr with a list: DESIGN §16
+    exchange_seed=None,  # seed of the exchange's random stream; None: drawn from torch's generator (so `seed` reproduces it)
     virtual_sites=None,  # None or "tip4p": four-site waters O,H1,H2,M; geometry from the force field's `virtual_sites` section: DESIGN §12
 )
 
@@ -115,6 +120,16 @@ def get_args(arguments=None):
         args.thermostat_temperature = [float(v) for v in args.thermostat_temperature]
     elif args.thermostat_temperature is not None:
         args.thermostat_temperature = float(args.thermostat_temperature)
+    for k in ("exchange_frequency", "exchange_seed"):
+        v = getattr(args, k)
+        if isinstance(v, str) and v.lower() in ("none", "null", ""):
+            v = None
+        setattr(args, k, int(v) if v is not None else None)
+    if args.exchange_frequency is not None:
+        if args.exchange_frequency < 1:
+            raise ValueError(f"exchange_frequency must be a positive number of steps, got {args.exchange_frequency}")
+        if args.thermostat != "csvr" or not isinstance(args.thermostat_temperature, list):
+            raise ValueError("exchange_frequency needs thermostat: csvr with a list as thermostat_temperature (the ladder)")
     if isinstance(args.remove_com, str):
         args.remove_com = args.remove_com.lower() not in ("false", "0", "no", "off")
     args.remove_com = bool(args.remove_com)
@@ -277,7 +292,7 @@ class FrameStager:
 def dynamics(args, mol, system, forces):
     torch.manual_seed(args.seed)
     device = torch.device(args.device)
-    barostat = thermostat = None
+    barostat = thermostat = exchange = None
     if args.thermostat is not None:
         from .thermostat import VelocityRescale
 
@@ -293,6 +308,11 @@ def dynamics(args, mol, system, forces):
                              "thermostat: csvr with a single thermostat_temperature")
         barostat = MonteCarloBarostat(args.barostat_pressure, bath, args.barostat_frequency)
     extra = {} if barostat is None else {"barostat": barostat}
+    thermostat_ladder = list(thermostat.temperatures) if thermostat is not None else []  # (before any exchange permutes it)
+    if args.exchange_frequency is not None:
+        from .exchange import ReplicaExchange
+
+        exchange = extra["exchange"] = ReplicaExchange(args.exchange_frequency, seed=args.exchange_seed)
     if thermostat is not None:
         integrator = Integrator(system, forces, args.timestep, device, constraints=args.constraints, thermostat=thermostat, **extra)
     else:
@@ -302,6 +322,7 @@ def dynamics(args, mol, system, forces):
     nper = args.steps // args.output_period
     stager = FrameStager(system, nper)
     columns = ("iter", "ns", "epot", "ekin", "etot", "T") + (("volume",) if barostat is not None else ())
+    columns += ("rung",) if exchange is not None else ()
     logs = [LogWriter(args.log_dir, columns, name=f"monitor_{k}.csv") for k in range(args.replicas)]
     boxes = []  # [frames][R,3] box edges, constant-pressure runs only
     if args.minimize is not None:
@@ -327,8 +348,16 @@ def dynamics(args, mol, system, forces):
                    "epot": Epot[k], "ekin": float(Ekin[k]), "etot": Epot[k] + float(Ekin[k]), "T": float(T[k])}
             if barostat is not None:
                 row["volume"] = float(np.prod(boxes[-1][k]))
+            if exchange is not None:
+                row["rung"] = int(exchange.rungs[k]) if exchange.rungs is not None else k
             logs[k].write_row(row)
     wall = time.time() - t0
+    if exchange is not None:
+        with open(os.path.join(args.log_dir, "exchange.json"), "w") as fh:
+            none = exchange.rungs is None  # (no attempt was made: the run was shorter than exchange_frequency)
+            json.dump({"frequency": exchange.frequency, "seed": exchange.seed, "temperatures": [float(t) for t in thermostat_ladder],
+                       "attempts": [] if none else exchange.attempts.tolist(), "accepted": [] if none else exchange.accepted.tolist(),
+                       "rungs": list(range(args.replicas)) if none else exchange.rungs.tolist()}, fh)
     print(f"{args.steps} steps in {wall:.2f} s = {args.steps * args.timestep * FS2NS / wall * 86400:.1f} ns/day per replica")
     return stager
 
