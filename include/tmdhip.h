@@ -439,6 +439,49 @@ int tmdhip_thermostat_apply(int dtype, int64_t nreplicas, int64_t natoms, void *
 int tmdhip_velocity_rescale_workspace(int64_t nreplicas, int64_t *record_doubles, int64_t *partials_doubles);
 int tmdhip_velocity_rescale(int dtype, int64_t nreplicas, int64_t natoms, void *vel_dev, const void *mass_dev,
                             const double *factor_host, double *record_dev, double *partials_dev, void *stream);
+/* Harmonic position and distance restraints with one target per replica (added to ABI 11: new symbols only).
+ *   position  d = minimum image of (x - x_ref) in the orthorhombic box (no image along an edge of zero); E = k |d|^2 / 2, F = -k d
+ *   distance  d = minimum image of (x_i - x_j), r = |d|; E = k (r - r0)^2 / 2 (the bond term with k0 = k / 2),
+ *             F_i = -k (r - r0) d / r = -F_j; r = 0: F = 0, E = k r0^2 / 2
+ * k >= 0, and k = 0 switches an entry off for that replica.  All real arrays are double HOST arrays, [R] outermost.
+ * tmdhip_set_restraints validates, builds one row per restrained atom (its position entry, then its distance entries by
+ * restraint index), copies the tables to the device and synchronises; calling it again replaces the tables (how a window's
+ * target is moved between two tmdhip_md_run calls); enable = 0, or no entries, releases everything.  Refused: sizes and indices
+ * out of range, i == j, two position entries for one atom, negative or non-finite k / r0, non-finite references, a restrained
+ * atom that is a virtual site of the context, a context with passive atoms (a brick of the domain decomposition), and, where
+ * masses are seen (tmdhip_restraint_apply with velocities, tmdhip_md_run), a restrained atom without mass.  That check reads
+ * the masses back once per mass array, told by its address, and again after the set of restrained atoms has changed: the
+ * caller must not change the masses of restrained atoms in place afterwards (the kernel leaves the velocity of a row with
+ * mass <= 0 alone and never divides by it).
+ * With restraints in place tmdhip_md_run integrates under the total force: the restraint force never enters the pair or step
+ * kernels; it is applied to the half-step velocities between their launches as the impulse dt a_r(x) / (1 - gamma dt), which
+ * the Langevin and half-kick lines of the step turn into exactly the kicks they would have made with a_r inside the force, and
+ * after the last step of the call a finishing launch adds dt/2 a_r to the velocities and F_r to forces_dev (the forces the call
+ * leaves are total) and sums the restraint energies; tmdhip_md_run fails when 1 - gamma dt <= 0.
+ * One thread per restrained atom, arithmetic in double from positions of either dtype, one rounding on each store, rows of
+ * atoms in no restraint never written, no floating-point atomics: two runs give the same bits. */
+typedef struct tmdhip_restraint_desc {
+  int32_t struct_size; /* = sizeof(tmdhip_restraint_desc) */
+  int32_t enable;
+  int32_t nreplicas;   /* = the context's */
+  int32_t npos, ndist;
+  int32_t reserved;
+  const int32_t *pos_atom_host;  /* [npos] */
+  const double *pos_ref_host;    /* [R][npos][3] */
+  const double *pos_k_host;      /* [R][npos] */
+  const int32_t *dist_pair_host; /* [ndist][2] */
+  const double *dist_r0_host;    /* [R][ndist] */
+  const double *dist_k_host;     /* [R][ndist] */
+} tmdhip_restraint_desc;
+int tmdhip_set_restraints(tmdhip_ctx *ctx, const tmdhip_restraint_desc *desc);
+/* One evaluation of the context's restraints at pos_dev (real [R][N][3], the context's dtype), box_host [R][3].  Whatever is
+ * not NULL is served: forces_dev += F_r; vel_dev += kick F_r / m (needs mass_dev, real [N]); energies_dev (double [R][2]) =
+ * (position, distance) energies, overwritten.  A context without restraints: nothing is launched, energies are zeroed. */
+int tmdhip_restraint_apply(tmdhip_ctx *ctx, const void *pos_dev, const double *box_host, void *forces_dev, void *vel_dev,
+                           const void *mass_dev, double kick, double *energies_dev, void *stream);
+/* The restraint energies of the last step of the last tmdhip_md_run: out_host double [R][2] = (position, distance).  One small
+ * copy and a synchronisation of the stream; zeros without restraints. */
+int tmdhip_restraint_energy(tmdhip_ctx *ctx, double *out_host, void *stream);
 /* Fill `out_dev` (real [n]) with the N(0,1) stream used by tmdhip_langevin_second_vv (for tests). */
 int tmdhip_normal_fill(int dtype, int64_t n, void *out_dev, uint64_t seed, uint64_t step, void *stream);
 

@@ -5,7 +5,8 @@ Public surface mirrors the reference package for this path:
     torchmd_amd.parameters.Parameters, torchmd_amd.forcefields.ForceField
 plus `torchmd_amd.MonteCarloBarostat` (constant pressure) and `torchmd_amd.VelocityRescale` (stochastic velocity
 rescaling, one target temperature per replica) and `torchmd_amd.ReplicaExchange` / `torchmd_amd.temperature_ladder`
-(temperature replica exchange on that thermostat's ladder); all imported on first use only,
+(temperature replica exchange on that thermostat's ladder) and `torchmd_amd.Restraints` (harmonic position and distance
+restraints with one target per replica); all imported on first use only,
 backed by hand-written HIP kernels in `torchmd_amd/lib/libtmdhip.so` (C ABI: include/tmdhip.h).
 """
 
@@ -30,6 +31,10 @@ def __getattr__(name):
         from . import exchange
 
         return getattr(exchange, name)
+    if name == "Restraints":
+        from .restraints import Restraints
+
+        return Restraints
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 
@@ -39,6 +44,7 @@ __all__ = [
     "MonteCarloBarostat",
     "Parameters",
     "ReplicaExchange",
+    "Restraints",
     "System",
     "VelocityRescale",
     "kinetic_energy",

@@ -246,6 +246,23 @@ class VsiteDesc(C.Structure):
     ]
 
 
+class RestraintDesc(C.Structure):
+    _fields_ = [
+        ("struct_size", C.c_int32),
+        ("enable", C.c_int32),
+        ("nreplicas", C.c_int32),
+        ("npos", C.c_int32),
+        ("ndist", C.c_int32),
+        ("reserved", C.c_int32),
+        ("pos_atom_host", C.c_void_p),
+        ("pos_ref_host", C.c_void_p),
+        ("pos_k_host", C.c_void_p),
+        ("dist_pair_host", C.c_void_p),
+        ("dist_r0_host", C.c_void_p),
+        ("dist_k_host", C.c_void_p),
+    ]
+
+
 class FireParams(C.Structure):
     _fields_ = [
         ("struct_size", C.c_int32),
@@ -364,6 +381,12 @@ SIGNATURES = {
         C.c_int,
         [C.c_int, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.POINTER(C.c_double), C.c_void_p, C.c_void_p, C.c_void_p],
     ),
+    "tmdhip_set_restraints": (C.c_int, [C.c_void_p, C.POINTER(RestraintDesc)]),
+    "tmdhip_restraint_apply": (
+        C.c_int,
+        [C.c_void_p, C.c_void_p, C.POINTER(C.c_double), C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p],
+    ),
+    "tmdhip_restraint_energy": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.c_void_p]),
     "tmdhip_normal_fill": (C.c_int, [C.c_int, C.c_int64, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p]),
     "tmdhip_dd_step": (
         C.c_int,

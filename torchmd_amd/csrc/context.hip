@@ -533,6 +533,7 @@ void tmdhip_destroy(tmdhip_ctx *ctx) {
   tmd::pme_release(ctx);
   tmd::cons_release(ctx);
   tmd::vsite_release(ctx);
+  tmd::restraint_release(ctx);
   delete ctx;
 }
 

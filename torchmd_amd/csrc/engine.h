@@ -641,6 +641,8 @@ struct tmdhip_ctx {
   void *cons = nullptr;
   // virtual sites the context's own launches serve (tmdhip_set_vsites), vsite.hip; null: none
   void *vsites = nullptr;
+  // harmonic restraints (tmdhip_set_restraints), restraint.hip; null: off (no launch, nothing allocated)
+  void *restraints = nullptr;
   // timing of the dominant kernel
   bool timing = false;
   int timing_stride = 1;    // every n-th launch is timed
@@ -818,6 +820,19 @@ void launch_cons_step(const tmdhip_ctx *ctx, const MdStepArgs<R> &a, const PairC
                       bool check, int nrep, hipStream_t st);
 // vsite.hip
 void vsite_release(tmdhip_ctx *ctx);
+// restraint.hip (only called with ctx->restraints set, except the release)
+void restraint_release(tmdhip_ctx *ctx);
+// what tmdhip_md_run refuses with restraints; on success *impulse_kick = dt / (1 - gamma dt) (gamma = 0 without Langevin)
+int restraint_run_check(tmdhip_ctx *ctx, const tmdhip_md_desc *d, double *impulse_kick, hipStream_t st);
+// vel += kick F_r(pos) / m for replicas rep0 .. rep0 + nrep - 1, whose rows pos / vel point at; box_host: of replica rep0 on
+int restraint_impulse(tmdhip_ctx *ctx, int rep0, int nrep, const void *pos, const double *box_host, void *vel, const void *mass,
+                      double kick, hipStream_t st);
+// the same for all replicas in one launch per 16, replica r's positions at pos_each[r] (the batched pair + step launch)
+int restraint_impulse_each(tmdhip_ctx *ctx, const void *const *pos_each, const double *box_host, void *vel, const void *mass, double kick,
+                           hipStream_t st);
+// after the last step of a call, all replicas: vel += kick F_r / m, forces += F_r, the context's energies [R][2]
+int restraint_finish(tmdhip_ctx *ctx, const void *pos, const double *box_host, void *vel, void *forces, const void *mass, double kick,
+                     hipStream_t st);
 int64_t pme_evaluations(const tmdhip_ctx *ctx, int r);
 int64_t pme_bytes(const tmdhip_ctx *ctx);
 // md_loop.hip

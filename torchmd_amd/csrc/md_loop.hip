@@ -434,11 +434,15 @@ struct MdRun {
   int batch_bonded = 0;
   int it = 0;
   bool first = true, second = false;
+  // restraints (restraint.hip): the impulse dt / (1 - gamma dt) that stands for a_r in the step that follows a force launch
+  const bool restrained;
+  double impulse_kick = 0;
+  std::vector<const void *> impulse_pos;  // a batched iteration: where each replica's positions live, for ONE impulse launch
 
   MdRun(tmdhip_ctx *ctx_, const tmdhip_md_desc *d_, hipStream_t st_)
       : ctx(ctx_), d(d_), st(st_), n(ctx_->d.natoms), nrep((int)ctx_->rep.size()), stride((size_t)ctx_->d.natoms * 3),
         langevin(d_->vcoeff_dev != nullptr), cur(nrep), owed(nrep, 0), stepped(nrep, 0), finalized(nrep, 0),
-        home_all((R *)d_->pos_dev), bcur((R *)d_->pos_dev) {
+        home_all((R *)d_->pos_dev), bcur((R *)d_->pos_dev), restrained(ctx_->restraints != nullptr) {
     const char *e_min = std::getenv("TMDHIP_DEBUG_CHAIN_MIN_ENTRIES"), *e_near = std::getenv("TMDHIP_DEBUG_CHAIN_NEAR"),
                *e_batch = std::getenv("TMDHIP_BATCH_REPLICAS");
     chain_skip_on = !env_is_zero("TMDHIP_CHAIN_SKIP") && !ctx->no_chain_skip_once;
@@ -483,6 +487,7 @@ struct MdRun {
   }
 
   int run() {
+    if (restrained) TMD_TRY(restraint_run_check(ctx, d, &impulse_kick, st));
     TMD_TRY(snapshot_unless_first_kernel_takes_it());
     for (it = 0; it <= d->niter; ++it) {
       first = it < d->niter;
@@ -503,7 +508,17 @@ struct MdRun {
         if (batching) TMD_TRY(finish_batch());
       }
     }
-    return copy_home();
+    TMD_TRY(copy_home());
+    return restrained ? finish_restraints() : 0;
+  }
+
+  // Restraints, the last step of the call: dt/2 a_r for the velocities, F_r for the caller's forces (total on return, and the
+  // next call's first half kick is right), the restraint energies.  The kinetic energy the last launch summed is stale.
+  int finish_restraints() {
+    TMD_TRY(restraint_finish(ctx, d->pos_dev, d->box_host, d->vel_dev, d->forces_dev, d->mass_dev, 0.5 * d->dt, st));
+    ctx->ke_from_run = nullptr;
+    ctx->run_published_seq = 0;
+    return 0;
   }
 
   int snapshot_unless_first_kernel_takes_it() {
@@ -559,6 +574,8 @@ struct MdRun {
     TMD_HIP(hipGetLastError());
     if (!first) return 0;
     R *pos = bcur;
+    if (restrained && it + 1 < d->niter)
+      TMD_TRY(restraint_impulse(ctx, 0, nrep, pos, d->box_host, d->vel_dev, d->mass_dev, impulse_kick, st));
     int flags_c = TMDHIP_WANT_FORCES;
     double *en = nullptr;
     if (wants_energy()) {
@@ -744,6 +761,15 @@ struct MdRun {
     Replica &rp = s.rp;
     const int r = s.r;
     R *pos = cur[r];
+    // (positions x_{it+1}, velocities v_{it+1/2} on every path: the step behind this launch turns the impulse into a_r's kicks)
+    if (restrained && it + 1 < d->niter) {
+      if (batching) {  // (one launch for all replicas in front of finish_batch's)
+        impulse_pos.resize(nrep);
+        impulse_pos[r] = pos;
+      } else {
+        TMD_TRY(restraint_impulse(ctx, r, 1, pos, s.box, (R *)d->vel_dev + r * stride, d->mass_dev, impulse_kick, st));
+      }
+    }
     int flags_c = TMDHIP_WANT_FORCES;
     double *en = nullptr;
     if (wants_energy()) {
@@ -856,6 +882,8 @@ struct MdRun {
 
   int finish_batch() {
     const bool want_e = wants_energy();
+    if (restrained && it + 1 < d->niter)
+      TMD_TRY(restraint_impulse_each(ctx, impulse_pos.data(), d->box_host, d->vel_dev, d->mass_dev, impulse_kick, st));
     {  // the rebuild chains the host has not left out: one launch per kernel for all of them
       std::vector<int> reps, par;
       std::vector<const float *> ps;

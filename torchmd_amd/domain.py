@@ -607,6 +607,9 @@ class DomainSet:
             raise ValueError("PME electrostatics cannot be domain-decomposed (no distributed FFT)")
         if engine_kwargs.get("virtual_sites") is not None:
             raise ValueError("virtual sites cannot be domain-decomposed (a site and its parents would straddle bricks)")
+        if engine_kwargs.get("restraints") is not None:
+            raise ValueError("restraints cannot be domain-decomposed (a pair's atoms would straddle bricks, and atom indices change "
+                             "at every migration)")
         self.dry = bool(dry)  # CPU tensors, no force engine (DryDomain): the plumbing of an N-rank run without a GPU
         self.grid = BrickGrid(box, world, grid)
         self.device, self.dtype = torch.device(device), dtype

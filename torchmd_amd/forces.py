@@ -223,8 +223,28 @@ class _Engine:
         self.comb = torch.zeros(nreplicas * (L.NENERGY + 1), dtype=torch.float64, device=device)
         self.ebuf = self.comb[: nreplicas * L.NENERGY].view(nreplicas, L.NENERGY)
         self.kebuf = self.comb[nreplicas * L.NENERGY:]
+        self.rbuf = torch.zeros(nreplicas, 2, dtype=torch.float64, device=device)  # restraint energies (position, distance)
+        self._restraint_version = None
         _LIVE_ENGINES.add(self)
         del keep
+
+    def sync_restraints(self, rs):
+        """Upload the tables of a `restraints.Restraints` when this context's copy is older (tmdhip_set_restraints)."""
+        if rs is None or self._restraint_version == (id(rs), rs.version):
+            return
+        if rs.nreplicas != self.nreplicas:
+            raise ValueError(f"restraints were made for {rs.nreplicas} replicas, the positions have {self.nreplicas}")
+        rs.upload(self.lib, self.ctx)
+        self._restraint_version = (id(rs), rs.version)
+
+    def apply_restraints(self, rs, pos, boxes, forces, want_energy):
+        """forces += F_r and / or the restraint energies into `rbuf`, on the current stream (tmdhip_restraint_apply)."""
+        if rs is None or (forces is None and not want_energy):
+            return
+        L.check(self.lib.tmdhip_restraint_apply(self.ctx, C.c_void_p(pos.data_ptr()), boxes.ctypes.data_as(C.POINTER(C.c_double)),
+                                                C.c_void_p(forces.data_ptr()) if forces is not None else C.c_void_p(), C.c_void_p(),
+                                                C.c_void_p(), 0.0, C.c_void_p(self.rbuf.data_ptr()) if want_energy else C.c_void_p(),
+                                                C.c_void_p(torch.cuda.current_stream(pos.device).cuda_stream)), "tmdhip_restraint_apply")
 
     def set_constraints(self, cs):
         """Hand a `constraints.ConstraintSet` to the context (tmdhip_set_constraints); None releases it."""
@@ -320,6 +340,11 @@ class Forces:
                           all see it), then hands every site's force to its parents: the forces returned have zero site
                           rows.  Every (site, parent) pair is excluded.  Not with `explicit_forces=False`, `torch.vmap`,
                           `update_atoms` or the domain decomposition.
+    restraints            a `restraints.Restraints`: harmonic position and distance restraints with one target per replica
+                          (DESIGN §17).  Their forces are added behind the site spread, `compute(returnDetails=True)` reports
+                          a "restraints" entry and the total includes it, and `Integrator.step` integrates under the total
+                          force and returns the total potential energy.  Not under `torch.vmap`, with `batch=`, with the
+                          domain decomposition, or (position restraints) with `barostat=`.
     """
 
     bonded = ["bonds", "angles", "dihedrals", "impropers", "1-4"]
@@ -346,6 +371,7 @@ class Forces:
         pme_order=5,
         pme_grid=None,
         virtual_sites=None,
+        restraints=None,
     ):
         self.par = parameters
         if terms is None:
@@ -424,6 +450,14 @@ class Forces:
                 # a union: nothing changes when the topology excludes the pairs already
                 excl = list(excl) + virtual_sites.exclusion_pairs().tolist()
         self._excl_csr = build_exclusion_csr(self.natoms, excl)
+        self.restraints = restraints
+        if restraints is not None:
+            from .restraints import Restraints
+
+            if not isinstance(restraints, Restraints):
+                raise ValueError("restraints must be a restraints.Restraints")
+            restraints.check(self.natoms, torch.as_tensor(parameters.masses).detach().cpu().double().reshape(-1).numpy(), virtual_sites)
+        self._restraint_energy = None  # [R, 2] (position, distance) of the last synchronous evaluation, host
         self._engines = {}
         self._box_cache = None
         self._ava_idx = None
@@ -559,6 +593,10 @@ class Forces:
         self._box_cache = (weakref.ref(box), box._version, host)
         return host
 
+    def _replica_boxes(self, box, R):
+        hbox = self._host_box(box)
+        return np.ascontiguousarray(np.stack([hbox[min(r, len(hbox) - 1)] for r in range(R)]).astype(np.float64))
+
     def _launch(self, eng, pos, box, forces, want_energy, want_forces, count_pairs=False):
         """Enqueue bonded + nonbonded kernels of every replica on the current stream."""
         lib = eng.lib
@@ -622,6 +660,7 @@ class Forces:
         self._pme_box(self._host_box(box))
         eng = self._engine(p, exact)
         with torch.cuda.device(p.device):
+            eng.sync_restraints(self.restraints)
             eng.place_sites(p)  # first launch (no-op without virtual sites)
             for _ in range(4):
                 self._launch(eng, p, box, forces, want_energy, want_forces, count_pairs)
@@ -631,6 +670,8 @@ class Forces:
                 raise RuntimeError("neighbour list kept overflowing; increase `skin` capacity")
             if want_forces:
                 eng.spread_sites(forces)  # last launch
+            if self.restraints is not None and not count_pairs:
+                eng.apply_restraints(self.restraints, p, self._replica_boxes(box, p.shape[0]), forces if want_forces else None, want_energy)
             if eng.vsites is not None and p.data_ptr() != pos.data_ptr():
                 pos.detach().copy_(p)  # (a non-contiguous `pos` was evaluated through a copy: the sites go back)
         if target is not None:
@@ -663,6 +704,7 @@ class Forces:
         out = np.empty((R, L.NENERGY), dtype=np.float64)
         with torch.cuda.device(p.device):
             stream = C.c_void_p(torch.cuda.current_stream(p.device).cuda_stream)
+            eng.sync_restraints(self.restraints)
             eng.place_sites(p)  # first launch (no-op without virtual sites)
             for _ in range(4):
                 rc = L.check(
@@ -679,6 +721,9 @@ class Forces:
                 raise RuntimeError("neighbour list kept overflowing; increase `skin` capacity")
             if forces is not None:
                 eng.spread_sites(forces)  # last launch
+            if self.restraints is not None:
+                eng.apply_restraints(self.restraints, p, np.ascontiguousarray(boxes, dtype=np.float64), forces, True)
+                self._restraint_energy = eng.rbuf.cpu().numpy()
             if eng.vsites is not None and p.data_ptr() != pos.data_ptr():
                 pos.detach().copy_(p)  # (a non-contiguous `pos` was evaluated through a copy: the sites go back)
         if target is not None:
@@ -696,6 +741,8 @@ class Forces:
         toNumpy=True,
         calculateForces=True,
     ):
+        if self.restraints is not None and _is_batched(pos):
+            raise ValueError("compute() with restraints cannot run under torch.vmap (their targets are per replica of the context)")
         if self.virtual_sites is not None:
             if _is_batched(pos):
                 raise ValueError("compute() with virtual_sites cannot run under torch.vmap (the sites are written into `pos` in place)")
@@ -745,6 +792,9 @@ class Forces:
                 cols[:, k] = ehost[:, slot]
         if ext_ene is not None:
             cols[:, -1] = torch.as_tensor(ext_ene).detach().to("cpu", torch.float64).reshape(nsystems).numpy()
+        if self.restraints is not None:  # (reported, and in the total, only when the keyword was given)
+            names.append("restraints")
+            cols = np.concatenate([cols, self._restraint_energy.sum(axis=1, keepdims=True)], axis=1)
 
         if not returnDetails:
             tot = cols.sum(axis=1)
@@ -790,12 +840,15 @@ class Forces:
     # used by Integrator: no host synchronisation unless energies are requested
     def _compute_async(self, pos, box, forces, want_energy):
         ebuf = self._evaluate(pos, box, forces, want_energy, True)
+        # (the restraint energy travels with the external one: a per-replica term outside the library's eight)
+        extra = self._engine(pos.detach()).rbuf.sum(dim=1) if (want_energy and self.restraints is not None) else None
         if self.external:
             ext_ene, ext_force = self.external.calculate(pos, box)
             forces += ext_force
             if want_energy:
-                return ebuf, torch.as_tensor(ext_ene, device=pos.device).detach().to(torch.float64).reshape(-1)
-        return (ebuf, None) if want_energy else (None, None)
+                ext = torch.as_tensor(ext_ene, device=pos.device).detach().to(torch.float64).reshape(-1)
+                return ebuf, ext if extra is None else ext + extra
+        return (ebuf, extra) if want_energy else (None, None)
 
     def _md_run(self, system, masses, vcoeff, dt, gamma, seed, step0, niter, restore=False, constraints=None):
         """Integrator fast path: `niter` MD steps enqueued by one C call; returns the energy buffer of the
@@ -810,6 +863,7 @@ class Forces:
         eng = self._engine(pos)
         if getattr(eng, "_constraints", None) is not constraints:
             eng.set_constraints(constraints)
+        eng.sync_restraints(self.restraints)
         R = pos.shape[0]
         # the descriptor and the per-replica box array are kept between calls (a 20-step call is short enough for
         # the Python in front of its first launch to show)

@@ -168,8 +168,9 @@ class Integrator:
                              "stepped as part of its rigid water (sites on flexible molecules: Forces.compute only)")
         if constraints is not None:
             self._init_constraints(constraints)
-        self.replays = 0  # batches that were rewound and repeated (list validity failure / step-block time-out)
         self.barostat = barostat  # barostat.MonteCarloBarostat
+        self._check_restraints()
+        self.replays = 0  # batches that were rewound and repeated (list validity failure / step-block time-out)
         self.thermostat = thermostat  # thermostat.VelocityRescale
         if thermostat is not None:
             self._init_thermostat(thermostat)
@@ -178,6 +179,19 @@ class Integrator:
         self.exchange = exchange  # exchange.ReplicaExchange
         if exchange is not None:
             self._init_exchange(exchange)
+
+    def _check_restraints(self):
+        """What is refused with restraints (ValueError): atom groups, whose replicas share one row of positions, and absolute
+        references under a barostat, which do not scale with the box (distance restraints are allowed).  Looked at when the
+        integrator is made and again at every `step`: entries may be added to a `Restraints` at any time."""
+        rs = getattr(self.forces, "restraints", None)
+        if rs is None:
+            return
+        if self.batch is not None:
+            raise ValueError("restraints do not support atom groups (batch=): their targets are per replica")
+        if self.barostat is not None and rs.npos:
+            raise ValueError("position restraints cannot run under barostat=: absolute references do not scale with the box "
+                             "(distance restraints can)")
 
     def _init_thermostat(self, th):
         """What is refused (ValueError): a second thermostat (Langevin), atom groups, a ladder of the wrong length, a ladder
@@ -264,6 +278,7 @@ class Integrator:
         lib = L.load()
         s = self.systems
         self._check_layout()
+        self._check_restraints()
         dev = s.pos.device
         code = L.dtype_code(s.pos.dtype)
         R, N = s.pos.shape[0], s.pos.shape[1]
@@ -404,6 +419,12 @@ class Integrator:
                 raise RuntimeError(_REPLAY_FAILED + L.last_error())
             cols = self.forces.energy_columns()
             tot = obs[:, cols].sum(axis=1) if cols else np.zeros(R)
+            if self.forces.restraints is not None:  # the run's finishing launch has summed them: one small copy
+                er = np.empty((R, 2), dtype=np.float64)
+                L.check(lib.tmdhip_restraint_energy(eng.ctx, er.ctypes.data_as(C.POINTER(C.c_double)), _stream(dev)),
+                        "tmdhip_restraint_energy")
+                self.forces._restraint_energy = er
+                tot = tot + er.sum(axis=1)
             pot = [float(v) for v in tot]
             Ekin = obs[:, L.NENERGY].copy()
             Ekin = Ekin.astype(np.dtype("float32") if s.pos.dtype == torch.float32 else np.float64)
@@ -443,6 +464,9 @@ class Integrator:
                     self.replays += 1
                     return self._step_body(lib, s, dev, code, R, N, fast, fused, niter, replay=True)
                 raise RuntimeError((_REPLAY_FAILED + why) if (fused and replay) else (_LIST_INVALID + ": " + why))
+            if ebuf is not None and getattr(self.forces, "restraints", None) is not None:
+                # (the step-by-step loop: the restraint energies of its last evaluation, as the fused path leaves them)
+                self.forces._restraint_energy = eng.rbuf.cpu().numpy()
         else:
             Ekin = ke.flatten().cpu().numpy()
         Ekin = Ekin.astype(np.dtype("float32") if s.pos.dtype == torch.float32 else np.float64)

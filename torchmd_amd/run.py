@@ -11,7 +11,10 @@ host ring with asynchronous copies instead of a blocking `.
 With `barostat_pressure` set (constant pressure) the box edges of every frame are saved as
 `{output}_box_{k}.npy` `[frames,3]` and the monitor file gains a `volume` column.  With `exchange_frequency` set (temperature
 replica exchange on the ladder of `thermostat: csvr`) every monitor file gains a `rung` column — the rung of the
-ladder the replica slot holds at that row — and the acceptance counts are written to `exchange.json` at the end.
+ladder the replica slot holds at that row — and the acceptance counts are written to `exchange.json` at the end.  With
+`restraints: file.npz` (harmonic position and distance restraints; arrays named as the fields of
+tmdhip_restraint_desc without `_host`, per-replica leading axes optional) every monitor file gains a `restraints` column: the
+restraint energy that `epot` contains.
 """
 
 from __future__ import annotations
@@ -56,6 +59,7 @@ DEFAULTS = dict(
     remove_com=True,  # the thermostat also takes out the centre-of-mass motion
     exchange_frequency=None,  # steps between two replica-exchange attempts; None: none.  Needs thermostat: csvr with a list: DESIGN §16
     exchange_seed=None,  # seed of the exchange's random stream; None: drawn from torch's generator (so `seed` reproduces it)
+    restraints=None,  # None or an .npz file: harmonic position / distance restraints (pos_atom, pos_ref, pos_k, dist_pair, dist_r0, dist_k): DESIGN §17
     virtual_sites=None,  # None or "tip4p": four-site waters O,H1,H2,M; geometry from the force field's `virtual_sites` section: DESIGN §12
 )
 
@@ -130,6 +134,8 @@ def get_args(arguments=None):
             raise ValueError(f"exchange_frequency must be a positive number of steps, got {args.exchange_frequency}")
         if args.thermostat != "csvr" or not isinstance(args.thermostat_temperature, list):
             raise ValueError("exchange_frequency needs thermostat: csvr with a list as thermostat_temperature (the ladder)")
+    if isinstance(args.restraints, str) and args.restraints.lower() in ("none", "null", ""):
+        args.restraints = None
     if isinstance(args.remove_com, str):
         args.remove_com = args.remove_com.lower() not in ("false", "0", "no", "off")
     args.remove_com = bool(args.remove_com)
@@ -240,6 +246,10 @@ def setup(args):
         vel[:, torch.as_tensor(vsites.sites, dtype=torch.long)] = 0.0  # (massless: the draw divided by zero)
     system.set_velocities(vel)
     extra = {} if vsites is None else {"virtual_sites": vsites}
+    if args.restraints is not None:
+        from .restraints import Restraints
+
+        extra["restraints"] = Restraints.from_npz(args.restraints, args.replicas)
     forces = Forces(parameters, terms=terms, external=external, cutoff=args.cutoff, rfa=args.rfa,
                     switch_dist=args.switch_dist, exclusions=tuple(args.exclusions), pme=args.pme,
                     ewald_tolerance=args.ewald_tolerance, pme_order=args.pme_order, pme_grid=args.pme_grid, **extra)
@@ -323,6 +333,8 @@ def dynamics(args, mol, system, forces):
     stager = FrameStager(system, nper)
     columns = ("iter", "ns", "epot", "ekin", "etot", "T") + (("volume",) if barostat is not None else ())
     columns += ("rung",) if exchange is not None else ()
+    restrained = getattr(forces, "restraints", None) is not None
+    columns += ("restraints",) if restrained else ()
     logs = [LogWriter(args.log_dir, columns, name=f"monitor_{k}.csv") for k in range(args.replicas)]
     boxes = []  # [frames][R,3] box edges, constant-pressure runs only
     if args.minimize is not None:
@@ -350,6 +362,8 @@ def dynamics(args, mol, system, forces):
                 row["volume"] = float(np.prod(boxes[-1][k]))
             if exchange is not None:
                 row["rung"] = int(exchange.rungs[k]) if exchange.rungs is not None else k
+            if restrained:  # the restraint energy inside `epot`, as of the last evaluation
+                row["restraints"] = float(forces._restraint_energy[k].sum())
             logs[k].write_row(row)
     wall = time.time() - t0
     if exchange is not None:
