@@ -482,6 +482,56 @@ int tmdhip_restraint_apply(tmdhip_ctx *ctx, const void *pos_dev, const double *b
 /* The restraint energies of the last step of the last tmdhip_md_run: out_host double [R][2] = (position, distance).  One small
  * copy and a synchronisation of the stream; zeros without restraints. */
 int tmdhip_restraint_energy(tmdhip_ctx *ctx, double *out_host, void *stream);
+/* Well-tempered metadynamics on one or two collective variables (added to ABI 11: new symbols only).
+ *   CVs       kind 0, distance: r = |minimum image of (x_i - x_j)| (atoms[c][0..1]), not periodic, grid [grid_min, grid_max];
+ *             kind 1, dihedral: the torsion of atoms[c][0..3] in radians with the sign of the bonded term, from the
+ *             minimum-imaged bond vectors, periodic on [-pi, pi) (grid_min / grid_max are not read)
+ *   grid      node k of CV c at lo + k h, h = (hi - lo) / bins; bins + 1 nodes (bins on a periodic CV); a node holds the
+ *             analytic sum of the deposited Gaussians and its derivatives, (V, V') or (V, d1 V, d2 V, d1 d2 V), double, the
+ *             second CV's index fastest; one grid per replica, or one for all (shared = 1: multiple walkers)
+ *   bias      the cubic / bicubic Hermite interpolant of the node values; outside a non-periodic grid the CV is clamped for the
+ *             lookup (V constant, no force); F = -dV/ds . ds/dx, the exact derivative of the energy reported
+ *   hill      every node += w exp(-sum_c Delta_c^2 / 2 sigma_c^2) and its derivatives (Delta = node - s0, the minimum image on
+ *             a periodic CV), no truncation; w = height, or height exp(-V(s0) / kdt) with V(s0) read before the deposition
+ * tmdhip_set_metadynamics validates, allocates the zeroed grid(s) and synchronises; calling it again starts from a zeroed grid;
+ * enable = 0 releases everything.  Refused: a bad struct size, ncv outside 1..2, an unknown kind, indices out of range, an
+ * atom repeated within a CV, non-finite or non-positive sigma, bins < 1, grid_min >= grid_max, a spacing h > sigma / 2, a CV
+ * atom that is a virtual site of the context, a context with passive atoms, a wrong nreplicas and, where masses are seen
+ * (tmdhip_metad_apply with velocities, tmdhip_md_run), a CV atom without mass (one read-back per mass array, as for restraints).
+ * With a bias in place tmdhip_md_run integrates under the total force exactly as it does with restraints: the impulse
+ * dt a_b(x) / (1 - gamma dt) on the half-step velocities between the step launches, a finishing launch (dt/2 a_b, forces_dev
+ * += F_b, the bias energy and the CVs) after the last step; it fails when 1 - gamma dt <= 0.  The grid is static during a call.
+ * One wave per replica, one thread per distinct CV atom, double arithmetic, one rounding on each store, no floating-point
+ * atomics anywhere (a deposition has one writer per node; shared walkers add their hills in replica order). */
+typedef struct tmdhip_metad_desc {
+  int32_t struct_size; /* = sizeof(tmdhip_metad_desc) */
+  int32_t enable;
+  int32_t nreplicas;   /* = the context's */
+  int32_t ncv;         /* 1 or 2 */
+  int32_t shared;      /* 0: one grid per replica; 1: one grid, every replica deposits into it */
+  int32_t reserved;
+  int32_t kind[2];
+  int32_t atoms[2][4];
+  int32_t bins[2];
+  double grid_min[2], grid_max[2], sigma[2];
+} tmdhip_metad_desc;
+int tmdhip_set_metadynamics(tmdhip_ctx *ctx, const tmdhip_metad_desc *desc);
+/* One evaluation of the bias at pos_dev (real [R][N][3], the context's dtype), box_host [R][3].  Whatever is not NULL is
+ * served: forces_dev += F_b; vel_dev += kick F_b / m (needs mass_dev, real [N]); out_dev (double [R][3]) = (V, s_0, s_1),
+ * overwritten.  A context without metadynamics: nothing is launched, out_dev is zeroed. */
+int tmdhip_metad_apply(tmdhip_ctx *ctx, const void *pos_dev, const double *box_host, void *forces_dev, void *vel_dev,
+                       const void *mass_dev, double kick, double *out_dev, void *stream);
+/* One deposition at the CV values of pos_dev, two launches and no synchronisation: log_row_dev (double [R][ncv + 1], a row of
+ * the caller's hills log on the device) = (s0..., w) per replica, all heights from the grid as it is, then every node of every
+ * grid adds its hill(s).  plain != 0: w = height; otherwise w = height exp(-V(s0) / kdt), kdt = k_B (bias_factor - 1) T. */
+int tmdhip_metad_deposit(tmdhip_ctx *ctx, const void *pos_dev, const double *box_host, double height, double kdt, int plain,
+                         double *log_row_dev, void *stream);
+/* (V, s_0, s_1) of the last step of the last tmdhip_md_run: out_host double [R][3].  One small copy and a synchronisation of the
+ * stream; zeros without metadynamics. */
+int tmdhip_metad_energy(tmdhip_ctx *ctx, double *out_host, void *stream);
+/* Host copies of the grid(s), for restart and inspection: `count` doubles = grids x nodes x (2 or 4); they synchronise. */
+int tmdhip_metad_get_grid(tmdhip_ctx *ctx, double *out_host, int64_t count);
+int tmdhip_metad_set_grid(tmdhip_ctx *ctx, const double *in_host, int64_t count);
 /* Fill `out_dev` (real [n]) with the N(0,1) stream used by tmdhip_langevin_second_vv (for tests). */
 int tmdhip_normal_fill(int dtype, int64_t n, void *out_dev, uint64_t seed, uint64_t step, void *stream);
 

@@ -6,7 +6,8 @@ Public surface mirrors the reference package for this path:
 plus `torchmd_amd.MonteCarloBarostat` (constant pressure) and `torchmd_amd.VelocityRescale` (stochastic velocity
 rescaling, one target temperature per replica) and `torchmd_amd.ReplicaExchange` / `torchmd_amd.temperature_ladder`
 (temperature replica exchange on that thermostat's ladder) and `torchmd_amd.Restraints` (harmonic position and distance
-restraints with one target per replica); all imported on first use only,
+restraints with one target per replica) and `torchmd_amd.Metadynamics` (well-tempered metadynamics on distance and
+dihedral collective variables); all imported on first use only,
 backed by hand-written HIP kernels in `torchmd_amd/lib/libtmdhip.so` (C ABI: include/tmdhip.h).
 """
 
@@ -35,12 +36,17 @@ def __getattr__(name):
         from .restraints import Restraints
 
         return Restraints
+    if name == "Metadynamics":
+        from .metadynamics import Metadynamics
+
+        return Metadynamics
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 
 __all__ = [
     "Forces",
     "Integrator",
+    "Metadynamics",
     "MonteCarloBarostat",
     "Parameters",
     "ReplicaExchange",

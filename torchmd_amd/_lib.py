@@ -263,6 +263,23 @@ class RestraintDesc(C.Structure):
     ]
 
 
+class MetadDesc(C.Structure):
+    _fields_ = [
+        ("struct_size", C.c_int32),
+        ("enable", C.c_int32),
+        ("nreplicas", C.c_int32),
+        ("ncv", C.c_int32),
+        ("shared", C.c_int32),
+        ("reserved", C.c_int32),
+        ("kind", C.c_int32 * 2),
+        ("atoms", (C.c_int32 * 4) * 2),
+        ("bins", C.c_int32 * 2),
+        ("grid_min", C.c_double * 2),
+        ("grid_max", C.c_double * 2),
+        ("sigma", C.c_double * 2),
+    ]
+
+
 class FireParams(C.Structure):
     _fields_ = [
         ("struct_size", C.c_int32),
@@ -387,6 +404,18 @@ SIGNATURES = {
         [C.c_void_p, C.c_void_p, C.POINTER(C.c_double), C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p],
     ),
     "tmdhip_restraint_energy": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.c_void_p]),
+    "tmdhip_set_metadynamics": (C.c_int, [C.c_void_p, C.POINTER(MetadDesc)]),
+    "tmdhip_metad_apply": (
+        C.c_int,
+        [C.c_void_p, C.c_void_p, C.POINTER(C.c_double), C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p],
+    ),
+    "tmdhip_metad_deposit": (
+        C.c_int,
+        [C.c_void_p, C.c_void_p, C.POINTER(C.c_double), C.c_double, C.c_double, C.c_int, C.c_void_p, C.c_void_p],
+    ),
+    "tmdhip_metad_energy": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.c_void_p]),
+    "tmdhip_metad_get_grid": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.c_int64]),
+    "tmdhip_metad_set_grid": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.c_int64]),
     "tmdhip_normal_fill": (C.c_int, [C.c_int, C.c_int64, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p]),
     "tmdhip_dd_step": (
         C.c_int,

@@ -534,6 +534,7 @@ void tmdhip_destroy(tmdhip_ctx *ctx) {
   tmd::cons_release(ctx);
   tmd::vsite_release(ctx);
   tmd::restraint_release(ctx);
+  tmd::metad_release(ctx);
   delete ctx;
 }
 

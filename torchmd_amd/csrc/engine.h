@@ -643,6 +643,8 @@ struct tmdhip_ctx {
   void *vsites = nullptr;
   // harmonic restraints (tmdhip_set_restraints), restraint.hip; null: off (no launch, nothing allocated)
   void *restraints = nullptr;
+  // the metadynamics bias (tmdhip_set_metadynamics), metad.hip; null: off (no launch, nothing allocated)
+  void *metad = nullptr;
   // timing of the dominant kernel
   bool timing = false;
   int timing_stride = 1;    // every n-th launch is timed
@@ -833,6 +835,15 @@ int restraint_impulse_each(tmdhip_ctx *ctx, const void *const *pos_each, const d
 // after the last step of a call, all replicas: vel += kick F_r / m, forces += F_r, the context's energies [R][2]
 int restraint_finish(tmdhip_ctx *ctx, const void *pos, const double *box_host, void *vel, void *forces, const void *mass, double kick,
                      hipStream_t st);
+// metad.hip (only called with ctx->metad set, except the release): the same four places, for the metadynamics bias
+void metad_release(tmdhip_ctx *ctx);
+int metad_run_check(tmdhip_ctx *ctx, const tmdhip_md_desc *d, double *impulse_kick, hipStream_t st);
+int metad_impulse(tmdhip_ctx *ctx, int rep0, int nrep, const void *pos, const double *box_host, void *vel, const void *mass, double kick,
+                  hipStream_t st);
+int metad_impulse_each(tmdhip_ctx *ctx, const void *const *pos_each, const double *box_host, void *vel, const void *mass, double kick,
+                       hipStream_t st);
+int metad_finish(tmdhip_ctx *ctx, const void *pos, const double *box_host, void *vel, void *forces, const void *mass, double kick,
+                 hipStream_t st);
 int64_t pme_evaluations(const tmdhip_ctx *ctx, int r);
 int64_t pme_bytes(const tmdhip_ctx *ctx);
 // md_loop.hip

@@ -436,13 +436,14 @@ struct MdRun {
   bool first = true, second = false;
   // restraints (restraint.hip): the impulse dt / (1 - gamma dt) that stands for a_r in the step that follows a force launch
   const bool restrained;
+  const bool biased;  // the metadynamics bias (metad.hip): the same impulse, a launch of its own
   double impulse_kick = 0;
   std::vector<const void *> impulse_pos;  // a batched iteration: where each replica's positions live, for ONE impulse launch
 
   MdRun(tmdhip_ctx *ctx_, const tmdhip_md_desc *d_, hipStream_t st_)
       : ctx(ctx_), d(d_), st(st_), n(ctx_->d.natoms), nrep((int)ctx_->rep.size()), stride((size_t)ctx_->d.natoms * 3),
         langevin(d_->vcoeff_dev != nullptr), cur(nrep), owed(nrep, 0), stepped(nrep, 0), finalized(nrep, 0),
-        home_all((R *)d_->pos_dev), bcur((R *)d_->pos_dev), restrained(ctx_->restraints != nullptr) {
+        home_all((R *)d_->pos_dev), bcur((R *)d_->pos_dev), restrained(ctx_->restraints != nullptr), biased(ctx_->metad != nullptr) {
     const char *e_min = std::getenv("TMDHIP_DEBUG_CHAIN_MIN_ENTRIES"), *e_near = std::getenv("TMDHIP_DEBUG_CHAIN_NEAR"),
                *e_batch = std::getenv("TMDHIP_BATCH_REPLICAS");
     chain_skip_on = !env_is_zero("TMDHIP_CHAIN_SKIP") && !ctx->no_chain_skip_once;
@@ -488,6 +489,7 @@ struct MdRun {
 
   int run() {
     if (restrained) TMD_TRY(restraint_run_check(ctx, d, &impulse_kick, st));
+    if (biased) TMD_TRY(metad_run_check(ctx, d, &impulse_kick, st));
     TMD_TRY(snapshot_unless_first_kernel_takes_it());
     for (it = 0; it <= d->niter; ++it) {
       first = it < d->niter;
@@ -509,13 +511,22 @@ struct MdRun {
       }
     }
     TMD_TRY(copy_home());
-    return restrained ? finish_restraints() : 0;
+    if (restrained) TMD_TRY(finish_restraints());
+    return biased ? finish_metad() : 0;
   }
 
   // Restraints, the last step of the call: dt/2 a_r for the velocities, F_r for the caller's forces (total on return, and the
   // next call's first half kick is right), the restraint energies.  The kinetic energy the last launch summed is stale.
   int finish_restraints() {
     TMD_TRY(restraint_finish(ctx, d->pos_dev, d->box_host, d->vel_dev, d->forces_dev, d->mass_dev, 0.5 * d->dt, st));
+    ctx->ke_from_run = nullptr;
+    ctx->run_published_seq = 0;
+    return 0;
+  }
+
+  // The metadynamics bias, the last step of the call: the same three things (metad.hip)
+  int finish_metad() {
+    TMD_TRY(metad_finish(ctx, d->pos_dev, d->box_host, d->vel_dev, d->forces_dev, d->mass_dev, 0.5 * d->dt, st));
     ctx->ke_from_run = nullptr;
     ctx->run_published_seq = 0;
     return 0;
@@ -576,6 +587,7 @@ struct MdRun {
     R *pos = bcur;
     if (restrained && it + 1 < d->niter)
       TMD_TRY(restraint_impulse(ctx, 0, nrep, pos, d->box_host, d->vel_dev, d->mass_dev, impulse_kick, st));
+    if (biased && it + 1 < d->niter) TMD_TRY(metad_impulse(ctx, 0, nrep, pos, d->box_host, d->vel_dev, d->mass_dev, impulse_kick, st));
     int flags_c = TMDHIP_WANT_FORCES;
     double *en = nullptr;
     if (wants_energy()) {
@@ -762,12 +774,13 @@ struct MdRun {
     const int r = s.r;
     R *pos = cur[r];
     // (positions x_{it+1}, velocities v_{it+1/2} on every path: the step behind this launch turns the impulse into a_r's kicks)
-    if (restrained && it + 1 < d->niter) {
+    if ((restrained || biased) && it + 1 < d->niter) {
       if (batching) {  // (one launch for all replicas in front of finish_batch's)
         impulse_pos.resize(nrep);
         impulse_pos[r] = pos;
       } else {
-        TMD_TRY(restraint_impulse(ctx, r, 1, pos, s.box, (R *)d->vel_dev + r * stride, d->mass_dev, impulse_kick, st));
+        if (restrained) TMD_TRY(restraint_impulse(ctx, r, 1, pos, s.box, (R *)d->vel_dev + r * stride, d->mass_dev, impulse_kick, st));
+        if (biased) TMD_TRY(metad_impulse(ctx, r, 1, pos, s.box, (R *)d->vel_dev + r * stride, d->mass_dev, impulse_kick, st));
       }
     }
     int flags_c = TMDHIP_WANT_FORCES;
@@ -884,6 +897,8 @@ struct MdRun {
     const bool want_e = wants_energy();
     if (restrained && it + 1 < d->niter)
       TMD_TRY(restraint_impulse_each(ctx, impulse_pos.data(), d->box_host, d->vel_dev, d->mass_dev, impulse_kick, st));
+    if (biased && it + 1 < d->niter)
+      TMD_TRY(metad_impulse_each(ctx, impulse_pos.data(), d->box_host, d->vel_dev, d->mass_dev, impulse_kick, st));
     {  // the rebuild chains the host has not left out: one launch per kernel for all of them
       std::vector<int> reps, par;
       std::vector<const float *> ps;

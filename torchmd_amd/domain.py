@@ -610,6 +610,9 @@ class DomainSet:
         if engine_kwargs.get("restraints") is not None:
             raise ValueError("restraints cannot be domain-decomposed (a pair's atoms would straddle bricks, and atom indices change "
                              "at every migration)")
+        if engine_kwargs.get("metadynamics") is not None:
+            raise ValueError("metadynamics cannot be domain-decomposed (a CV's atoms would straddle bricks, and atom indices change "
+                             "at every migration)")
         self.dry = bool(dry)  # CPU tensors, no force engine (DryDomain): the plumbing of an N-rank run without a GPU
         self.grid = BrickGrid(box, world, grid)
         self.device, self.dtype = torch.device(device), dtype

@@ -225,6 +225,7 @@ class _Engine:
         self.kebuf = self.comb[nreplicas * L.NENERGY:]
         self.rbuf = torch.zeros(nreplicas, 2, dtype=torch.float64, device=device)  # restraint energies (position, distance)
         self._restraint_version = None
+        self.mbuf = torch.zeros(nreplicas, 3, dtype=torch.float64, device=device)  # metadynamics: (V, s_0, s_1) per replica
         _LIVE_ENGINES.add(self)
         del keep
 
@@ -245,6 +246,15 @@ class _Engine:
                                                 C.c_void_p(forces.data_ptr()) if forces is not None else C.c_void_p(), C.c_void_p(),
                                                 C.c_void_p(), 0.0, C.c_void_p(self.rbuf.data_ptr()) if want_energy else C.c_void_p(),
                                                 C.c_void_p(torch.cuda.current_stream(pos.device).cuda_stream)), "tmdhip_restraint_apply")
+
+    def apply_metad(self, md, pos, boxes, forces, want_energy):
+        """forces += F_b and / or (V, CVs) into `mbuf`, on the current stream (tmdhip_metad_apply)."""
+        if md is None or (forces is None and not want_energy):
+            return
+        L.check(self.lib.tmdhip_metad_apply(self.ctx, C.c_void_p(pos.data_ptr()), boxes.ctypes.data_as(C.POINTER(C.c_double)),
+                                            C.c_void_p(forces.data_ptr()) if forces is not None else C.c_void_p(), C.c_void_p(),
+                                            C.c_void_p(), 0.0, C.c_void_p(self.mbuf.data_ptr()) if want_energy else C.c_void_p(),
+                                            C.c_void_p(torch.cuda.current_stream(pos.device).cuda_stream)), "tmdhip_metad_apply")
 
     def set_constraints(self, cs):
         """Hand a `constraints.ConstraintSet` to the context (tmdhip_set_constraints); None releases it."""
@@ -345,6 +355,11 @@ class Forces:
                           a "restraints" entry and the total includes it, and `Integrator.step` integrates under the total
                           force and returns the total potential energy.  Not under `torch.vmap`, with `batch=`, with the
                           domain decomposition, or (position restraints) with `barostat=`.
+    metadynamics          a `metadynamics.Metadynamics`: a history-dependent bias on one or two collective variables
+                          (DESIGN §18).  Its force is added behind the restraints', `compute(returnDetails=True)` reports a
+                          "metadynamics" entry and the total includes it, and `Integrator.step` integrates under the total
+                          force and deposits a hill every `frequency` steps.  Not under `torch.vmap`, with `batch=`,
+                          `barostat=`, `exchange=` or the domain decomposition.
     """
 
     bonded = ["bonds", "angles", "dihedrals", "impropers", "1-4"]
@@ -371,6 +386,7 @@ class Forces:
         pme_order=5,
         pme_grid=None,
         virtual_sites=None,
+        metadynamics=None,
         restraints=None,
     ):
         self.par = parameters
@@ -458,6 +474,14 @@ class Forces:
                 raise ValueError("restraints must be a restraints.Restraints")
             restraints.check(self.natoms, torch.as_tensor(parameters.masses).detach().cpu().double().reshape(-1).numpy(), virtual_sites)
         self._restraint_energy = None  # [R, 2] (position, distance) of the last synchronous evaluation, host
+        self.metadynamics = metadynamics
+        if metadynamics is not None:
+            from .metadynamics import Metadynamics
+
+            if not isinstance(metadynamics, Metadynamics):
+                raise ValueError("metadynamics must be a metadynamics.Metadynamics")
+            metadynamics.check(self.natoms, torch.as_tensor(parameters.masses).detach().cpu().double().reshape(-1).numpy(), virtual_sites)
+            metadynamics._forces = self
         self._engines = {}
         self._box_cache = None
         self._ava_idx = None
@@ -523,6 +547,8 @@ class Forces:
 
     def close(self):
         """Release the device contexts (they are re-created on the next compute())."""
+        if getattr(self, "metadynamics", None) is not None:
+            self.metadynamics.detach()  # (its grid lives in one of the contexts: read it back first)
         for eng in self._engines.values():
             eng.close()
         self._engines = {}
@@ -661,6 +687,8 @@ class Forces:
         eng = self._engine(p, exact)
         with torch.cuda.device(p.device):
             eng.sync_restraints(self.restraints)
+            if self.metadynamics is not None:
+                self.metadynamics.sync(eng)
             eng.place_sites(p)  # first launch (no-op without virtual sites)
             for _ in range(4):
                 self._launch(eng, p, box, forces, want_energy, want_forces, count_pairs)
@@ -672,6 +700,8 @@ class Forces:
                 eng.spread_sites(forces)  # last launch
             if self.restraints is not None and not count_pairs:
                 eng.apply_restraints(self.restraints, p, self._replica_boxes(box, p.shape[0]), forces if want_forces else None, want_energy)
+            if self.metadynamics is not None and not count_pairs:
+                eng.apply_metad(self.metadynamics, p, self._replica_boxes(box, p.shape[0]), forces if want_forces else None, want_energy)
             if eng.vsites is not None and p.data_ptr() != pos.data_ptr():
                 pos.detach().copy_(p)  # (a non-contiguous `pos` was evaluated through a copy: the sites go back)
         if target is not None:
@@ -705,6 +735,8 @@ class Forces:
         with torch.cuda.device(p.device):
             stream = C.c_void_p(torch.cuda.current_stream(p.device).cuda_stream)
             eng.sync_restraints(self.restraints)
+            if self.metadynamics is not None:
+                self.metadynamics.sync(eng)
             eng.place_sites(p)  # first launch (no-op without virtual sites)
             for _ in range(4):
                 rc = L.check(
@@ -724,6 +756,9 @@ class Forces:
             if self.restraints is not None:
                 eng.apply_restraints(self.restraints, p, np.ascontiguousarray(boxes, dtype=np.float64), forces, True)
                 self._restraint_energy = eng.rbuf.cpu().numpy()
+            if self.metadynamics is not None:
+                eng.apply_metad(self.metadynamics, p, np.ascontiguousarray(boxes, dtype=np.float64), forces, True)
+                self.metadynamics.report(eng.mbuf.cpu().numpy())
             if eng.vsites is not None and p.data_ptr() != pos.data_ptr():
                 pos.detach().copy_(p)  # (a non-contiguous `pos` was evaluated through a copy: the sites go back)
         if target is not None:
@@ -743,6 +778,8 @@ class Forces:
     ):
         if self.restraints is not None and _is_batched(pos):
             raise ValueError("compute() with restraints cannot run under torch.vmap (their targets are per replica of the context)")
+        if self.metadynamics is not None and _is_batched(pos):
+            raise ValueError("compute() with metadynamics cannot run under torch.vmap (its grids are per replica of the context)")
         if self.virtual_sites is not None:
             if _is_batched(pos):
                 raise ValueError("compute() with virtual_sites cannot run under torch.vmap (the sites are written into `pos` in place)")
@@ -795,6 +832,9 @@ class Forces:
         if self.restraints is not None:  # (reported, and in the total, only when the keyword was given)
             names.append("restraints")
             cols = np.concatenate([cols, self._restraint_energy.sum(axis=1, keepdims=True)], axis=1)
+        if self.metadynamics is not None:
+            names.append("metadynamics")
+            cols = np.concatenate([cols, self.metadynamics.energy.reshape(-1, 1)], axis=1)
 
         if not returnDetails:
             tot = cols.sum(axis=1)
@@ -842,6 +882,9 @@ class Forces:
         ebuf = self._evaluate(pos, box, forces, want_energy, True)
         # (the restraint energy travels with the external one: a per-replica term outside the library's eight)
         extra = self._engine(pos.detach()).rbuf.sum(dim=1) if (want_energy and self.restraints is not None) else None
+        if want_energy and self.metadynamics is not None:
+            vb = self._engine(pos.detach()).mbuf[:, 0]
+            extra = vb if extra is None else extra + vb
         if self.external:
             ext_ene, ext_force = self.external.calculate(pos, box)
             forces += ext_force
@@ -864,6 +907,8 @@ class Forces:
         if getattr(eng, "_constraints", None) is not constraints:
             eng.set_constraints(constraints)
         eng.sync_restraints(self.restraints)
+        if self.metadynamics is not None:
+            self.metadynamics.sync(eng)
         R = pos.shape[0]
         # the descriptor and the per-replica box array are kept between calls (a 20-step call is short enough for
         # the Python in front of its first launch to show)

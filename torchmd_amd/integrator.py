@@ -179,6 +179,22 @@ class Integrator:
         self.exchange = exchange  # exchange.ReplicaExchange
         if exchange is not None:
             self._init_exchange(exchange)
+        self._check_metadynamics()
+
+    def _check_metadynamics(self):
+        """What is refused with a metadynamics bias (ValueError): atom groups, a barostat (the distance grid does not scale
+        with the box) and replica exchange (the bias would have to travel with the rung)."""
+        md = getattr(self.forces, "metadynamics", None)
+        if md is None:
+            return
+        if self.batch is not None:
+            raise ValueError("metadynamics does not support atom groups (batch=): its grids are per replica")
+        if self.barostat is not None:
+            raise ValueError("metadynamics cannot run under barostat=")
+        if self.exchange is not None:
+            raise ValueError("metadynamics cannot run under exchange=: the bias would have to travel with the rung")
+        if md.nreplicas != self.systems.pos.shape[0]:
+            raise ValueError(f"the metadynamics bias was made for {md.nreplicas} replicas, the systems have {self.systems.pos.shape[0]}")
 
     def _check_restraints(self):
         """What is refused with restraints (ValueError): atom groups, whose replicas share one row of positions, and absolute
@@ -279,6 +295,7 @@ class Integrator:
         s = self.systems
         self._check_layout()
         self._check_restraints()
+        self._check_metadynamics()
         dev = s.pos.device
         code = L.dtype_code(s.pos.dtype)
         R, N = s.pos.shape[0], s.pos.shape[1]
@@ -291,6 +308,8 @@ class Integrator:
                 return self._step_thermostat(lib, s, dev, code, R, N, fast, niter)
             if self.barostat is not None and niter > 0:
                 return self._step_npt(lib, s, dev, code, R, N, fast, niter)
+            if getattr(self.forces, "metadynamics", None) is not None and niter > 0:
+                return self._step_metad(lib, s, dev, code, R, N, fast, niter)
             return self._step_body(lib, s, dev, code, R, N, fast, fused, niter, replay=False)
 
     def _step_npt(self, lib, s, dev, code, R, N, fast, niter):
@@ -307,6 +326,20 @@ class Integrator:
                 out = (out[0], pot, out[2])
         return out
 
+    def _step_metad(self, lib, s, dev, code, R, N, fast, niter):
+        """`step(niter)` under a metadynamics bias: segments that end on multiples of its frequency (counted over the
+        integrator's life), each run as `step` runs it (the grid is static inside a segment, so rewind and replay need nothing
+        new), and a deposition after every segment that ends on a multiple.  The potential energy returned contains V(s(x)) as
+        of before the deposition, and `systems.forces` stay as the finishing launch left them: a Gaussian is flat at its own
+        centre."""
+        md, out = self.forces.metadynamics, None
+        for n, hit in cut_segments(self._nstep, niter, md.frequency):
+            fused = fast and not self.forces.external
+            out = self._step_body(lib, s, dev, code, R, N, fast, fused, n, replay=False)
+            if hit and not md.frozen:
+                md.deposit(s)
+        return out
+
     def _step_thermostat(self, lib, s, dev, code, R, N, fast, niter):
         """`step(niter)` under a rescaling thermostat (and possibly a barostat, or replica exchange): segments cut at the
         union of the schedules, each run as `step` runs it (rewind and replay included); the thermostat is applied after a
@@ -316,7 +349,8 @@ class Integrator:
         th, baro = self.thermostat, self.barostat
         if self.exchange is not None:
             return self._step_exchange(lib, s, dev, code, R, N, fast, niter)
-        freqs = (th.frequency,) + ((baro.frequency,) if baro is not None else ())
+        md = getattr(self.forces, "metadynamics", None)  # (never with a barostat: refused)
+        freqs = (th.frequency,) + ((baro.frequency,) if baro is not None else ()) + ((md.frequency,) if md is not None else ())
         out, rescaled = None, False
         for n, hit in cut_schedules(self._nstep, niter, freqs):
             fused = fast and not self.forces.external
@@ -328,6 +362,8 @@ class Integrator:
                 rec = baro.attempt(s, self.forces, out[1])
                 pot = [float(un if ok else u) for u, un, ok in zip(rec["U"], rec["U_new"], rec["accepted"])]
                 out = (out[0], pot, out[2])
+            if md is not None and hit[-1] and not md.frozen:  # (after the thermostat's application where both fall on one step)
+                md.deposit(s)
         if rescaled:
             Ekin = th.last[:, L.THERMOSTAT_K_AFTER].cpu().numpy()
             Ekin = Ekin.astype(np.dtype("float32") if s.pos.dtype == torch.float32 else np.float64)
@@ -425,6 +461,11 @@ class Integrator:
                         "tmdhip_restraint_energy")
                 self.forces._restraint_energy = er
                 tot = tot + er.sum(axis=1)
+            if getattr(self.forces, "metadynamics", None) is not None:  # (V, CVs) of the finishing launch: one small copy
+                em = np.empty((R, 3), dtype=np.float64)
+                L.check(lib.tmdhip_metad_energy(eng.ctx, em.ctypes.data_as(C.POINTER(C.c_double)), _stream(dev)), "tmdhip_metad_energy")
+                self.forces.metadynamics.report(em)
+                tot = tot + em[:, 0]
             pot = [float(v) for v in tot]
             Ekin = obs[:, L.NENERGY].copy()
             Ekin = Ekin.astype(np.dtype("float32") if s.pos.dtype == torch.float32 else np.float64)
@@ -467,6 +508,8 @@ class Integrator:
             if ebuf is not None and getattr(self.forces, "restraints", None) is not None:
                 # (the step-by-step loop: the restraint energies of its last evaluation, as the fused path leaves them)
                 self.forces._restraint_energy = eng.rbuf.cpu().numpy()
+            if ebuf is not None and getattr(self.forces, "metadynamics", None) is not None:
+                self.forces.metadynamics.report(eng.mbuf.cpu().numpy())
         else:
             Ekin = ke.flatten().cpu().numpy()
         Ekin = Ekin.astype(np.dtype("float32") if s.pos.dtype == torch.float32 else np.float64)

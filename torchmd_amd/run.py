@@ -14,7 +14,10 @@ replica exchange on the ladder of `thermostat: csvr`) every monitor
 ladder the replica slot holds at that row — and the acceptance counts are written to `exchange.json` at the end.  With
 `restraints: file.npz` (harmonic position and distance restraints; arrays named as the fields of
 tmdhip_restraint_desc without `_host`, per-replica leading axes optional) every monitor file gains a `restraints` column: the
-restraint energy that `epot` contains.
+restraint energy that `epot` contains.  With a `metadynamics:` mapping (the arguments of `metadynamics.Metadynamics`: cvs, sigma,
+height, frequency, temperature, bias_factor, grid_min, grid_max, grid_bins, walkers) every monitor file gains a `bias`
+column (V(s(x)), inside `epot`) and one column per CV (`cv0`, `cv1`), and the hills log and the grid are written to
+`{output}_hills.npy` `[n,R,ncv+1]` and `{output}_bias_grid.npz` at the end.
 """
 
 from __future__ import annotations
@@ -60,6 +63,7 @@ DEFAULTS = dict(
     exchange_frequency=None,  # steps between two replica-exchange attempts; None: none.  Needs thermostat: csvr with a list: DESIGN §16
     exchange_seed=None,  # seed of the exchange's random stream; None: drawn from torch's generator (so `seed` reproduces it)
     restraints=None,  # None or an .npz file: harmonic position / distance restraints (pos_atom, pos_ref, pos_k, dist_pair, dist_r0, dist_k): DESIGN §17
+    metadynamics=None,  # None or a mapping with the arguments of metadynamics.Metadynamics (cvs: [[kind, [atoms]], ...]): DESIGN §18
     virtual_sites=None,  # None or "tip4p": four-site waters O,H1,H2,M; geometry from the force field's `virtual_sites` section: DESIGN §12
 )
 
@@ -73,7 +77,7 @@ def get_args(arguments=None):
             ap.add_argument(opt, dest=key, action="store_true", default=None)
         elif key in ("forceterms", "structure"):
             ap.add_argument(opt, dest=key, nargs="+", default=None)
-        elif key in ("external", "exclusions", "pme_grid"):
+        elif key in ("external", "exclusions", "pme_grid", "metadynamics"):
             continue
         else:
             ap.add_argument(opt, dest=key, default=None, type=type(val) if val is not None else str)
@@ -136,6 +140,10 @@ def get_args(arguments=None):
             raise ValueError("exchange_frequency needs thermostat: csvr with a list as thermostat_temperature (the ladder)")
     if isinstance(args.restraints, str) and args.restraints.lower() in ("none", "null", ""):
         args.restraints = None
+    if isinstance(args.metadynamics, str) and args.metadynamics.lower() in ("none", "null", ""):
+        args.metadynamics = None
+    if args.metadynamics is not None and not isinstance(args.metadynamics, dict):
+        raise ValueError("metadynamics must be a mapping with the arguments of Metadynamics (cvs, sigma, height, frequency, ...)")
     if isinstance(args.remove_com, str):
         args.remove_com = args.remove_com.lower() not in ("false", "0", "no", "off")
     args.remove_com = bool(args.remove_com)
@@ -250,6 +258,10 @@ def setup(args):
         from .restraints import Restraints
 
         extra["restraints"] = Restraints.from_npz(args.restraints, args.replicas)
+    if args.metadynamics is not None:
+        from .metadynamics import Metadynamics
+
+        extra["metadynamics"] = Metadynamics.from_config(args.metadynamics, args.replicas)
     forces = Forces(parameters, terms=terms, external=external, cutoff=args.cutoff, rfa=args.rfa,
                     switch_dist=args.switch_dist, exclusions=tuple(args.exclusions), pme=args.pme,
                     ewald_tolerance=args.ewald_tolerance, pme_order=args.pme_order, pme_grid=args.pme_grid, **extra)
@@ -335,6 +347,8 @@ def dynamics(args, mol, system, forces):
     columns += ("rung",) if exchange is not None else ()
     restrained = getattr(forces, "restraints", None) is not None
     columns += ("restraints",) if restrained else ()
+    metad = getattr(forces, "metadynamics", None)
+    columns += ("bias",) + tuple(f"cv{c}" for c in range(metad.ncv)) if metad is not None else ()
     logs = [LogWriter(args.log_dir, columns, name=f"monitor_{k}.csv") for k in range(args.replicas)]
     boxes = []  # [frames][R,3] box edges, constant-pressure runs only
     if args.minimize is not None:
@@ -364,8 +378,15 @@ def dynamics(args, mol, system, forces):
                 row["rung"] = int(exchange.rungs[k]) if exchange.rungs is not None else k
             if restrained:  # the restraint energy inside `epot`, as of the last evaluation
                 row["restraints"] = float(forces._restraint_energy[k].sum())
+            if metad is not None:  # the bias energy inside `epot` and the CVs, as of the last evaluation
+                row["bias"] = float(metad.energy[k])
+                for c in range(metad.ncv):
+                    row[f"cv{c}"] = float(metad.cv[k, c])
             logs[k].write_row(row)
     wall = time.time() - t0
+    if metad is not None:
+        np.save(os.path.join(args.log_dir, f"{name}_hills.npy"), metad.hills())
+        metad.save(os.path.join(args.log_dir, f"{name}_bias_grid.npz"))
     if exchange is not None:
         with open(os.path.join(args.log_dir, "exchange.json"), "w") as fh:
             none = exchange.rungs is None  # (no attempt was made: the run was shorter than exchange_frequency)
