@@ -532,6 +532,42 @@ int tmdhip_metad_energy(tmdhip_ctx *ctx, double *out_host, void *stream);
 /* Host copies of the grid(s), for restart and inspection: `count` doubles = grids x nodes x (2 or 4); they synchronise. */
 int tmdhip_metad_get_grid(tmdhip_ctx *ctx, double *out_host, int64_t count);
 int tmdhip_metad_set_grid(tmdhip_ctx *ctx, const double *in_host, int64_t count);
+/* Instantaneous pressure: the molecular virial (added to ABI 11: new symbols only; the suite pins the number).  For orthorhombic periodic boxes, per replica and axis a:
+ *   P_aa V = sum_I M_I V_I,a^2 + W_aa,   P = (P_xx + P_yy + P_zz) / 3
+ *   W_aa   = 1/2 sum_i sum_{j in list(i)} d_ij,a f_ij,a - sum_i delta_i,a F_i,a
+ * R_I / V_I = the mass-weighted centre of molecule I and its velocity, delta_i = r_i - R_I(i), d_ij the engine's minimum-image
+ * vector, f_ij the nonbonded pair force on i as the pair kernels evaluate it (pair_terms: reaction field, plain Coulomb, the
+ * real-space Ewald term, LJ with either switching flavour, repulsion, repulsionCG), F_i its sum over i's pairs: the virial of the nonbonded force field under a
+ * rigid displacement of whole molecules.  Bonded terms (1-4 included) and constraint forces are intramolecular and appear in
+ * neither sum; restraints, the metadynamics bias and external forces are not part of it; there is no long-range dispersion
+ * correction (as in the energy).  Molecules must be whole (what tmdhip_wrap leaves, or an unwrapped trajectory): no minimum image
+ * inside a molecule.  Every exclusion must lie inside one molecule (the caller checks: torchmd_amd.forces does).
+ * tmdhip_set_molecules: the molecules as a CSR over atoms on the host (offsets [nmol + 1], members [natoms]); every atom in
+ * exactly one molecule, indices in range, no empty molecule.  Copies to the device and synchronises; calling it again replaces
+ * the table.
+ * tmdhip_pressure: all replicas.  pos_dev / vel_dev real [R][N][3] (vel_dev NULL: the virial only, the kinetic entries are 0),
+ * mass_dev real [N], box_host [R][3], out_host double [R][8] = (sum M V^2 x, y, z; W x, y, z; V; P), energies in kcal/mol
+ * (velocities in the integrator's units, as for tmdhip_kinetic_energy), V in A^3, P in kcal/mol/A^3.  On the cell-list path the
+ * call advances every replica's list bookkeeping exactly as an evaluation does (displacement test, rebuild chain) and nothing
+ * else; it makes separate launches, synchronises the stream once and returns as tmdhip_compute: 0 = valid, 1 = a list was
+ * truncated (capacity grown): call again, negative = error.  Refused before any launch: a null argument, a wrong struct size, a
+ * box with a zero edge, a context with passive atoms (a brick of the domain decomposition), molecules not set, a molecule
+ * whose mass sum is <= 0 (the masses are read back once per mass array).
+ * PME contexts (grid and beta fixed, as the barostat scales a PME box): W gains the real-space Ewald branch of pair_terms, the
+ * reciprocal part sum_m e(m) [1 - 2 (1 + pi^2 m^2 / beta^2) m_a^2 / m^2] with e(m) the energy of a half-complex mode (Essmann et al.
+ * 1995), - sum_i delta_i,a F^rec_i,a and the neutralising background's own value; the self term has no volume dependence and the
+ * excluded-pair correction is intramolecular.
+ * Sums in double in both precisions, in one fixed order, no floating-point atomics: two calls on the same state give the same
+ * bits. */
+typedef struct tmdhip_molecule_desc {
+  int32_t struct_size; /* = sizeof(tmdhip_molecule_desc) */
+  int32_t nmol;
+  const int32_t *offsets_host; /* [nmol + 1] */
+  const int32_t *members_host; /* [natoms] */
+} tmdhip_molecule_desc;
+int tmdhip_set_molecules(tmdhip_ctx *ctx, const tmdhip_molecule_desc *desc);
+int tmdhip_pressure(tmdhip_ctx *ctx, const void *pos_dev, const void *vel_dev, const void *mass_dev, const double *box_host,
+                    double *out_host, void *stream);
 /* Fill `out_dev` (real [n]) with the N(0,1) stream used by tmdhip_langevin_second_vv (for tests). */
 int tmdhip_normal_fill(int dtype, int64_t n, void *out_dev, uint64_t seed, uint64_t step, void *stream);
 

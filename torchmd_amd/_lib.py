@@ -280,6 +280,15 @@ class MetadDesc(C.Structure):
     ]
 
 
+class MoleculeDesc(C.Structure):
+    _fields_ = [
+        ("struct_size", C.c_int32),
+        ("nmol", C.c_int32),
+        ("offsets_host", C.c_void_p),
+        ("members_host", C.c_void_p),
+    ]
+
+
 class FireParams(C.Structure):
     _fields_ = [
         ("struct_size", C.c_int32),
@@ -416,6 +425,11 @@ SIGNATURES = {
     "tmdhip_metad_energy": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.c_void_p]),
     "tmdhip_metad_get_grid": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.c_int64]),
     "tmdhip_metad_set_grid": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.c_int64]),
+    "tmdhip_set_molecules": (C.c_int, [C.c_void_p, C.POINTER(MoleculeDesc)]),
+    "tmdhip_pressure": (
+        C.c_int,
+        [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_void_p],
+    ),
     "tmdhip_normal_fill": (C.c_int, [C.c_int, C.c_int64, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p]),
     "tmdhip_dd_step": (
         C.c_int,

@@ -645,6 +645,8 @@ struct tmdhip_ctx {
   void *restraints = nullptr;
   // the metadynamics bias (tmdhip_set_metadynamics), metad.hip; null: off (no launch, nothing allocated)
   void *metad = nullptr;
+  // the molecule table and scratch of the pressure observable (tmdhip_set_molecules), virial.hip; null: not set
+  void *virial = nullptr;
   // timing of the dominant kernel
   bool timing = false;
   int timing_stride = 1;    // every n-th launch is timed
@@ -809,6 +811,11 @@ int pme_apply(tmdhip_ctx *ctx, int r, const R *pos, const double *box, R *forces
 // the same for an entry point's flags and untyped buffers: forces only with TMDHIP_WANT_FORCES, energies only with
 // TMDHIP_WANT_ENERGY
 int pme_hook(tmdhip_ctx *ctx, int r, const void *pos, const double *box, void *forces, double *energies, int flags, hipStream_t st);
+// the reciprocal-space part of the molecular virial (virial.hip): pme_virial_partials() x 3 doubles per replica
+int pme_virial_partials(const tmdhip_ctx *ctx);
+template <typename R>
+int pme_virial(tmdhip_ctx *ctx, int r, const R *pos, const double *box, const int *mol_of, const double *centre, double *vpart,
+               hipStream_t st);
 void pme_release(tmdhip_ctx *ctx);
 // md_cons.hip: the constraint state of the MD loop (tmdhip_set_constraints).  cons_verdict: < 0 (and the message) when a
 // constrained step since the last look failed to converge; reads a host-mapped word, so the caller must have waited for the
@@ -836,6 +843,8 @@ int restraint_impulse_each(tmdhip_ctx *ctx, const void *const *pos_each, const d
 int restraint_finish(tmdhip_ctx *ctx, const void *pos, const double *box_host, void *vel, void *forces, const void *mass, double kick,
                      hipStream_t st);
 // metad.hip (only called with ctx->metad set, except the release): the same four places, for the metadynamics bias
+// virial.hip
+void virial_release(tmdhip_ctx *ctx);
 void metad_release(tmdhip_ctx *ctx);
 int metad_run_check(tmdhip_ctx *ctx, const tmdhip_md_desc *d, double *impulse_kick, hipStream_t st);
 int metad_impulse(tmdhip_ctx *ctx, int rep0, int nrep, const void *pos, const double *box_host, void *vel, const void *mass, double kick,

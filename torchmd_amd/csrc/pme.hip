@@ -26,6 +26,7 @@
 #include <hipfft/hipfft.h>
 
 #include "engine.h"
+#include "virial_math.h"
 
 namespace tmd {
 
@@ -36,10 +37,11 @@ constexpr int kPmeMaxOrder = 6;
 
 struct PmeRep {
   DevBuf key, val, skey, sval, start, theta, grid, cgrid, infl, epart;
+  DevBuf vforce;  // pme_virial: the reciprocal-space force alone, real [N][3] (allocated on first use)
   double infl_box[3] = {-1, -1, -1};
   int64_t evals = 0;
   void release() {
-    for (DevBuf *b : {&key, &val, &skey, &sval, &start, &theta, &grid, &cgrid, &infl, &epart}) b->release();
+    for (DevBuf *b : {&key, &val, &skey, &sval, &start, &theta, &grid, &cgrid, &infl, &epart, &vforce}) b->release();
   }
 };
 
@@ -449,7 +451,158 @@ int apply_order(tmdhip_ctx *ctx, PmeState &S, PmeRep &pr, const R *pos, const Pm
   return 0;
 }
 
+// ---- the reciprocal-space part of the molecular virial (virial.hip: tmdhip_pressure) -------------------------------------
+// pme_conv_kernel plus three per-block partials of e(m) [1 - 2 (1 + pi^2 m^2 / beta^2) m_a^2 / m^2], e(m) = w_z G |S|^2 / 2
+template <typename R, typename C>
+__global__ __launch_bounds__(kPmeThreads) void pme_conv_virial_kernel(PmeBox<R> bx, double beta, const R *__restrict__ infl, C *__restrict__ cg,
+                                                                     double *__restrict__ vpart) {
+  __shared__ double lds[3][kPmeThreads / 64];
+  const int Kx = bx.K[0], Ky = bx.K[1], Kz = bx.K[2], Kh = Kz / 2 + 1;
+  const int c = blockIdx.x * blockDim.x + threadIdx.x;
+  double w[3] = {0.0, 0.0, 0.0};
+  if (c < Kx * Ky * Kh) {
+    const int mz = c % Kh, my = (c / Kh) % Ky, mx = c / (Kh * Ky);
+    const R G = infl[c];
+    C v = cg[c];
+    const double wz = (mz == 0 || (Kz % 2 == 0 && mz == Kz / 2)) ? 1.0 : 2.0;
+    const double e = 0.5 * wz * (double)G * ((double)v.x * (double)v.x + (double)v.y * (double)v.y);
+    const double f[3] = {(double)(mx <= Kx / 2 ? mx : mx - Kx) / (double)bx.L[0], (double)(my <= Ky / 2 ? my : my - Ky) / (double)bx.L[1],
+                         (double)mz / (double)bx.L[2]};
+    const double m2 = f[0] * f[0] + f[1] * f[1] + f[2] * f[2];
+    if (m2 > 0.0)
+      for (int a = 0; a < 3; ++a) w[a] = e * virial_mode_factor(m2, f[a] * f[a], beta);
+    v.x *= G;
+    v.y *= G;
+    cg[c] = v;
+  }
+  for (int a = 0; a < 3; ++a) {
+    const double s = wave_sum(w[a]);
+    if ((threadIdx.x & 63) == 0) lds[a][threadIdx.x >> 6] = s;
+  }
+  __syncthreads();
+  if (threadIdx.x < 3) {
+    double s = 0.0;
+    for (int k = 0; k < kPmeThreads / 64; ++k) s += lds[threadIdx.x][k];
+    vpart[3 * (size_t)blockIdx.x + threadIdx.x] = s;
+  }
+}
+
+// one thread per atom: -delta_i,a F^rec_i,a, per-block partials; block 0 also stores the background's share (E ~ 1 / V: its
+// own value on every diagonal element) in the slot behind the last block
+template <typename R>
+__global__ __launch_bounds__(kPmeThreads) void pme_virial_atoms_kernel(int n, const R *__restrict__ pos, const R *__restrict__ frec,
+                                                                      const int *__restrict__ mol_of, const double *__restrict__ centre,
+                                                                      double background, double *__restrict__ vpart) {
+#pragma clang fp contract(off)
+  __shared__ double lds[3][kPmeThreads / 64];
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  double w[3] = {0.0, 0.0, 0.0};
+  if (i < n) {
+    const double *c = centre + 3 * (size_t)mol_of[i];
+    for (int a = 0; a < 3; ++a) w[a] = -(((double)pos[3 * (size_t)i + a] - c[a]) * (double)frec[3 * (size_t)i + a]);
+  }
+  for (int a = 0; a < 3; ++a) {
+    const double s = wave_sum(w[a]);
+    if ((threadIdx.x & 63) == 0) lds[a][threadIdx.x >> 6] = s;
+  }
+  __syncthreads();
+  if (threadIdx.x < 3) {
+    double s = 0.0;
+    for (int k = 0; k < kPmeThreads / 64; ++k) s += lds[threadIdx.x][k];
+    vpart[3 * (size_t)blockIdx.x + threadIdx.x] = s;
+    if (blockIdx.x == 0) vpart[3 * (size_t)gridDim.x + threadIdx.x] = background;
+  }
+}
+
+template <typename R, int P>
+int virial_order(tmdhip_ctx *ctx, PmeState &S, PmeRep &pr, const R *pos, const PmeBox<R> &bx, const int *mol_of, const double *centre,
+                 double *vpart, hipStream_t st) {
+  const int n = ctx->d.natoms;
+  const int nb = (int)S.nbins(), nc = (int)S.ncomplex();
+  const unsigned ga = (unsigned)((n + kPmeThreads - 1) / kPmeThreads);
+  const R *qs = ctx->qs.as<R>();
+  TMD_TRY(pr.vforce.ensure(sizeof(R) * 3 * (size_t)n));
+  hipLaunchKernelGGL((pme_key_kernel<R>), dim3(ga), dim3(kPmeThreads), 0, st, n, pos, bx, pr.key.as<int>(), pr.val.as<int>());
+  TMD_HIP(hipGetLastError());
+  size_t tmp = S.sort_bytes;
+  TMD_HIP(hipcub::DeviceRadixSort::SortPairs(S.sort_tmp.p, tmp, pr.key.as<int>(), pr.skey.as<int>(), pr.val.as<int>(), pr.sval.as<int>(), n,
+                                             0, S.key_bits, st));
+  hipLaunchKernelGGL(pme_start_kernel, dim3((unsigned)((n + 1 + kPmeThreads - 1) / kPmeThreads)), dim3(kPmeThreads), 0, st, n, nb,
+                     pr.skey.as<int>(), pr.start.as<int>());
+  hipLaunchKernelGGL((pme_theta_kernel<R, P>), dim3(ga), dim3(kPmeThreads), 0, st, n, pos, qs, bx, pr.sval.as<int>(), pr.theta.as<R>());
+  hipLaunchKernelGGL((pme_spread_kernel<R, P>), dim3((unsigned)((nb + kPmeThreads - 1) / kPmeThreads)), dim3(kPmeThreads), 0, st, bx,
+                     pr.start.as<int>(), pr.skey.as<int>(), pr.theta.as<R>(), pr.grid.as<R>());
+  TMD_HIP(hipGetLastError());
+  if (hipfftSetStream(S.fwd, st) != HIPFFT_SUCCESS || hipfftSetStream(S.bwd, st) != HIPFFT_SUCCESS) return fail("PME: hipfftSetStream failed");
+  hipfftResult fr;
+  if constexpr (std::is_same<R, float>::value)
+    fr = hipfftExecR2C(S.fwd, pr.grid.as<hipfftReal>(), pr.cgrid.as<hipfftComplex>());
+  else
+    fr = hipfftExecD2Z(S.fwd, pr.grid.as<hipfftDoubleReal>(), pr.cgrid.as<hipfftDoubleComplex>());
+  if (fr != HIPFFT_SUCCESS) return fail("PME: forward FFT failed (" + std::to_string((int)fr) + ")");
+  const int nconv = (nc + kPmeThreads - 1) / kPmeThreads;
+  using C = typename std::conditional<std::is_same<R, float>::value, hipfftComplex, hipfftDoubleComplex>::type;
+  hipLaunchKernelGGL((pme_conv_virial_kernel<R, C>), dim3((unsigned)nconv), dim3(kPmeThreads), 0, st, bx, S.beta, pr.infl.as<R>(),
+                     pr.cgrid.as<C>(), vpart);
+  TMD_HIP(hipGetLastError());
+  if constexpr (std::is_same<R, float>::value)
+    fr = hipfftExecC2R(S.bwd, pr.cgrid.as<hipfftComplex>(), pr.grid.as<hipfftReal>());
+  else
+    fr = hipfftExecZ2D(S.bwd, pr.cgrid.as<hipfftDoubleComplex>(), pr.grid.as<hipfftDoubleReal>());
+  if (fr != HIPFFT_SUCCESS) return fail("PME: inverse FFT failed (" + std::to_string((int)fr) + ")");
+  TMD_HIP(hipMemsetAsync(pr.vforce.p, 0, sizeof(R) * 3 * (size_t)n, st));
+  hipLaunchKernelGGL((pme_force_kernel<R, P>), dim3(ga), dim3(kPmeThreads), 0, st, n, pos, qs, bx, pr.grid.as<R>(), pr.vforce.as<R>());
+  const double V = (double)bx.L[0] * (double)bx.L[1] * (double)bx.L[2], pi = 3.141592653589793;
+  const double background = -pi * S.sumq * S.sumq / (2.0 * V * S.beta * S.beta);
+  hipLaunchKernelGGL((pme_virial_atoms_kernel<R>), dim3(ga), dim3(kPmeThreads), 0, st, n, pos, pr.vforce.as<R>(), mol_of, centre, background,
+                     vpart + 3 * (size_t)nconv);
+  TMD_HIP(hipGetLastError());
+  return 0;
+}
+
 }  // namespace
+
+// entries [3] of the partials pme_virial writes per replica (0 without PME)
+int pme_virial_partials(const tmdhip_ctx *ctx) {
+  if (!ctx->pme) return 0;
+  const PmeState &S = *static_cast<const PmeState *>(ctx->pme);
+  return (int)((S.ncomplex() + kPmeThreads - 1) / kPmeThreads) + (ctx->d.natoms + kPmeThreads - 1) / kPmeThreads + 1;
+}
+
+// The reciprocal-space part of replica r's molecular virial as pme_virial_partials() x 3 doubles at `vpart`: the modes' W^rec (the
+// existing chain key / sort / theta / spread / forward FFT, then pme_conv_virial_kernel), -delta_i . F^rec_i from the usual C2R +
+// pme_force_kernel into a zeroed scratch array, and the neutralising background.  The self term has no volume dependence; the
+// excluded-pair correction is intramolecular and does not enter.  mol_of / centre: virial.hip's tables (centre: this replica's).
+template <typename R>
+int pme_virial(tmdhip_ctx *ctx, int r, const R *pos, const double *box, const int *mol_of, const double *centre, double *vpart,
+               hipStream_t st) {
+  if (!ctx->pme) return 0;
+  PmeState &S = *static_cast<PmeState *>(ctx->pme);
+  if (!(box[0] > 0 && box[1] > 0 && box[2] > 0)) return fail("PME needs a periodic box (all three edges > 0)");
+  if (r < 0 || r >= (int)S.rep.size()) return fail("PME: bad replica index");
+  PmeRep &pr = S.rep[r];
+  PmeBox<R> bx;
+  for (int d = 0; d < 3; ++d) {
+    bx.L[d] = (R)box[d];
+    bx.invL[d] = R(1) / bx.L[d];
+    bx.K[d] = S.K[d];
+  }
+  if (box[0] != pr.infl_box[0] || box[1] != pr.infl_box[1] || box[2] != pr.infl_box[2]) {  // C(m) of this box
+    const int nc = (int)S.ncomplex();
+    hipLaunchKernelGGL((pme_influence_kernel<R>), dim3((unsigned)((nc + kPmeThreads - 1) / kPmeThreads)), dim3(kPmeThreads), 0, st, bx, S.beta,
+                       S.moduli.as<double>(), pr.infl.as<R>());
+    TMD_HIP(hipGetLastError());
+    for (int d = 0; d < 3; ++d) pr.infl_box[d] = box[d];
+  }
+  switch (S.order) {
+    case 4: return virial_order<R, 4>(ctx, S, pr, pos, bx, mol_of, centre, vpart, st);
+    case 5: return virial_order<R, 5>(ctx, S, pr, pos, bx, mol_of, centre, vpart, st);
+    default: return virial_order<R, 6>(ctx, S, pr, pos, bx, mol_of, centre, vpart, st);
+  }
+}
+
+template int pme_virial<float>(tmdhip_ctx *, int, const float *, const double *, const int *, const double *, double *, hipStream_t);
+template int pme_virial<double>(tmdhip_ctx *, int, const double *, const double *, const int *, const double *, double *, hipStream_t);
 
 template <typename R>
 int pme_apply(tmdhip_ctx *ctx, int r, const R *pos, const double *box, R *forces, double *energies, hipStream_t st) {
@@ -515,7 +668,7 @@ int64_t pme_bytes(const tmdhip_ctx *ctx) {
   const PmeState &S = *static_cast<const PmeState *>(ctx->pme);
   int64_t b = (int64_t)(S.moduli.bytes + S.sort_tmp.bytes + S.fft_work);
   for (const auto &pr : S.rep)
-    for (const DevBuf *d : {&pr.key, &pr.val, &pr.skey, &pr.sval, &pr.start, &pr.theta, &pr.grid, &pr.cgrid, &pr.infl, &pr.epart})
+    for (const DevBuf *d : {&pr.key, &pr.val, &pr.skey, &pr.sval, &pr.start, &pr.theta, &pr.grid, &pr.cgrid, &pr.infl, &pr.epart, &pr.vforce})
       b += (int64_t)d->bytes;
   return b;
 }

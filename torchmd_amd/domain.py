@@ -601,6 +601,12 @@ class DryDomain(Domain):
 class DomainSet:
     """Drives the domains of this process: one (`DistTransport`) or all of them (`LocalTransport`)."""
 
+    def pressure(self, *args, **kwargs):
+        """Refused: the molecular virial is evaluated by one context over whole molecules, a brick holds passive atoms."""
+        raise ValueError("the pressure is not available under the domain decomposition")
+
+    pressure_tensor = pressure
+
     def __init__(self, box, world, device, dtype, terms, cutoff, A=None, B=None, skin=1.5, grid=None, transport=None,
                  dry=False, **engine_kwargs):
         if engine_kwargs.get("pme"):

@@ -954,6 +954,93 @@ class Forces:
         self._evaluate(pos, box, None, False, False, count_pairs=True)
         return [self.stats(pos, r)["pairs_in_cutoff"] for r in range(pos.shape[0])]
 
+    # ------------------------------------------------------------------ pressure
+    def _molecules(self):
+        """The molecule table of the pressure observable, made and checked once: (offsets, members, mol_of)."""
+        from . import pressure as P
+
+        tab = getattr(self, "_molecule_table", None)
+        if tab is None or len(tab[2]) != self.natoms:
+            bp = getattr(self.par, "bond_params", None)
+            bonds = bp["idx"].detach().cpu().numpy() if bp is not None and len(bp["idx"]) else None
+            tab = P.molecule_table(self.natoms, bonds, self.virtual_sites)
+            P.check_molecules(tab[2], self._excl_csr, self.virtual_sites)
+            self._molecule_table = tab
+        return tab
+
+    def _pressure_terms(self, pos, box, vel=None, masses=None):
+        """`tmdhip_pressure` for every replica: [R, 8] float64 on the host = (sum M V^2 x, y, z; W x, y, z; V; P), energies in
+        kcal/mol, V in A^3, P in kcal/mol/A^3.  `vel` None: the virial alone (the kinetic entries are 0)."""
+        from . import pressure as P
+
+        if _is_batched(pos) or _is_batched(box):
+            raise ValueError("the pressure cannot be evaluated under torch.vmap (its molecule table and lists are per replica of the context)")
+        if getattr(self, "_nactive", None):
+            raise ValueError("the pressure is not available for a brick of the domain decomposition (its context holds passive atoms)")
+        L.require_device_tensor(pos, "pos")
+        L.require_device_tensor(box, "box")
+        if pos.dim() != 3 or pos.shape[2] != 3 or pos.shape[1] != self.natoms:
+            raise RuntimeError(f"pos must have shape (nreplicas, {self.natoms}, 3), got {tuple(pos.shape)}")
+        p = pos.detach()
+        if not p.is_contiguous():
+            p = p.contiguous()
+        R = p.shape[0]
+        boxes = self._replica_boxes(box, R)
+        P.check_edges(boxes)
+        self._pme_box(boxes)
+        off, mem, _ = self._molecules()
+        if masses is None:
+            masses = torch.as_tensor(self.par.masses).detach()
+        m = masses.detach().to(device=p.device, dtype=p.dtype).reshape(-1).contiguous()
+        if m.numel() != self.natoms:
+            raise RuntimeError("masses must hold one entry per atom")
+        v = None
+        if vel is not None:
+            L.require_device_tensor(vel, "vel")
+            if vel.shape != p.shape or vel.dtype != p.dtype:
+                raise RuntimeError("vel must have the dtype and shape of pos")
+            v = vel.detach().contiguous()
+        eng = self._engine(p)
+        out = np.empty((R, 8), dtype=np.float64)
+        with torch.cuda.device(p.device):
+            if getattr(eng, "_molecules_set", None) is not off:
+                md = L.MoleculeDesc()
+                md.struct_size = C.sizeof(L.MoleculeDesc)
+                md.nmol = len(off) - 1
+                md.offsets_host, md.members_host = off.ctypes.data_as(C.c_void_p), mem.ctypes.data_as(C.c_void_p)
+                L.check(eng.lib.tmdhip_set_molecules(eng.ctx, C.byref(md)), "tmdhip_set_molecules")
+                eng._molecules_set = off
+            stream = C.c_void_p(torch.cuda.current_stream(p.device).cuda_stream)
+            eng.place_sites(p)  # first launch (no-op without virtual sites), as compute() does
+            for _ in range(4):
+                rc = L.check(
+                    eng.lib.tmdhip_pressure(eng.ctx, C.c_void_p(p.data_ptr()), C.c_void_p(v.data_ptr()) if v is not None else C.c_void_p(),
+                                            C.c_void_p(m.data_ptr()), boxes.ctypes.data_as(C.POINTER(C.c_double)),
+                                            out.ctypes.data_as(C.POINTER(C.c_double)), stream),
+                    "tmdhip_pressure",
+                )
+                if rc == 0:
+                    break
+            else:
+                raise RuntimeError("neighbour list kept overflowing; increase `skin` capacity")
+            if eng.vsites is not None and p.data_ptr() != pos.data_ptr():
+                pos.detach().copy_(p)  # (a non-contiguous `pos` was evaluated through a copy: the sites go back)
+        return out
+
+    def virial(self, pos, box):
+        """The diagonal of the molecular virial of the nonbonded force field, [R, 3] float64 (numpy) in kcal/mol:
+        W_aa = -(dU/d ln L_a) under a scaling of the box edge L_a that moves every molecule rigidly with its mass-weighted
+        centre, so that P_aa V = sum_I M_I V_I,a^2 + W_aa.  Molecules are the connected components of the bond
+        graph (a virtual site belongs to its parents' molecule) and must be whole, as `Wrapper.wrap` leaves them; bonded
+        terms and constraint forces act inside a molecule and do not contribute.  `external`, restraints and the
+        metadynamics bias are NOT included, and there is no long-range dispersion correction.  With virtual sites the site
+        rows of `pos` are written first, as `compute()` does.  On the cell-list path the call advances the neighbour-list
+        bookkeeping exactly as an evaluation does and changes nothing else.  ValueError: under `torch.vmap`, on a brick
+        of the domain decomposition, with a zero box edge, and when an exclusion or a site's parents span two
+        molecules.  With `pme=True` (grid and beta fixed, as the barostat scales a PME box) the reciprocal-space part, its
+        molecular correction and the neutralising background are included."""
+        return self._pressure_terms(pos, box)[:, 3:6].copy()
+
     def invalidate_lists(self, pos):
         """Drop the neighbour lists of every replica: the next evaluation re-plans the grid and rebuilds them
         (`tmdhip_invalidate_list`; after positions were changed out of band, and by tests)."""

@@ -312,6 +312,34 @@ class Integrator:
                 return self._step_metad(lib, s, dev, code, R, N, fast, niter)
             return self._step_body(lib, s, dev, code, R, N, fast, fused, niter, replay=False)
 
+    def _pressure_terms(self):
+        from .forces import Forces
+
+        if not isinstance(self.forces, Forces):
+            raise ValueError("the pressure needs this package's Forces (duck-typed force objects are not supported)")
+        if self.batch is not None:
+            raise ValueError("the pressure does not support atom groups (batch=): its molecules are per replica")
+        self._check_layout()
+        s = self.systems
+        return self.forces._pressure_terms(s.pos, s.box, vel=s.vel, masses=self.masses)
+
+    def pressure_tensor(self):
+        """The diagonal (P_xx, P_yy, P_zz) of the instantaneous pressure of every replica, [R, 3] float64 in bar, from the
+        molecular virial: P_aa V = sum_I M_I V_I,a^2 + W_aa with `Forces.virial`'s W and the velocities of the
+        molecules' centres of mass as they are now (after `step()`: both half kicks made).  The pressure of the force
+        field: no `external`, restraint or metadynamics contribution, no dispersion correction.  Separate launches between
+        two `step()` calls; a run `step(); pressure(); step()` equals the run that calls `forces.compute()` there."""
+        from .barostat import BAR_TO_KCAL_MOL_A3
+
+        t = self._pressure_terms()
+        return (t[:, 0:3] + t[:, 3:6]) / t[:, 6:7] / BAR_TO_KCAL_MOL_A3
+
+    def pressure(self):
+        """The instantaneous pressure (P_xx + P_yy + P_zz) / 3 of every replica, [R] float64 in bar (`pressure_tensor`)."""
+        from .barostat import BAR_TO_KCAL_MOL_A3
+
+        return self._pressure_terms()[:, 7] / BAR_TO_KCAL_MOL_A3
+
     def _step_npt(self, lib, s, dev, code, R, N, fast, niter):
         """`step(niter)` at constant pressure: segments that end on multiples of the barostat's frequency (counted over the
         integrator's life), each run as `step` runs it, and a volume move after every segment that ends on a multiple.

@@ -18,6 +18,8 @@ restraint energy that `epot` contains.  With a `metadynamics:` mapping (the argu
 height, frequency, temperature, bias_factor, grid_min, grid_max, grid_bins, walkers) every monitor file gains a `bias`
 column (V(s(x)), inside `epot`) and one column per CV (`cv0`, `cv1`), and the hills log and the grid are written to
 `{output}_hills.npy` `[n,R,ncv+1]` and `{output}_bias_grid.npz` at the end.
+With `pressure: true` every monitor file gains a `pressure` column (bar): the instantaneous pressure of the force field from the
+molecular virial, evaluated when a monitor row is written, with or without `barostat_pressure`.
 """
 
 from __future__ import annotations
@@ -64,6 +66,7 @@ DEFAULTS = dict(
     exchange_seed=None,  # seed of the exchange's random stream; None: drawn from torch's generator (so `seed` reproduces it)
     restraints=None,  # None or an .npz file: harmonic position / distance restraints (pos_atom, pos_ref, pos_k, dist_pair, dist_r0, dist_k): DESIGN §17
     metadynamics=None,  # None or a mapping with the arguments of metadynamics.Metadynamics (cvs: [[kind, [atoms]], ...]): DESIGN §18
+    pressure=False,  # True: every monitor file gains a `pressure` column (bar): the instantaneous pressure from the molecular virial: DESIGN §19
     virtual_sites=None,  # None or "tip4p": four-site waters O,H1,H2,M; geometry from the force field's `virtual_sites` section: DESIGN §12
 )
 
@@ -93,6 +96,7 @@ def get_args(arguments=None):
             setattr(args, k, float(getattr(args, k)))
     args.ewald_tolerance = float(args.ewald_tolerance)
     args.pme = bool(args.pme)
+    args.pressure = args.pressure.lower() in ("true", "yes", "1") if isinstance(args.pressure, str) else bool(args.pressure)
     if isinstance(args.constraints, str) and args.constraints.lower() in ("none", "null", ""):
         args.constraints = None
     if args.constraints not in (None, "water", "hbonds"):
@@ -344,6 +348,7 @@ def dynamics(args, mol, system, forces):
     nper = args.steps // args.output_period
     stager = FrameStager(system, nper)
     columns = ("iter", "ns", "epot", "ekin", "etot", "T") + (("volume",) if barostat is not None else ())
+    columns += ("pressure",) if args.pressure else ()
     columns += ("rung",) if exchange is not None else ()
     restrained = getattr(forces, "restraints", None) is not None
     columns += ("restraints",) if restrained else ()
@@ -365,6 +370,7 @@ def dynamics(args, mol, system, forces):
         stager.push(system.pos)
         if barostat is not None:
             boxes.append(torch.diagonal(system.box, dim1=-2, dim2=-1).to("cpu", torch.float64).numpy().copy())
+        pressure = integrator.pressure() if args.pressure else None  # (of the wrapped positions: molecules are whole)
         for k in range(args.replicas):
             if (i * args.output_period) % args.save_period == 0 or i == nper:
                 np.save(os.path.join(args.log_dir, f"{name}_{k}{ext or '.npy'}"), stager.frames(k))
@@ -374,6 +380,8 @@ def dynamics(args, mol, system, forces):
                    "epot": Epot[k], "ekin": float(Ekin[k]), "etot": Epot[k] + float(Ekin[k]), "T": float(T[k])}
             if barostat is not None:
                 row["volume"] = float(np.prod(boxes[-1][k]))
+            if pressure is not None:
+                row["pressure"] = float(pressure[k])
             if exchange is not None:
                 row["rung"] = int(exchange.rungs[k]) if exchange.rungs is not None else k
             if restrained:  # the restraint energy inside `epot`, as of the last evaluation
