@@ -48,6 +48,7 @@
 #include "pacing.h"
 #include "chain_plan.h"
 #include "grid_plan.h"
+#include "allpairs_split.h"
 #include "rng.h"
 
 namespace tmd {
@@ -728,6 +729,26 @@ inline void launch_with_events(K kernel, dim3 grid, dim3 block, unsigned shmem, 
                                hipEvent_t e1, Args... args) {
   if (e0 && e1) hipExtLaunchKernelGGL(kernel, grid, block, shmem, st, e0, e1, 0u, args...);
   else hipLaunchKernelGGL(kernel, grid, block, shmem, st, args...);
+}
+
+// blocks of four waves that a pair launch over the replica's list takes (ListGeom::apw atoms per wave)
+inline int list_blocks(const tmdhip_ctx *ctx, const Replica &rp) {
+  const int waves = (ctx->d.natoms + rp.lg.apw - 1) / rp.lg.apw;
+  return (waves + 3) / 4;
+}
+
+// f(std::integral_constant<int, LPA>{}) for the list's lanes per atom (ListGeom::lpa: a power of two, 1 .. 64)
+template <typename F>
+inline void dispatch_lpa(int lpa, F &&f) {
+  switch (lpa) {
+    case 1: f(std::integral_constant<int, 1>{}); break;
+    case 2: f(std::integral_constant<int, 2>{}); break;
+    case 4: f(std::integral_constant<int, 4>{}); break;
+    case 8: f(std::integral_constant<int, 8>{}); break;
+    case 16: f(std::integral_constant<int, 16>{}); break;
+    case 32: f(std::integral_constant<int, 32>{}); break;
+    default: f(std::integral_constant<int, 64>{}); break;
+  }
 }
 
 // a FUSED launch of a lean pair kernel (see FusedStepT): device copy of the static part, this launch's part

@@ -220,10 +220,7 @@ template <bool ENERGY>
 int launch_pair_lean_f64(tmdhip_ctx *ctx, Replica &rp, const PairConsts<double> &c, double *f, int overwrite,
                          hipStream_t st, hipEvent_t e0, hipEvent_t e1, int lmode) {
   const int n = ctx->d.natoms;
-  const int apw = rp.lg.apw;
-  const int waves = (n + apw - 1) / apw;
-  const int blocks = (waves + 3) / 4;
-  const int npair8 = (blocks + 7) / 8 * 8;
+  const int npair8 = (list_blocks(ctx, rp) + 7) / 8 * 8;
   const bool lj = c.terms & TMDHIP_TERM_LJ, el = c.terms & TMDHIP_TERM_ELECTROSTATICS;
 #define TMD_LAUNCH_FAST_T(L, A, B)       \
   if (c.switch_on && A) {               \

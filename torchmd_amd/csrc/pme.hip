@@ -219,24 +219,53 @@ __device__ __forceinline__ double block_sum(double v, double *lds) {
   return s;
 }
 
-// S(m) *= G(m); epart[block] = sum of weight G |S|^2 over the block's points (weight 2 for the modes whose conjugate the
-// half-complex grid leaves out)
+// block-wide meeting of three per-lane doubles: dst[0..2] = the block's sums, the wave partials added in sequence
+__device__ __forceinline__ void block_store3(const double (&w)[3], double *dst) {
+  __shared__ double lds[3][kPmeThreads / 64];
+  for (int a = 0; a < 3; ++a) {
+    const double s = wave_sum(w[a]);
+    if ((threadIdx.x & 63) == 0) lds[a][threadIdx.x >> 6] = s;
+  }
+  __syncthreads();
+  if (threadIdx.x < 3) {
+    double s = 0.0;
+    for (int k = 0; k < kPmeThreads / 64; ++k) s += lds[threadIdx.x][k];
+    dst[threadIdx.x] = s;
+  }
+}
+
+// mode c of the half-complex grid: S(m) *= G(m) in place; its indices, the weight of the mode (2 where the grid leaves the
+// conjugate out), G and |S|^2 before the multiplication
+struct PmeMode {
+  int mx, my, mz;
+  double wz, G, s2;
+};
+template <typename R, typename C>
+__device__ __forceinline__ PmeMode conv_mode(int c, int Ky, int Kz, const R *__restrict__ infl, C *__restrict__ cg) {
+  const int Kh = Kz / 2 + 1;
+  PmeMode m;
+  m.mz = c % Kh, m.my = (c / Kh) % Ky, m.mx = c / (Kh * Ky);
+  const R G = infl[c];
+  C v = cg[c];
+  m.wz = (m.mz == 0 || (Kz % 2 == 0 && m.mz == Kz / 2)) ? 1.0 : 2.0;
+  m.G = (double)G;
+  m.s2 = (double)v.x * (double)v.x + (double)v.y * (double)v.y;
+  v.x *= G;
+  v.y *= G;
+  cg[c] = v;
+  return m;
+}
+
+// S(m) *= G(m); epart[block] = sum of weight G |S|^2 over the block's points
 template <typename R, typename C>
 __global__ __launch_bounds__(kPmeThreads) void pme_conv_kernel(int Kx, int Ky, int Kz, const R *__restrict__ infl, C *__restrict__ cg,
                                                               double *__restrict__ epart) {
   __shared__ double lds[kPmeThreads / 64];
-  const int Kh = Kz / 2 + 1;
   const int c = blockIdx.x * blockDim.x + threadIdx.x;
   double e = 0.0;
-  if (c < Kx * Ky * Kh) {
-    const int mz = c % Kh;
-    const R G = infl[c];
-    C v = cg[c];
-    const double wz = (mz == 0 || (Kz % 2 == 0 && mz == Kz / 2)) ? 1.0 : 2.0;
-    e = wz * (double)G * ((double)v.x * (double)v.x + (double)v.y * (double)v.y);
-    v.x *= G;
-    v.y *= G;
-    cg[c] = v;
+  if (c < Kx * Ky * (Kz / 2 + 1)) {
+    const PmeMode m = conv_mode<R, C>(c, Ky, Kz, infl, cg);
+    e = m.wz * m.G * m.s2;
   }
   const double s = block_sum<R>(e, lds);
   if (threadIdx.x == 0) epart[blockIdx.x] = s;
@@ -399,11 +428,11 @@ int alloc_rep(PmeState &P, PmeRep &pr, int n) {
   return 0;
 }
 
+// key ... forward FFT: S(m) of the replica's charges in pr.cgrid (both FFT plans are put on the stream)
 template <typename R, int P>
-int apply_order(tmdhip_ctx *ctx, PmeState &S, PmeRep &pr, const R *pos, const PmeBox<R> &bx, R *forces, double *energies,
-                hipStream_t st) {
+int pme_forward(tmdhip_ctx *ctx, PmeState &S, PmeRep &pr, const R *pos, const PmeBox<R> &bx, hipStream_t st) {
   const int n = ctx->d.natoms;
-  const int nb = (int)S.nbins(), nc = (int)S.ncomplex();
+  const int nb = (int)S.nbins();
   const unsigned ga = (unsigned)((n + kPmeThreads - 1) / kPmeThreads);
   const R *qs = ctx->qs.as<R>();
   hipLaunchKernelGGL((pme_key_kernel<R>), dim3(ga), dim3(kPmeThreads), 0, st, n, pos, bx, pr.key.as<int>(), pr.val.as<int>());
@@ -424,6 +453,29 @@ int apply_order(tmdhip_ctx *ctx, PmeState &S, PmeRep &pr, const R *pos, const Pm
   else
     fr = hipfftExecD2Z(S.fwd, pr.grid.as<hipfftDoubleReal>(), pr.cgrid.as<hipfftDoubleComplex>());
   if (fr != HIPFFT_SUCCESS) return fail("PME: forward FFT failed (" + std::to_string((int)fr) + ")");
+  return 0;
+}
+
+// the inverse FFT: pr.cgrid -> pr.grid
+template <typename R>
+int pme_inverse(PmeState &S, PmeRep &pr) {
+  hipfftResult fr;
+  if constexpr (std::is_same<R, float>::value)
+    fr = hipfftExecC2R(S.bwd, pr.cgrid.as<hipfftComplex>(), pr.grid.as<hipfftReal>());
+  else
+    fr = hipfftExecZ2D(S.bwd, pr.cgrid.as<hipfftDoubleComplex>(), pr.grid.as<hipfftDoubleReal>());
+  if (fr != HIPFFT_SUCCESS) return fail("PME: inverse FFT failed (" + std::to_string((int)fr) + ")");
+  return 0;
+}
+
+template <typename R, int P>
+int apply_order(tmdhip_ctx *ctx, PmeState &S, PmeRep &pr, const R *pos, const PmeBox<R> &bx, R *forces, double *energies,
+                hipStream_t st) {
+  const int n = ctx->d.natoms;
+  const int nc = (int)S.ncomplex();
+  const unsigned ga = (unsigned)((n + kPmeThreads - 1) / kPmeThreads);
+  const R *qs = ctx->qs.as<R>();
+  TMD_TRY((pme_forward<R, P>(ctx, S, pr, pos, bx, st)));
   double *epart = pr.epart.as<double>();
   const int nconv = (nc + kPmeThreads - 1) / kPmeThreads, nex = (int)ga;
   using C = typename std::conditional<std::is_same<R, float>::value, hipfftComplex, hipfftDoubleComplex>::type;
@@ -431,11 +483,7 @@ int apply_order(tmdhip_ctx *ctx, PmeState &S, PmeRep &pr, const R *pos, const Pm
                      pr.cgrid.as<C>(), epart);
   TMD_HIP(hipGetLastError());
   if (forces) {
-    if constexpr (std::is_same<R, float>::value)
-      fr = hipfftExecC2R(S.bwd, pr.cgrid.as<hipfftComplex>(), pr.grid.as<hipfftReal>());
-    else
-      fr = hipfftExecZ2D(S.bwd, pr.cgrid.as<hipfftDoubleComplex>(), pr.grid.as<hipfftDoubleReal>());
-    if (fr != HIPFFT_SUCCESS) return fail("PME: inverse FFT failed (" + std::to_string((int)fr) + ")");
+    TMD_TRY(pme_inverse<R>(S, pr));
     hipLaunchKernelGGL((pme_force_kernel<R, P>), dim3(ga), dim3(kPmeThreads), 0, st, n, pos, qs, bx, pr.grid.as<R>(), forces);
     TMD_HIP(hipGetLastError());
   }
@@ -452,39 +500,23 @@ int apply_order(tmdhip_ctx *ctx, PmeState &S, PmeRep &pr, const R *pos, const Pm
 }
 
 // ---- the reciprocal-space part of the molecular virial (virial.hip: tmdhip_pressure) -------------------------------------
-// pme_conv_kernel plus three per-block partials of e(m) [1 - 2 (1 + pi^2 m^2 / beta^2) m_a^2 / m^2], e(m) = w_z G |S|^2 / 2
+// pme_conv_kernel's modes (conv_mode) with three per-block partials of e(m) [1 - 2 (1 + pi^2 m^2 / beta^2) m_a^2 / m^2], e(m) = w_z G |S|^2 / 2
 template <typename R, typename C>
 __global__ __launch_bounds__(kPmeThreads) void pme_conv_virial_kernel(PmeBox<R> bx, double beta, const R *__restrict__ infl, C *__restrict__ cg,
                                                                      double *__restrict__ vpart) {
-  __shared__ double lds[3][kPmeThreads / 64];
-  const int Kx = bx.K[0], Ky = bx.K[1], Kz = bx.K[2], Kh = Kz / 2 + 1;
+  const int Kx = bx.K[0], Ky = bx.K[1], Kz = bx.K[2];
   const int c = blockIdx.x * blockDim.x + threadIdx.x;
   double w[3] = {0.0, 0.0, 0.0};
-  if (c < Kx * Ky * Kh) {
-    const int mz = c % Kh, my = (c / Kh) % Ky, mx = c / (Kh * Ky);
-    const R G = infl[c];
-    C v = cg[c];
-    const double wz = (mz == 0 || (Kz % 2 == 0 && mz == Kz / 2)) ? 1.0 : 2.0;
-    const double e = 0.5 * wz * (double)G * ((double)v.x * (double)v.x + (double)v.y * (double)v.y);
-    const double f[3] = {(double)(mx <= Kx / 2 ? mx : mx - Kx) / (double)bx.L[0], (double)(my <= Ky / 2 ? my : my - Ky) / (double)bx.L[1],
-                         (double)mz / (double)bx.L[2]};
+  if (c < Kx * Ky * (Kz / 2 + 1)) {
+    const PmeMode m = conv_mode<R, C>(c, Ky, Kz, infl, cg);
+    const double e = 0.5 * m.wz * m.G * m.s2;
+    const double f[3] = {(double)(m.mx <= Kx / 2 ? m.mx : m.mx - Kx) / (double)bx.L[0],
+                         (double)(m.my <= Ky / 2 ? m.my : m.my - Ky) / (double)bx.L[1], (double)m.mz / (double)bx.L[2]};
     const double m2 = f[0] * f[0] + f[1] * f[1] + f[2] * f[2];
     if (m2 > 0.0)
       for (int a = 0; a < 3; ++a) w[a] = e * virial_mode_factor(m2, f[a] * f[a], beta);
-    v.x *= G;
-    v.y *= G;
-    cg[c] = v;
   }
-  for (int a = 0; a < 3; ++a) {
-    const double s = wave_sum(w[a]);
-    if ((threadIdx.x & 63) == 0) lds[a][threadIdx.x >> 6] = s;
-  }
-  __syncthreads();
-  if (threadIdx.x < 3) {
-    double s = 0.0;
-    for (int k = 0; k < kPmeThreads / 64; ++k) s += lds[threadIdx.x][k];
-    vpart[3 * (size_t)blockIdx.x + threadIdx.x] = s;
-  }
+  block_store3(w, vpart + 3 * (size_t)blockIdx.x);
 }
 
 // one thread per atom: -delta_i,a F^rec_i,a, per-block partials; block 0 also stores the background's share (E ~ 1 / V: its
@@ -494,62 +526,31 @@ __global__ __launch_bounds__(kPmeThreads) void pme_virial_atoms_kernel(int n, co
                                                                       const int *__restrict__ mol_of, const double *__restrict__ centre,
                                                                       double background, double *__restrict__ vpart) {
 #pragma clang fp contract(off)
-  __shared__ double lds[3][kPmeThreads / 64];
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   double w[3] = {0.0, 0.0, 0.0};
   if (i < n) {
     const double *c = centre + 3 * (size_t)mol_of[i];
     for (int a = 0; a < 3; ++a) w[a] = -(((double)pos[3 * (size_t)i + a] - c[a]) * (double)frec[3 * (size_t)i + a]);
   }
-  for (int a = 0; a < 3; ++a) {
-    const double s = wave_sum(w[a]);
-    if ((threadIdx.x & 63) == 0) lds[a][threadIdx.x >> 6] = s;
-  }
-  __syncthreads();
-  if (threadIdx.x < 3) {
-    double s = 0.0;
-    for (int k = 0; k < kPmeThreads / 64; ++k) s += lds[threadIdx.x][k];
-    vpart[3 * (size_t)blockIdx.x + threadIdx.x] = s;
-    if (blockIdx.x == 0) vpart[3 * (size_t)gridDim.x + threadIdx.x] = background;
-  }
+  block_store3(w, vpart + 3 * (size_t)blockIdx.x);
+  if (blockIdx.x == 0 && threadIdx.x < 3) vpart[3 * (size_t)gridDim.x + threadIdx.x] = background;
 }
 
 template <typename R, int P>
 int virial_order(tmdhip_ctx *ctx, PmeState &S, PmeRep &pr, const R *pos, const PmeBox<R> &bx, const int *mol_of, const double *centre,
                  double *vpart, hipStream_t st) {
   const int n = ctx->d.natoms;
-  const int nb = (int)S.nbins(), nc = (int)S.ncomplex();
+  const int nc = (int)S.ncomplex();
   const unsigned ga = (unsigned)((n + kPmeThreads - 1) / kPmeThreads);
   const R *qs = ctx->qs.as<R>();
   TMD_TRY(pr.vforce.ensure(sizeof(R) * 3 * (size_t)n));
-  hipLaunchKernelGGL((pme_key_kernel<R>), dim3(ga), dim3(kPmeThreads), 0, st, n, pos, bx, pr.key.as<int>(), pr.val.as<int>());
-  TMD_HIP(hipGetLastError());
-  size_t tmp = S.sort_bytes;
-  TMD_HIP(hipcub::DeviceRadixSort::SortPairs(S.sort_tmp.p, tmp, pr.key.as<int>(), pr.skey.as<int>(), pr.val.as<int>(), pr.sval.as<int>(), n,
-                                             0, S.key_bits, st));
-  hipLaunchKernelGGL(pme_start_kernel, dim3((unsigned)((n + 1 + kPmeThreads - 1) / kPmeThreads)), dim3(kPmeThreads), 0, st, n, nb,
-                     pr.skey.as<int>(), pr.start.as<int>());
-  hipLaunchKernelGGL((pme_theta_kernel<R, P>), dim3(ga), dim3(kPmeThreads), 0, st, n, pos, qs, bx, pr.sval.as<int>(), pr.theta.as<R>());
-  hipLaunchKernelGGL((pme_spread_kernel<R, P>), dim3((unsigned)((nb + kPmeThreads - 1) / kPmeThreads)), dim3(kPmeThreads), 0, st, bx,
-                     pr.start.as<int>(), pr.skey.as<int>(), pr.theta.as<R>(), pr.grid.as<R>());
-  TMD_HIP(hipGetLastError());
-  if (hipfftSetStream(S.fwd, st) != HIPFFT_SUCCESS || hipfftSetStream(S.bwd, st) != HIPFFT_SUCCESS) return fail("PME: hipfftSetStream failed");
-  hipfftResult fr;
-  if constexpr (std::is_same<R, float>::value)
-    fr = hipfftExecR2C(S.fwd, pr.grid.as<hipfftReal>(), pr.cgrid.as<hipfftComplex>());
-  else
-    fr = hipfftExecD2Z(S.fwd, pr.grid.as<hipfftDoubleReal>(), pr.cgrid.as<hipfftDoubleComplex>());
-  if (fr != HIPFFT_SUCCESS) return fail("PME: forward FFT failed (" + std::to_string((int)fr) + ")");
+  TMD_TRY((pme_forward<R, P>(ctx, S, pr, pos, bx, st)));
   const int nconv = (nc + kPmeThreads - 1) / kPmeThreads;
   using C = typename std::conditional<std::is_same<R, float>::value, hipfftComplex, hipfftDoubleComplex>::type;
   hipLaunchKernelGGL((pme_conv_virial_kernel<R, C>), dim3((unsigned)nconv), dim3(kPmeThreads), 0, st, bx, S.beta, pr.infl.as<R>(),
                      pr.cgrid.as<C>(), vpart);
   TMD_HIP(hipGetLastError());
-  if constexpr (std::is_same<R, float>::value)
-    fr = hipfftExecC2R(S.bwd, pr.cgrid.as<hipfftComplex>(), pr.grid.as<hipfftReal>());
-  else
-    fr = hipfftExecZ2D(S.bwd, pr.cgrid.as<hipfftDoubleComplex>(), pr.grid.as<hipfftDoubleReal>());
-  if (fr != HIPFFT_SUCCESS) return fail("PME: inverse FFT failed (" + std::to_string((int)fr) + ")");
+  TMD_TRY(pme_inverse<R>(S, pr));
   TMD_HIP(hipMemsetAsync(pr.vforce.p, 0, sizeof(R) * 3 * (size_t)n, st));
   hipLaunchKernelGGL((pme_force_kernel<R, P>), dim3(ga), dim3(kPmeThreads), 0, st, n, pos, qs, bx, pr.grid.as<R>(), pr.vforce.as<R>());
   const double V = (double)bx.L[0] * (double)bx.L[1] * (double)bx.L[2], pi = 3.141592653589793;
@@ -560,28 +561,9 @@ int virial_order(tmdhip_ctx *ctx, PmeState &S, PmeRep &pr, const R *pos, const P
   return 0;
 }
 
-}  // namespace
-
-// entries [3] of the partials pme_virial writes per replica (0 without PME)
-int pme_virial_partials(const tmdhip_ctx *ctx) {
-  if (!ctx->pme) return 0;
-  const PmeState &S = *static_cast<const PmeState *>(ctx->pme);
-  return (int)((S.ncomplex() + kPmeThreads - 1) / kPmeThreads) + (ctx->d.natoms + kPmeThreads - 1) / kPmeThreads + 1;
-}
-
-// The reciprocal-space part of replica r's molecular virial as pme_virial_partials() x 3 doubles at `vpart`: the modes' W^rec (the
-// existing chain key / sort / theta / spread / forward FFT, then pme_conv_virial_kernel), -delta_i . F^rec_i from the usual C2R +
-// pme_force_kernel into a zeroed scratch array, and the neutralising background.  The self term has no volume dependence; the
-// excluded-pair correction is intramolecular and does not enter.  mol_of / centre: virial.hip's tables (centre: this replica's).
+// the box as the kernels take it; brings the replica's influence function up to date with it
 template <typename R>
-int pme_virial(tmdhip_ctx *ctx, int r, const R *pos, const double *box, const int *mol_of, const double *centre, double *vpart,
-               hipStream_t st) {
-  if (!ctx->pme) return 0;
-  PmeState &S = *static_cast<PmeState *>(ctx->pme);
-  if (!(box[0] > 0 && box[1] > 0 && box[2] > 0)) return fail("PME needs a periodic box (all three edges > 0)");
-  if (r < 0 || r >= (int)S.rep.size()) return fail("PME: bad replica index");
-  PmeRep &pr = S.rep[r];
-  PmeBox<R> bx;
+int pme_box_for(PmeState &S, PmeRep &pr, const double *box, hipStream_t st, PmeBox<R> &bx) {
   for (int d = 0; d < 3; ++d) {
     bx.L[d] = (R)box[d];
     bx.invL[d] = R(1) / bx.L[d];
@@ -594,6 +576,31 @@ int pme_virial(tmdhip_ctx *ctx, int r, const R *pos, const double *box, const in
     TMD_HIP(hipGetLastError());
     for (int d = 0; d < 3; ++d) pr.infl_box[d] = box[d];
   }
+  return 0;
+}
+
+}  // namespace
+
+// entries [3] of the partials pme_virial writes per replica (0 without PME)
+int pme_virial_partials(const tmdhip_ctx *ctx) {
+  if (!ctx->pme) return 0;
+  const PmeState &S = *static_cast<const PmeState *>(ctx->pme);
+  return (int)((S.ncomplex() + kPmeThreads - 1) / kPmeThreads) + (ctx->d.natoms + kPmeThreads - 1) / kPmeThreads + 1;
+}
+
+// The reciprocal-space part of replica r's molecular virial as pme_virial_partials() x 3 doubles at `vpart`: the modes' W^rec
+// (pme_forward, then pme_conv_virial_kernel), -delta_i . F^rec_i from pme_inverse + pme_force_kernel into a zeroed scratch array, and the neutralising background.  The self term has no volume dependence; the
+// excluded-pair correction is intramolecular and does not enter.  mol_of / centre: virial.hip's tables (centre: this replica's).
+template <typename R>
+int pme_virial(tmdhip_ctx *ctx, int r, const R *pos, const double *box, const int *mol_of, const double *centre, double *vpart,
+               hipStream_t st) {
+  if (!ctx->pme) return 0;
+  PmeState &S = *static_cast<PmeState *>(ctx->pme);
+  if (!(box[0] > 0 && box[1] > 0 && box[2] > 0)) return fail("PME needs a periodic box (all three edges > 0)");
+  if (r < 0 || r >= (int)S.rep.size()) return fail("PME: bad replica index");
+  PmeRep &pr = S.rep[r];
+  PmeBox<R> bx;
+  TMD_TRY(pme_box_for<R>(S, pr, box, st, bx));
   switch (S.order) {
     case 4: return virial_order<R, 4>(ctx, S, pr, pos, bx, mol_of, centre, vpart, st);
     case 5: return virial_order<R, 5>(ctx, S, pr, pos, bx, mol_of, centre, vpart, st);
@@ -612,18 +619,7 @@ int pme_apply(tmdhip_ctx *ctx, int r, const R *pos, const double *box, R *forces
   if (r < 0 || r >= (int)S.rep.size()) return fail("PME: bad replica index");
   PmeRep &pr = S.rep[r];
   PmeBox<R> bx;
-  for (int d = 0; d < 3; ++d) {
-    bx.L[d] = (R)box[d];
-    bx.invL[d] = R(1) / bx.L[d];
-    bx.K[d] = S.K[d];
-  }
-  if (box[0] != pr.infl_box[0] || box[1] != pr.infl_box[1] || box[2] != pr.infl_box[2]) {  // C(m) of this box
-    const int nc = (int)S.ncomplex();
-    hipLaunchKernelGGL((pme_influence_kernel<R>), dim3((unsigned)((nc + kPmeThreads - 1) / kPmeThreads)), dim3(kPmeThreads), 0, st, bx, S.beta,
-                       S.moduli.as<double>(), pr.infl.as<R>());
-    TMD_HIP(hipGetLastError());
-    for (int d = 0; d < 3; ++d) pr.infl_box[d] = box[d];
-  }
+  TMD_TRY(pme_box_for<R>(S, pr, box, st, bx));
   pr.evals++;
   switch (S.order) {
     case 4: return apply_order<R, 4>(ctx, S, pr, pos, bx, forces, energies, st);

@@ -6,21 +6,23 @@
 // whole molecules the bonded terms, the constraint forces and every other intramolecular force do no work, so none of them
 // appears; molecules must be whole (no minimum image inside a molecule: the barostat's contract).
 //
-// Separate launches between two tmdhip_md_run calls, like a plain evaluation; no pair, step or list-build kernel is touched.
+// Separate launches between two tmdhip_md_run calls, like a plain evaluation.  The pair kernels walk the pair set with the
+// functions the force kernels use (pair_walk.h), at the launch geometry the force launches use (list_blocks, allpairs_split).
 //   mol_centre_kernel      one thread per molecule of <= 64 atoms (one wave per larger one: a second launch, only when such
 //                          molecules exist), blockIdx.y = replica: R_I in double, per-block partials of sum M_I V_I,a^2
-//   virial_list_kernel     the twin of list_pair_kernel<R, false, LPA, 0> (pair_generic.hip): the same row addressing, entry
-//                          decoding, unroll, predication and pair_terms; every lane adds f_a (d_a / 2 - delta_i,a) pair by pair
-//                          in double; wave butterfly, the four waves meet in LDS, one thread stores the block's three partials
-//   virial_allpairs_kernel the twin of allpairs_kernel: all-pairs contexts and cell-list contexts that fell back
-//   pme.hip: pme_virial    PME contexts: the modes' W^rec from a twin of the convolution kernel, -delta_i . F^rec_i from the usual
-//                          C2R + force kernel into a scratch array, and the neutralising background, as partials of their own
+//   virial_list_kernel     walk_list_rows, as list_pair_kernel<R, false, LPA, 0>: every lane adds f_a (d_a / 2 - delta_i,a)
+//                          pair by pair in double; wave butterfly, the four waves meet in LDS, one thread stores the block's
+//                          three partials
+//   virial_allpairs_kernel walk_allpairs_tiles, as allpairs_kernel: all-pairs contexts and cell-list contexts that fell back
+//   pme.hip: pme_virial    PME contexts: the chain of pme_apply (pme_forward / pme_inverse) with the modes' W^rec from
+//                          pme_conv_virial_kernel, -delta_i . F^rec_i from the force kernel into a scratch array, and the
+//                          neutralising background, as partials of their own
 //   virial_fold_kernel     one wave per replica: lane l sums the partials l, l + 64, ..., then the butterfly; writes
 //                          double [R][8] = (sum M V^2 x, y, z; W x, y, z; V; P)
 // No floating-point atomics anywhere, every sum in one fixed order: two calls on the same state give the same bits.
-// The pair kernels are bound like the generic list kernel they copy (gather latency + pair_terms); everything else is a few
+// The pair kernels are bound like the generic list kernel (gather latency + pair_terms); everything else is a few
 // microseconds of launch.
-#include "engine.h"
+#include "pair_walk.h"
 #include "virial_math.h"
 
 using namespace tmd;
@@ -130,7 +132,7 @@ __device__ __forceinline__ void centre_offset(const int *__restrict__ mol_of, co
   delta[0] = (double)x - c[0], delta[1] = (double)y - c[1], delta[2] = (double)z - c[2];
 }
 
-// list_pair_kernel<R, false, LPA, 0> with the force accumulation replaced by the virial's; wpart: this replica's [blocks][3]
+// list_pair_kernel<R, false, LPA, 0>'s walk (pair_walk.h) with the virial's accumulation; wpart: this replica's [blocks][3]
 template <typename R, int LPA>
 __global__ __launch_bounds__(256) void virial_list_kernel(int n, const typename Vec<R>::T4 *__restrict__ sorted, const int *__restrict__ stype,
                                                           const int *__restrict__ order, int ntypes,
@@ -138,83 +140,28 @@ __global__ __launch_bounds__(256) void virial_list_kernel(int n, const typename 
                                                           const int *__restrict__ nneigh, int maxn, PairConsts<R> c,
                                                           const int *__restrict__ mol_of, const double *__restrict__ centre,
                                                           double *__restrict__ wpart) {
-  using R4 = typename Vec<R>::T4;
-  using R2 = typename Vec<R>::T2;
-  constexpr int APW = 64 / LPA;
-  constexpr int UNROLL = 4;
-  extern __shared__ __align__(16) unsigned char smem[];
-  R2 *stab = reinterpret_cast<R2 *>(smem);
-  for (int t = threadIdx.x; t < ntypes * ntypes; t += blockDim.x) stab[t] = tab[t];
-  __syncthreads();
-
-  const int lane = threadIdx.x & 63;
-  const int wave = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
-  const int a = wave * APW + lane / LPA;
-  const int sub = lane % LPA;
-  const bool active = a < n;
-  const int aself = active ? a : 0;
-  R4 pi;
-  pi.x = pi.y = pi.z = pi.w = 0;
-  int nn = 0, trow = 0;
-  double delta[3] = {0.0, 0.0, 0.0};
-  if (active) {
-    pi = sorted[a];
-    nn = nneigh[a];
-    trow = stype[a] * ntypes;
-    centre_offset<R>(mol_of, centre, order[a], pi.x, pi.y, pi.z, delta);
-  }
-  int nmax = nn;
-#pragma unroll
-  for (int o = 32; o >= LPA; o >>= 1) nmax = max(nmax, __shfl_xor(nmax, o, 64));
-  const int nkk = (nmax + LPA - 1) / LPA;
-  const unsigned *row = nlist + (size_t)wave * maxn * APW + lane * 4;  // + (kk / 4) * 256 + kk % 4
-
-  double w[3] = {0.0, 0.0, 0.0};
-  for (int kk0 = 0; kk0 < nkk; kk0 += UNROLL) {
-    unsigned entry[UNROLL];
-    R4 pj[UNROLL];
-    bool valid[UNROLL];
-    int jdx[UNROLL], tj[UNROLL];
-#pragma unroll
-    for (int u = 0; u < UNROLL; ++u) entry[u] = (kk0 + u < nkk) ? row[(size_t)(kk0 >> 2) * 256 + u] : 0u;
-#pragma unroll
-    for (int u = 0; u < UNROLL; ++u) {
-      valid[u] = (kk0 + u) * LPA + sub < nn;
-      jdx[u] = valid[u] ? (int)((entry[u] & kEntryOffMask) >> 4) : aself;
-      pj[u] = sorted[jdx[u]];
-      tj[u] = !valid[u] ? 0 : (ntypes <= kEntryTypes ? (int)(entry[u] >> kEntryTypeShift) : stype[jdx[u]]);
-    }
-#pragma unroll
-    for (int u = 0; u < UNROLL; ++u) {
-      const R dx = min_image(pi.x - pj[u].x, c.box[0], c.invbox[0]);
-      const R dy = min_image(pi.y - pj[u].y, c.box[1], c.invbox[1]);
-      const R dz = min_image(pi.z - pj[u].z, c.box[2], c.invbox[2]);
-      const R r2 = norm2(dx, dy, dz);
-      const bool hit = valid[u] && (r2 <= c.r2max);
-      const R2 ab = stab[trow + tj[u]];
-      const R r2s = hit ? r2 : R(1);
-      R e4[4] = {0, 0, 0, 0};
-      R fs = pair_terms<R, false>(c, r2s, pi.w * pj[u].w, ab.x, ab.y, e4);
-      fs = hit ? fs : R(0);
-      virial_pair<R>(dx, dy, dz, fs, delta, w);
-    }
-  }
+  double delta[3] = {0.0, 0.0, 0.0}, w[3] = {0.0, 0.0, 0.0};
+  walk_list_rows<R, LPA>(
+      n, sorted, stype, ntypes, tab, nlist, nneigh, maxn, c,
+      [&](int a, const typename Vec<R>::T4 &pi) { centre_offset<R>(mol_of, centre, order[a], pi.x, pi.y, pi.z, delta); },
+      [&](R dx, R dy, R dz, R r2s, bool hit, R qq, typename Vec<R>::T2 ab) {
+        R e4[4] = {0, 0, 0, 0};
+        R fs = pair_terms<R, false>(c, r2s, qq, ab.x, ab.y, e4);
+        fs = hit ? fs : R(0);
+        virial_pair<R>(dx, dy, dz, fs, delta, w);
+      });
   block_store3<4>(w[0], w[1], w[2], wpart + 3 * (size_t)blockIdx.x);
 }
 
-// allpairs_kernel<R, false> with the force accumulation replaced by the virial's.  grid = (ceil(N / 64), nsplit, replicas), one
-// wave per block; boxes[z] = {box[3], 1 / box[3]} (set_boxes); wpart [R][wstride][3], block (x, y) of a replica at y gridDim.x + x
+// allpairs_kernel<R, false>'s walk (pair_walk.h) with the virial's accumulation.  grid = (nb, nsplit, replicas) of allpairs_split,
+// one wave per block; boxes[z] = {box[3], 1 / box[3]} (set_boxes); wpart [R][nb nsplit][3], block (x, y) of a replica at y nb + x
 template <typename R>
 __global__ __launch_bounds__(64) void virial_allpairs_kernel(int n, const R *__restrict__ pos, const R *__restrict__ qs,
                                                              const int *__restrict__ types, int ntypes,
                                                              const typename Vec<R>::T2 *__restrict__ tab, const int *__restrict__ excl_off,
                                                              const int *__restrict__ excl_idx, PairConsts<R> c, int jchunk,
                                                              const R *__restrict__ boxes, const int *__restrict__ mol_of,
-                                                             const double *__restrict__ centre, int nmol, double *__restrict__ wpart,
-                                                             int wstride) {
-  using R4 = typename Vec<R>::T4;
-  __shared__ R4 sj[64];
-  __shared__ int st[64];
+                                                             const double *__restrict__ centre, int nmol, double *__restrict__ wpart) {
   const int rep = blockIdx.z;
   pos += (size_t)rep * 3 * n;
   centre += (size_t)rep * 3 * nmol;
@@ -223,63 +170,17 @@ __global__ __launch_bounds__(64) void virial_allpairs_kernel(int n, const R *__r
     c.box[k] = boxes[6 * rep + k];
     c.invbox[k] = boxes[6 * rep + 3 + k];
   }
-  const int lane = threadIdx.x;
-  const int i = blockIdx.x * 64 + lane;
-  const bool active = i < n;
-  const int jbeg = blockIdx.y * jchunk;
-  const int jend = min(n, jbeg + jchunk);
-  R xi = 0, yi = 0, zi = 0, qi = 0;
-  int trow = 0, ebeg = 0, eend = 0;
-  double delta[3] = {0.0, 0.0, 0.0};
-  if (active) {
-    xi = pos[3 * i + 0];
-    yi = pos[3 * i + 1];
-    zi = pos[3 * i + 2];
-    qi = qs[i];
-    trow = types[i] * ntypes;
-    ebeg = excl_off[i];
-    eend = excl_off[i + 1];
-    centre_offset<R>(mol_of, centre, i, xi, yi, zi, delta);
-  }
-  double w[3] = {0.0, 0.0, 0.0};
-  for (int j0 = jbeg; j0 < jend; j0 += 64) {
-    __syncthreads();
-    const int jl = j0 + lane;
-    if (jl < jend) {
-      R4 v;
-      v.x = pos[3 * jl + 0];
-      v.y = pos[3 * jl + 1];
-      v.z = pos[3 * jl + 2];
-      v.w = qs[jl];
-      sj[lane] = v;
-      st[lane] = types[jl];
-    }
-    __syncthreads();
-    // exclusion mask of this tile for atom i (rows are sorted)
-    unsigned long long skip = 0;
-    for (int e = ebeg; e < eend; ++e) {
-      const int x = excl_idx[e];
-      if (x >= j0 + 64) break;
-      if (x >= j0) skip |= 1ull << (x - j0);
-    }
-    if (i >= j0 && i < j0 + 64) skip |= 1ull << (i - j0);
-    const int tile = min(64, jend - j0);
-    for (int k = 0; k < tile; ++k) {
-      const R4 pj = sj[k];
-      const R dx = min_image(xi - pj.x, c.box[0], c.invbox[0]);
-      const R dy = min_image(yi - pj.y, c.box[1], c.invbox[1]);
-      const R dz = min_image(zi - pj.z, c.box[2], c.invbox[2]);
-      const R r2 = norm2(dx, dy, dz);
-      const bool hit = active && !((skip >> k) & 1ull) && (r2 <= c.r2max);
-      if (hit) {
-        const typename Vec<R>::T2 ab = tab[trow + st[k]];
-        R e4[4] = {0, 0, 0, 0};
-        const R fs = pair_terms<R, false>(c, r2, qi * pj.w, ab.x, ab.y, e4);
-        virial_pair<R>(dx, dy, dz, fs, delta, w);
-      }
-    }
-  }
-  block_store3<1>(w[0], w[1], w[2], wpart + ((size_t)rep * wstride + (size_t)blockIdx.y * gridDim.x + blockIdx.x) * 3);
+  const int i = blockIdx.x * 64 + threadIdx.x;
+  double delta[3] = {0.0, 0.0, 0.0}, w[3] = {0.0, 0.0, 0.0};
+  if (i < n) centre_offset<R>(mol_of, centre, i, pos[3 * i + 0], pos[3 * i + 1], pos[3 * i + 2], delta);
+  walk_allpairs_tiles<R>(n, pos, qs, types, ntypes, tab, excl_off, excl_idx, c, jchunk,
+                         [&](R dx, R dy, R dz, R r2, R qq, typename Vec<R>::T2 ab, int) {
+                           R e4[4] = {0, 0, 0, 0};
+                           const R fs = pair_terms<R, false>(c, r2, qq, ab.x, ab.y, e4);
+                           virial_pair<R>(dx, dy, dz, fs, delta, w);
+                         });
+  const size_t slot = ((size_t)rep * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
+  block_store3<1>(w[0], w[1], w[2], wpart + 3 * slot);
 }
 
 // one wave per replica: lane l takes the partials l, l + 64, ..., then the butterfly
@@ -324,45 +225,18 @@ int check_masses(tmdhip_ctx *ctx, VirialState *S, const void *mass_dev, hipStrea
   return 0;
 }
 
-// the j split of launch_allpairs (pair_generic.hip)
-void allpairs_split(int n, int nrep, int &nb, int &nsplit, int &jchunk) {
-  nb = (n + 63) / 64;
-  const double pairs = (double)n * (double)n * (double)nrep;
-  const int want_waves = (int)std::min(4096.0, std::max(1024.0, pairs / 512.0));
-  nsplit = std::max(1, std::min((n + 15) / 16, want_waves / std::max(nb * nrep, 1)));
-  jchunk = ((n + nsplit - 1) / nsplit + 15) / 16 * 16;
-  nsplit = (n + jchunk - 1) / jchunk;
-}
-
 template <typename R>
 int launch_list(tmdhip_ctx *ctx, VirialState *S, Replica &rp, const PairConsts<R> &c, const double *centre, double *wpart, hipStream_t st) {
   using R4 = typename Vec<R>::T4;
   using R2 = typename Vec<R>::T2;
-  const int n = ctx->d.natoms;
-  const int waves = (n + rp.lg.apw - 1) / rp.lg.apw;
-  const int blocks = (waves + 3) / 4;
   const size_t shmem = (size_t)ctx->d.ntypes * ctx->d.ntypes * sizeof(R2);
-#define TMD_LAUNCH(L)                                                                                                             \
-  hipLaunchKernelGGL((virial_list_kernel<R, L>), dim3(blocks), dim3(256), shmem, st, n, rp.sorted.as<R4>(), rp.stype.as<int>(),   \
-                     rp.order.as<int>(), ctx->d.ntypes, ctx->tab.as<R2>(), rp.nlist.as<unsigned>(), rp.nneigh.as<int>(), rp.lg.maxn, \
-                     c, S->mol_of.as<int>(), centre, wpart)
-  switch (rp.lg.lpa) {
-    case 1: TMD_LAUNCH(1); break;
-    case 2: TMD_LAUNCH(2); break;
-    case 4: TMD_LAUNCH(4); break;
-    case 8: TMD_LAUNCH(8); break;
-    case 16: TMD_LAUNCH(16); break;
-    case 32: TMD_LAUNCH(32); break;
-    default: TMD_LAUNCH(64); break;
-  }
-#undef TMD_LAUNCH
+  dispatch_lpa(rp.lg.lpa, [&](auto lpa) {
+    hipLaunchKernelGGL((virial_list_kernel<R, decltype(lpa)::value>), dim3(list_blocks(ctx, rp)), dim3(256), shmem, st, ctx->d.natoms,
+                       rp.sorted.as<R4>(), rp.stype.as<int>(), rp.order.as<int>(), ctx->d.ntypes, ctx->tab.as<R2>(),
+                       rp.nlist.as<unsigned>(), rp.nneigh.as<int>(), rp.lg.maxn, c, S->mol_of.as<int>(), centre, wpart);
+  });
   TMD_HIP(hipGetLastError());
   return 0;
-}
-
-inline int list_blocks(const tmdhip_ctx *ctx, const Replica &rp) {
-  const int waves = (ctx->d.natoms + rp.lg.apw - 1) / rp.lg.apw;
-  return (waves + 3) / 4;
 }
 
 template <typename R>
@@ -426,7 +300,7 @@ int pressure(tmdhip_ctx *ctx, VirialState *S, const void *pos_dev, const void *v
     hipLaunchKernelGGL((virial_allpairs_kernel<R>), dim3((unsigned)nb, (unsigned)nsplit, (unsigned)nrep), dim3(64), 0, st, n, pos,
                        ctx->qs.as<R>(), ctx->types.as<int>(), ctx->d.ntypes, ctx->tab.as<R2>(), ctx->excl_off.as<int>(),
                        ctx->excl_idx.as<int>(), c, jchunk, boxes, S->mol_of.as<int>(), S->centre.as<double>(), nmol,
-                       S->wpart.as<double>(), wstride);
+                       S->wpart.as<double>());
     TMD_HIP(hipGetLastError());
   }
   if (ctx->d.terms == 0) {
