@@ -568,6 +568,26 @@ typedef struct tmdhip_molecule_desc {
 int tmdhip_set_molecules(tmdhip_ctx *ctx, const tmdhip_molecule_desc *desc);
 int tmdhip_pressure(tmdhip_ctx *ctx, const void *pos_dev, const void *vel_dev, const void *mass_dev, const double *box_host,
                     double *out_host, void *stream);
+/* The move of a virial-driven barostat (stochastic cell rescaling, Berendsen; added to ABI 11): the box edges of replica r are
+ * multiplied by scale[r][a] and every molecule follows rigidly: each of its atoms is translated by (s_a - 1) R_a and each velocity
+ * by (1 / s_a - 1) V_a, with R = sum m x / sum m and V = sum m v / sum m the MASS-WEIGHTED centre of the molecule and its velocity
+ * (the quantities tmdhip_pressure's virial is defined on; tmdhip_scale_groups uses the unweighted mean and leaves velocities).
+ * Sums in double in both precisions, members in index order, one rounding on the store.  pos_dev / vel_dev real [R][N][3] in
+ * place, mass_dev real [N], scale_host double [R][3] (read before the call returns), the molecules as a CSR over atoms in
+ * device int32 arrays (offsets [nmol + 1], members [natoms], every atom once); has_big != 0 if a molecule has more than 64
+ * atoms: the launch for those molecules is made only then, so a caller that passes 0 for such a table leaves them where they are
+ * while the box changes (the flag is the caller's promise; it is not checked, the table being on the device).  record_dev
+ * receives double [R][2] = (K_before, K_after), sum m v^2 / 2 over the atoms before and after the shift (of the
+ * velocities as stored); partials_dev is scratch; tmdhip_rescale_molecules_workspace returns both sizes in doubles.  A replica
+ * whose three factors are exactly 1 is not written (its record is).  A member of mass 0 (a virtual site) moves with its molecule,
+ * its velocity is neither read nor written and it enters no sum; a molecule without mass stays where it is.  Molecules must be
+ * whole.  Stateless, no host synchronisation, no floating-point atomics: two calls on the same input give the same bits.
+ * Refused before any launch: a bad dtype, bad sizes, a null pointer, a factor that is not positive and finite,
+ * pos_dev == vel_dev. */
+int tmdhip_rescale_molecules_workspace(int64_t nreplicas, int64_t nmol, int64_t *record_doubles, int64_t *partials_doubles);
+int tmdhip_rescale_molecules(int dtype, int64_t nreplicas, int64_t natoms, void *pos_dev, void *vel_dev, const void *mass_dev,
+                             const double *scale_host, int32_t nmol, const int32_t *offsets_dev, const int32_t *members_dev,
+                             int32_t has_big, double *record_dev, double *partials_dev, void *stream);
 /* Fill `out_dev` (real [n]) with the N(0,1) stream used by tmdhip_langevin_second_vv (for tests). */
 int tmdhip_normal_fill(int dtype, int64_t n, void *out_dev, uint64_t seed, uint64_t step, void *stream);
 

@@ -3,7 +3,8 @@
 Public surface mirrors the reference package for this path:
     torchmd_amd.forces.Forces, torchmd_amd.integrator.Integrator, torchmd_amd.systems.System,
     torchmd_amd.parameters.Parameters, torchmd_amd.forcefields.ForceField
-plus `torchmd_amd.MonteCarloBarostat` (constant pressure) and `torchmd_amd.VelocityRescale` (stochastic velocity
+plus `torchmd_amd.MonteCarloBarostat` (constant pressure) and `torchmd_amd.CRescaleBarostat` (constant pressure from the
+virial: stochastic cell rescaling, one target per replica) and `torchmd_amd.VelocityRescale` (stochastic velocity
 rescaling, one target temperature per replica) and `torchmd_amd.ReplicaExchange` / `torchmd_amd.temperature_ladder`
 (temperature replica exchange on that thermostat's ladder) and `torchmd_amd.Restraints` (harmonic position and distance
 restraints with one target per replica) and `torchmd_amd.Metadynamics` (well-tempered metadynamics on distance and
@@ -24,6 +25,10 @@ def __getattr__(name):
         from .barostat import MonteCarloBarostat
 
         return MonteCarloBarostat
+    if name == "CRescaleBarostat":
+        from .crescale import CRescaleBarostat
+
+        return CRescaleBarostat
     if name == "VelocityRescale":
         from .thermostat import VelocityRescale
 
@@ -44,6 +49,7 @@ def __getattr__(name):
 
 
 __all__ = [
+    "CRescaleBarostat",
     "Forces",
     "Integrator",
     "Metadynamics",

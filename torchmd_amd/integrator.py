@@ -4,7 +4,8 @@ Mirror of the reference module (`torchmd/integrator.py`): same constants, helper
 `Integrator(systems, forces, timestep, device, gamma=None, T=None, batch=None)` constructor and
 `step(niter) -> (Ekin, pot, T)` contract, plus an opt-in `constraints` keyword ("water": rigid waters by SETTLE;
 "hbonds": also every X-H bond by SHAKE/RATTLE) and an opt-in `barostat` keyword (a
-`barostat.MonteCarloBarostat`: constant pressure) and an opt-in `thermostat` keyword (a
+`barostat.MonteCarloBarostat`, or a `crescale.CRescaleBarostat` driven by the virial: constant pressure, DESIGN §11 and
+§20) and an opt-in `thermostat` keyword (a
 `thermostat.VelocityRescale`: stochastic velocity rescaling between batches of steps, one target temperature per replica,
 DESIGN §14) and an opt-in `exchange` keyword (an `exchange.ReplicaExchange`: temperature replica exchange on the thermostat's
 ladder) that this package adds.  Each iteration is
@@ -168,13 +169,17 @@ class Integrator:
                              "stepped as part of its rigid water (sites on flexible molecules: Forces.compute only)")
         if constraints is not None:
             self._init_constraints(constraints)
-        self.barostat = barostat  # barostat.MonteCarloBarostat
+        self.barostat = barostat  # barostat.MonteCarloBarostat or crescale.CRescaleBarostat
+        # (a virial-driven barostat moves every time, rescales velocities too and holds one target per replica)
+        self._virial_barostat = bool(getattr(barostat, "virial_driven", False))
         self._check_restraints()
         self.replays = 0  # batches that were rewound and repeated (list validity failure / step-block time-out)
         self.thermostat = thermostat  # thermostat.VelocityRescale
         if thermostat is not None:
             self._init_thermostat(thermostat)
-        if barostat is not None:
+        if barostat is not None and self._virial_barostat:
+            barostat.check(self)
+        elif barostat is not None:
             barostat.check(systems, forces, temperature=(thermostat.temperature if thermostat is not None else T) or 0)
         self.exchange = exchange  # exchange.ReplicaExchange
         if exchange is not None:
@@ -218,7 +223,7 @@ class Integrator:
         if self.batch is not None:
             raise ValueError("thermostat= does not support atom groups (batch=): its scale factor is per replica")
         th.targets(self.systems.pos.shape[0])
-        if self.barostat is not None and th.temperature is None:
+        if self.barostat is not None and th.temperature is None and not self._virial_barostat:
             raise ValueError("a temperature ladder cannot run under barostat=: the barostat holds one temperature")
         if self.constraints is not None:
             ndof = int(self._ndof)
@@ -349,10 +354,20 @@ class Integrator:
             fused = fast and not self.forces.external
             out = self._step_body(lib, s, dev, code, R, N, fast, fused, n, replay=False)
             if attempt:
-                rec = self.barostat.attempt(s, self.forces, out[1])
-                pot = [float(un if ok else u) for u, un, ok in zip(rec["U"], rec["U_new"], rec["accepted"])]
-                out = (out[0], pot, out[2])
+                out = self._barostat_move(s, out)
         return out
+
+    def _barostat_move(self, s, out):
+        """The barostat's move after a segment that returned `out`; what `step` returns for the state it leaves.  Monte Carlo:
+        the potential energy of the replicas whose move was accepted changes.  Virial-driven (`CRescaleBarostat`): every
+        replica is rescaled, velocities included, so all three entries are those of the rescaled state."""
+        if not self._virial_barostat:
+            rec = self.barostat.attempt(s, self.forces, out[1])
+            pot = [float(un if ok else u) for u, un, ok in zip(rec["U"], rec["U_new"], rec["accepted"])]
+            return (out[0], pot, out[2])
+        rec = self.barostat.apply(s, self.forces, self.masses, self.dt, out[1], out[0])
+        Ekin = rec["K_after"].astype(np.dtype("float32") if s.pos.dtype == torch.float32 else np.float64)
+        return (Ekin, [float(u) for u in rec["U_new"]], self._temperature(Ekin))
 
     def _step_metad(self, lib, s, dev, code, R, N, fast, niter):
         """`step(niter)` under a metadynamics bias: segments that end on multiples of its frequency (counted over the
@@ -387,9 +402,8 @@ class Integrator:
             if hit[0]:
                 th.apply(s, self.masses, self.dt, self._thermostat_ndof)
             if baro is not None and hit[1]:
-                rec = baro.attempt(s, self.forces, out[1])
-                pot = [float(un if ok else u) for u, un, ok in zip(rec["U"], rec["U_new"], rec["accepted"])]
-                out = (out[0], pot, out[2])
+                out = self._barostat_move(s, out)
+                rescaled = rescaled and not self._virial_barostat  # (the kinetic energy returned is the barostat's K_after)
             if md is not None and hit[-1] and not md.frozen:  # (after the thermostat's application where both fall on one step)
                 md.deposit(s)
         if rescaled:

@@ -9,7 +9,9 @@ Outputs like the reference (`run.py:230-291`): `monitor_{k}.csv` (iter, ns, epot
 `{output}_{k}.npy` trajectory `[N,3,frames]`, `input.yaml` echo.  Frames are staged through a pinned
 host ring with asynchronous copies instead of a blocking `.cpu()` per period.
 With `barostat_pressure` set (constant pressure) the box edges of every frame are saved as
-`{output}_box_{k}.npy` `[frames,3]` and the monitor file gains a `volume` column.  With `exchange_frequency` set (temperature
+`{output}_box_{k}.npy` `[frames,3]` and the monitor file gains a `volume` column; `barostat: crescale` (with `barostat_tau` in ps
+and `barostat_compressibility` in 1/bar) replaces the Monte Carlo barostat by stochastic cell rescaling on the virial (DESIGN
+§20), which also runs on a thermostat ladder.  With `exchange_frequency` set (temperature
 replica exchange on the ladder of `thermostat: csvr`) every monitor file gains a `rung` column — the rung of the
 ladder the replica slot holds at that row — and the acceptance counts are written to `exchange.json` at the end.  With
 `restraints: file.npz` (harmonic position and distance restraints; arrays named as the fields of
@@ -56,6 +58,9 @@ DEFAULTS = dict(
     constraints=None,  # None, "water" (rigid waters) or "hbonds" (rigid waters and X-H bonds): DESIGN §10
     barostat_pressure=None,  # bar; None: constant volume.  Monte Carlo barostat at langevin_temperature: DESIGN §11
     barostat_frequency=25,  # steps between two volume moves
+    barostat="montecarlo",  # with barostat_pressure set: "montecarlo"  or "crescale" (stochastic cell rescaling on the virial: DESIGN §20)
+    barostat_tau=1.0,  # ps: the relaxation time of barostat: crescale
+    barostat_compressibility=4.5e-5,  # 1/bar: the isothermal compressibility barostat: crescale assumes (water)
     minimizer="bfgs",  # what `minimize: N` runs: "bfgs" (scipy L-BFGS-B, one replica) or "fire" (on the device, every replica): DESIGN §13
     thermostat=None,  # None or "csvr": stochastic velocity rescaling between batches of steps (instead of Langevin): DESIGN §14
     thermostat_tau=0.1,  # ps; 0 resamples the kinetic energy at every application
@@ -115,6 +120,11 @@ def get_args(arguments=None):
     args.barostat_frequency = int(args.barostat_frequency)
     if args.barostat_frequency < 1:
         raise ValueError(f"barostat_frequency must be a positive number of steps, got {args.barostat_frequency}")
+    args.barostat = str(args.barostat).lower()
+    if args.barostat not in ("montecarlo", "crescale"):
+        raise ValueError(f"barostat must be 'montecarlo' or 'crescale', got {args.barostat!r}")
+    args.barostat_tau = float(args.barostat_tau)
+    args.barostat_compressibility = float(args.barostat_compressibility)
     if isinstance(args.thermostat, str) and args.thermostat.lower() in ("none", "null", ""):
         args.thermostat = None
     if args.thermostat is not None:
@@ -325,7 +335,15 @@ def dynamics(args, mol, system, forces):
         target = args.thermostat_temperature if args.thermostat_temperature is not None else args.temperature
         thermostat = VelocityRescale(target, tau=args.thermostat_tau, frequency=args.thermostat_frequency,
                                      remove_com=args.remove_com)
-    if args.barostat_pressure is not None:
+    if args.barostat_pressure is not None and args.barostat == "crescale":
+        from .crescale import CRescaleBarostat
+
+        bath = thermostat.targets(args.replicas) if thermostat is not None else args.langevin_temperature
+        if thermostat is None and not bath:
+            raise ValueError("barostat: crescale needs a thermostat: set langevin_temperature, or thermostat: csvr")
+        barostat = CRescaleBarostat(args.barostat_pressure, bath, tau=args.barostat_tau, compressibility=args.barostat_compressibility,
+                                    frequency=args.barostat_frequency)
+    elif args.barostat_pressure is not None:
         from .barostat import MonteCarloBarostat
 
         bath = thermostat.temperature if thermostat is not None else args.langevin_temperature
