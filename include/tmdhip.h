@@ -142,6 +142,8 @@ typedef struct tmdhip_stats {
   int64_t batched_launches;     /* pair + step launches that served several replicas of a cell-list context at once (ABI 8; whole context) */
   int64_t pme_evaluations;      /* reciprocal-space (PME) evaluations of this replica (ABI 9)                  */
   int64_t pme_bytes;            /* device memory held by the context's PME buffers and FFT plans (ABI 9)      */
+  int64_t charge_by_class;      /* 1: the charges are a function of the LJ class and the lean fp32 pair kernel takes the charge
+                                 * products of a pair from its class table; 0: from the gathered records (whole context) */
 } tmdhip_stats;
 
 int tmdhip_abi_version(void);

@@ -204,6 +204,7 @@ class Stats(C.Structure):
         ("batched_launches", C.c_int64),
         ("pme_evaluations", C.c_int64),
         ("pme_bytes", C.c_int64),
+        ("charge_by_class", C.c_int64),
     ]
 
 

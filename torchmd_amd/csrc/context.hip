@@ -329,6 +329,22 @@ int compute_list(tmdhip_ctx *ctx, Replica &rp, const void *pos_v, const double *
   return 0;
 }
 
+// Charge products from the class table (pair_fast_kernel.h: QTAB): decided for the atom set just uploaded.  An fp32 context
+// whose list entries carry the LJ class (<= kEntryTypes classes) and whose scaled charges are, bit for bit, a function of that
+// class gets the class charges uploaded and `charge_by_class` set; every other context keeps the kernel that reads the charge
+// from the gathered record.  TMDHIP_CHARGE_TABLE=0 (read when the context is created) forces the latter.
+int decide_charge_table(tmdhip_ctx *ctx, const int32_t *types, const float *qs, int n) {
+  ctx->charge_by_class = false;
+  const unsigned both = TMDHIP_TERM_LJ | TMDHIP_TERM_ELECTROSTATICS;
+  if (!ctx->charge_table_allowed || ctx->d.dtype != TMDHIP_F32 || ctx->d.ntypes > kEntryTypes || (ctx->d.terms & both) != both) return 0;
+  float qclass[kEntryTypes];
+  if (!charges_by_class(n, types, qs, ctx->d.ntypes, qclass)) return 0;
+  TMD_TRY(ctx->qclass.ensure(sizeof(qclass)));
+  TMD_HIP(hipMemcpy(ctx->qclass.p, qclass, sizeof(float) * ctx->d.ntypes, hipMemcpyHostToDevice));
+  ctx->charge_by_class = true;
+  return 0;
+}
+
 template <typename R>
 int upload_params(tmdhip_ctx *ctx) {
   using R2 = typename Vec<R>::T2;
@@ -340,6 +356,7 @@ int upload_params(tmdhip_ctx *ctx) {
   for (int i = 0; i < n; ++i) qs[i] = q ? (R)((double)q[i] * s) : R(0);
   TMD_TRY(ctx->qs.ensure(sizeof(R) * std::max(n, 1)));
   TMD_HIP(hipMemcpy(ctx->qs.p, qs.data(), sizeof(R) * n, hipMemcpyHostToDevice));
+  if constexpr (std::is_same<R, float>::value) TMD_TRY(decide_charge_table(ctx, d.types_host, q ? qs.data() : nullptr, n));
   std::vector<R2> tab((size_t)T * T);
   const R *A = (const R *)d.lj_A_host, *B = (const R *)d.lj_B_host;
   for (size_t k = 0; k < tab.size(); ++k) {
@@ -449,6 +466,7 @@ int tmdhip_create(tmdhip_ctx **out, const tmdhip_nonbonded_desc *desc) {
   ctx->real_size = desc->dtype == TMDHIP_F32 ? 4 : 8;
   ctx->skin = desc->skin > 0 ? desc->skin : 1.2;  // measured optimum for the C3 water box (tools/time_kernels.py)
   ctx->rlist = desc->cutoff > 0 ? desc->cutoff + ctx->skin : 0;
+  if (const char *e = std::getenv("TMDHIP_CHARGE_TABLE")) ctx->charge_table_allowed = std::atoi(e) != 0;
   const int n = desc->natoms;
   auto cleanup = [&](int rc) {
     tmdhip_destroy(ctx);
@@ -519,7 +537,7 @@ void tmdhip_destroy(tmdhip_ctx *ctx) {
     rp.hostpub = nullptr;
     rp.release();
   }
-  for (DevBuf *b : {&ctx->types, &ctx->qs, &ctx->tab, &ctx->excl_off, &ctx->excl_idx, &ctx->half_skin, &ctx->half_skin2, &ctx->escratch, &ctx->boxes, &ctx->pos_alt_all, &ctx->snap, &ctx->batch_tab, &ctx->chain_tab})
+  for (DevBuf *b : {&ctx->types, &ctx->qs, &ctx->tab, &ctx->qclass, &ctx->excl_off, &ctx->excl_idx, &ctx->half_skin, &ctx->half_skin2, &ctx->escratch, &ctx->boxes, &ctx->pos_alt_all, &ctx->snap, &ctx->batch_tab, &ctx->chain_tab})
     b->release();
   for (auto &ev : ctx->events) {
     (void)hipEventDestroy(ev.first);
@@ -612,6 +630,7 @@ int tmdhip_update_atoms(tmdhip_ctx *ctx, int natoms, const int32_t *types_host, 
     std::vector<float> q(n);
     for (int i = 0; i < n; ++i) q[i] = charges_host ? (float)((double)((const float *)charges_host)[i] * s) : 0.f;
     TMD_HIP(hipMemcpy(ctx->qs.p, q.data(), sizeof(float) * n, hipMemcpyHostToDevice));
+    TMD_TRY(decide_charge_table(ctx, types_host, q.data(), n));
   } else {
     std::vector<double> q(n);
     for (int i = 0; i < n; ++i) q[i] = charges_host ? ((const double *)charges_host)[i] * s : 0.0;
@@ -707,6 +726,7 @@ int tmdhip_get_stats(tmdhip_ctx *ctx, int replica, tmdhip_stats *out) {
   out->batched_launches = ctx->batched_launches;
   out->pme_evaluations = pme_evaluations(ctx, replica);
   out->pme_bytes = pme_bytes(ctx);
+  out->charge_by_class = ctx->charge_by_class ? 1 : 0;
   out->pairs_in_cutoff = (int64_t)pc;
   out->algorithm = ctx->algorithm;
   out->max_neighbours = rp.lg.maxn;

@@ -517,6 +517,7 @@ int migrate(tmdhip_ctx *ctx, tmdhip_comm *c, tmdhip_dd_brick *b, hipStream_t st)
     if (ctx->d.dtype != dtype) return fail("tmdhip_dd_migrate: dtype of the context differs");
     ctx->d.natoms = (int)n;
     ctx->nactive = nown > 0 ? (int)nown : 0x7fffffff;
+    ctx->charge_by_class = false;  // (types and charges arrive on the device: nobody has looked at them)
     TMD_TRY(ctx->types.ensure(sizeof(int) * (size_t)n));
     TMD_TRY(ctx->qs.ensure(sizeof(R) * (size_t)n));
     TMD_TRY(ctx->excl_off.ensure(sizeof(int) * ((size_t)n + 1)));

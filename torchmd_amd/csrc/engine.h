@@ -49,6 +49,7 @@
 #include "chain_plan.h"
 #include "grid_plan.h"
 #include "allpairs_split.h"
+#include "charge_class.h"
 #include "rng.h"
 
 namespace tmd {
@@ -305,6 +306,7 @@ __device__ __forceinline__ size_t list_slot(const ListGeom &lg, int a, int k) {
 }
 
 typedef unsigned v4u __attribute__((ext_vector_type(4)));
+typedef unsigned v3u __attribute__((ext_vector_type(3)));
 
 // k = round-half-even(d / box) by the magic-number trick: fma(d, 1/box, 1.5*2^23) - 1.5*2^23 is exact
 // round-to-nearest-even for |d/box| < 2^22 (v_rndne_f32 would be a fourth instruction).  It differs from
@@ -598,6 +600,11 @@ struct tmdhip_ctx {
   unsigned run_published_seq = 0;
   const double *run_published_energies = nullptr;
   tmd::DevBuf types, qs, tab, excl_off, excl_idx;
+  // charge products from the class table (context.hip: decide_charge_table): the charges of the current atom set are a
+  // function of the LJ class; qclass = float[ntypes], the scaled charge of every class
+  tmd::DevBuf qclass;
+  bool charge_by_class = false;
+  bool charge_table_allowed = true;  // TMDHIP_CHARGE_TABLE=0 at tmdhip_create: never
   // per-atom Verlet skins (tmdhip_set_skin_weights): half_skin[i] = w_i * skin / 2 and its square, original atom
   // order; empty = skin / 2 for every atom
   tmd::DevBuf half_skin, half_skin2;

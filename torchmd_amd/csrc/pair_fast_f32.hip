@@ -11,25 +11,29 @@ int launch_pair_fast_f32(tmdhip_ctx *ctx, Replica &rp, const PairConsts<float> &
   const int apw = rp.lg.apw;
   const int waves = (n + apw - 1) / apw;
   const bool lj = c.terms & TMDHIP_TERM_LJ, el = c.terms & TMDHIP_TERM_ELECTROSTATICS;
-#define TMD_LAUNCH_FAST_T(L, A, B, F)       \
-  if (c.switch_on && A) {                  \
-    TMD_LAUNCH_FAST_S(L, A, B, true, F);   \
-  } else {                                 \
-    TMD_LAUNCH_FAST_S(L, A, B, false, F);  \
+  // (Q: charge products from the class table, pair_fast_kernel.h: QTAB)
+  const bool qtab = TMD_CHARGE_TABLE && ctx->charge_by_class;
+#define TMD_LAUNCH_FAST_T(L, A, B, F, Q)       \
+  if (c.switch_on && A) {                     \
+    TMD_LAUNCH_FAST_S(L, A, B, true, F, Q);   \
+  } else {                                    \
+    TMD_LAUNCH_FAST_S(L, A, B, false, F, Q);  \
   }
-#define TMD_LAUNCH_FAST_S(L, A, B, S, F)                                                                                  \
-  launch_with_events(list_pair_fast_f32_kernel<L, A, B, ENERGY, S, F>, dim3(npair8 + (F ? fstep.nstep_blocks : 0)),        \
+#define TMD_LAUNCH_FAST_S(L, A, B, S, F, Q)                                                                               \
+  launch_with_events(list_pair_fast_f32_kernel<L, A, B, ENERGY, S, F, Q>, dim3(npair8 + (F ? fstep.nstep_blocks : 0)),     \
                      dim3(kFastThreads), 0u, st, e0, e1, n, rp.sorted.as<float4>(), rp.stype.as<int>(), rp.order.as<int>(), \
                      ctx->d.ntypes, ctx->tab.as<float2>(), rp.nlist.as<unsigned>(), rp.nneigh.as<int>(), rp.lg.maxn, c, f,  \
                      overwrite, ctx->escratch.as<double>(), rp.pub_ptr, rp.pub_val, rp.extent.as<int>(),                  \
-                     rp.flags.as<int>(), lmode, F ? fl->fst : nullptr, fstep, rp.padgen.as<int>())
-#define TMD_LAUNCH_FAST(L, F)               \
-  if (lj && el) {                           \
-    TMD_LAUNCH_FAST_T(L, true, true, F);    \
-  } else if (lj) {                          \
-    TMD_LAUNCH_FAST_T(L, true, false, F);   \
-  } else {                                  \
-    TMD_LAUNCH_FAST_T(L, false, true, F);   \
+                     rp.flags.as<int>(), lmode, F ? fl->fst : nullptr, fstep, rp.padgen.as<int>(), ctx->qclass.as<float>())
+#define TMD_LAUNCH_FAST(L, F)                             \
+  if (lj && el && qtab) {                                 \
+    TMD_LAUNCH_FAST_T(L, true, true, F, TMD_CHARGE_TABLE != 0); \
+  } else if (lj && el) {                                  \
+    TMD_LAUNCH_FAST_T(L, true, true, F, false);           \
+  } else if (lj) {                                        \
+    TMD_LAUNCH_FAST_T(L, true, false, F, false);          \
+  } else {                                                \
+    TMD_LAUNCH_FAST_T(L, false, true, F, false);          \
   }
   constexpr int wpb = kFastThreads / 64;
   const int npair8 = ((waves + wpb - 1) / wpb + 7) / 8 * 8;

@@ -22,22 +22,26 @@ int launch_pair_fast_f32_batch(tmdhip_ctx *ctx, int rep0, const PairConsts<float
   const bool lj = c.terms & TMDHIP_TERM_LJ, el = c.terms & TMDHIP_TERM_ELECTROSTATICS;
   const dim3 grid((unsigned)bl.nrep * (unsigned)(bl.pair_blocks + bl.step_blocks)), block(kFastThreads);
   const BatchRep *reps = ctx->batch_tab.as<BatchRep>() + rep0;
-#define TMD_B_S(L, A, B, E, S, F)                                                                                          \
-  hipLaunchKernelGGL((list_pair_fast_f32_batch_kernel<L, A, B, E, S, F>), grid, block, 0, st, ctx->d.natoms, ctx->d.ntypes, \
-                     ctx->tab.as<float2>(), c, reps, bl)
-#define TMD_B_T(L, A, B, E, F)        \
-  if (c.switch_on && A) {            \
-    TMD_B_S(L, A, B, E, true, F);    \
-  } else {                           \
-    TMD_B_S(L, A, B, E, false, F);   \
+  // (Q: charge products from the class table, pair_fast_kernel.h: QTAB)
+  const bool qtab = TMD_CHARGE_TABLE && ctx->charge_by_class;
+#define TMD_B_S(L, A, B, E, S, F, Q)                                                                                          \
+  hipLaunchKernelGGL((list_pair_fast_f32_batch_kernel<L, A, B, E, S, F, Q>), grid, block, 0, st, ctx->d.natoms, ctx->d.ntypes, \
+                     ctx->tab.as<float2>(), c, reps, bl, ctx->qclass.as<float>())
+#define TMD_B_T(L, A, B, E, F, Q)       \
+  if (c.switch_on && A) {              \
+    TMD_B_S(L, A, B, E, true, F, Q);   \
+  } else {                             \
+    TMD_B_S(L, A, B, E, false, F, Q);  \
   }
-#define TMD_B_TERMS(L, E, F)          \
-  if (lj && el) {                     \
-    TMD_B_T(L, true, true, E, F);     \
-  } else if (lj) {                    \
-    TMD_B_T(L, true, false, E, F);    \
-  } else {                            \
-    TMD_B_T(L, false, true, E, F);    \
+#define TMD_B_TERMS(L, E, F)                               \
+  if (lj && el && qtab) {                                  \
+    TMD_B_T(L, true, true, E, F, TMD_CHARGE_TABLE != 0);   \
+  } else if (lj && el) {                                   \
+    TMD_B_T(L, true, true, E, F, false);                   \
+  } else if (lj) {                                         \
+    TMD_B_T(L, true, false, E, F, false);                  \
+  } else {                                                 \
+    TMD_B_T(L, false, true, E, F, false);                  \
   }
 #define TMD_B_MODE(L)                 \
   if (energy) {                       \

@@ -52,6 +52,12 @@ namespace tmd {
 #ifndef TMD_BASE_ENTRIES_AT_ONCE
 #define TMD_BASE_ENTRIES_AT_ONCE 4
 #endif
+#ifndef TMD_PROLOGUE_BATCH  // (A/B builds: 0 stages the table behind the atom's loads and reads the padding words behind the barrier)
+#define TMD_PROLOGUE_BATCH 1
+#endif
+#ifndef TMD_CHARGE_TABLE  // (A/B builds: 0 leaves the QTAB variants out, every context runs the kernel that gathers the charge)
+#define TMD_CHARGE_TABLE 1
+#endif
 constexpr int kFastWaves = 5;  // waves per SIMD of the pipelined loop (94 VGPRs); measured at 4 / 6 / 7 / 8: docs/history/round3.md
 // Waves per SIMD a variant is compiled for.  Round 6: the variants with energies and / or the LJ switching function run the
 // pipelined loop too — at five waves with their entries evaluated one at a time (kEntriesAtOnce, below), except the variant
@@ -110,14 +116,26 @@ static __device__ unsigned long long g_pair_timeline[4 * 65536];
 // launch.  list_pair_fast_f32_kernel passes blockIdx.x / gridDim.x and its own arguments; the replica-batched kernel
 // (list_pair_fast_f32_batch_kernel, round 6) the block's position inside its replica's share of the grid and that replica's
 // buffers from a device table.
-template <int LPA, bool LJ, bool ELEC, bool ENERGY, bool SWITCH, int FUSED, bool TABLE = false>
+//
+// QTAB (LJ and ELEC; the launchers choose it when the context's charges are a function of the LJ class, context.hip:
+// decide_charge_table): the charge products of a pair come from the class table instead of the gathered record.  The table row
+// of class i is then 512 bytes — {-12 A, 6 B}[32] at +0, {q_i q_j, (q_i 2 krf) q_j}[32] at +256, both products formed in the
+// prologue with the operands and the order the per-pair code uses (`pi.w * pjw`, `qi2k * pjw`): results are bit-identical — the
+// gathers are 12 bytes (buffer_load_dwordx3; the records keep their 16-byte stride and their .w for everybody else), and two
+// multiplies per entry, the .w of both register sets, pi.w and qi2k go away.  `qclass`: float[ntypes], the classes' scaled charges.
+// (Measured, profiles/r07_charge_table_ab.txt: 96 -> 88 VGPRs, 4.7 % fewer VALU instructions, the same 16.0 texture-addresser
+// cycles per gather at either width; with the batched prologue the launch 43.7 -> 42.7 us.  List words two groups ahead in the
+// freed registers: the compiler copies the carried word behind a full wait, or spills; not kept.)
+template <int LPA, bool LJ, bool ELEC, bool ENERGY, bool SWITCH, int FUSED, bool TABLE = false, bool QTAB = false>
 __device__ __forceinline__ void pair_fast_body(
     const unsigned bid, const unsigned nblocks,
     int n, const float4 *__restrict__ sorted, const int *__restrict__ stype, const int *__restrict__ order,
     int ntypes, const float2 *__restrict__ tab, const unsigned *__restrict__ nlist,
     const int *__restrict__ nneigh, int maxn, const PairConsts<float> &c, float *__restrict__ forces, int overwrite,
     double *__restrict__ energies, unsigned *publish, unsigned publish_value, const int *__restrict__ ext,
-    int *lflags, int lmode, const FusedStatic *__restrict__ fst, const FusedStep &fstep, int *__restrict__ padgen) {
+    int *lflags, int lmode, const FusedStatic *__restrict__ fst, const FusedStep &fstep, int *__restrict__ padgen,
+    const float *__restrict__ qclass = nullptr) {
+  static_assert(!QTAB || (LJ && ELEC), "the charge table rides on the LJ class table");
   constexpr int APW = 64 / LPA;
   constexpr int UNROLL = 4;
   constexpr bool kPipelined = ELEC;  // the software-pipelined loop over the unchecked groups (below)
@@ -151,7 +169,8 @@ __device__ __forceinline__ void pair_fast_body(
       if (FUSED == 1 || FUSED == 2) lflags[F_REBUILD0 + parity] = 0;
     }
   }
-  __shared__ __align__(16) float2 stab[kEntryTypes * kEntryTypes];  // row of type i: 32 x {-12 A, 6 B}
+  constexpr int kRowShift = QTAB ? 9 : 8;  // log2(bytes of a table row)
+  __shared__ __align__(16) float2 stab[kEntryTypes * kEntryTypes * (QTAB ? 2 : 1)];  // row of type i: 32 x {-12 A, 6 B} (QTAB: + 32 x {qq, rq})
   const int lane = threadIdx.x & 63;
   // pair blocks of the launch (FUSED: step blocks follow them)
   const unsigned npair = FUSED ? nblocks - (unsigned)fstep.nstep_blocks : nblocks;
@@ -185,20 +204,75 @@ __device__ __forceinline__ void pair_fast_body(
   float4 pi = make_float4(0.f, 0.f, 0.f, 0.f);
   int nn = 0, oi = 0;
   unsigned trow = 0;  // byte offset of this atom's row of the LDS table
+  // (only the rows of existing classes are ever read: ntypes x 32 entries instead of 32 x 32 — at 10^6 LJ atoms
+  // with 64 atoms per block the full table was 15 625 x 8 KB of staging)
+  // one table slot: what it is made of (columns past the last class hold zeros: the garbage entries of a checked group may
+  // point there) ...
+  // (loads without a branch, from a slot that exists: nothing stands between the requests of the batch)
+  auto stage_load = [&](int t, float2 &ab, float &qi, float &qj) {
+    const int ti = min(t >> 5, ntypes - 1), tj = min(t & 31, ntypes - 1);
+    ab = tab[ti * ntypes + tj];
+    qi = qj = 0.f;
+    if constexpr (QTAB) qi = qclass[ti], qj = qclass[tj];
+  };
+  // ... and its store (QTAB: the two charge products in the per-pair code's arithmetic, see the head comment)
+  auto stage_store = [&](int t, float2 ab, float qi, float qj) {
+    if (t >= ntypes * kEntryTypes) return;
+    const int ti = t >> 5, tj = t & 31;
+    if (tj >= ntypes) ab = make_float2(0.f, 0.f), qi = qj = 0.f;
+    if constexpr (QTAB) {
+      stab[ti * 2 * kEntryTypes + tj] = make_float2(-12.0f * ab.x, 6.0f * ab.y);
+      stab[ti * 2 * kEntryTypes + kEntryTypes + tj] = make_float2(qi * qj, (qi * (2.0f * c.krf)) * qj);
+    } else {
+      stab[t] = make_float2(-12.0f * ab.x, 6.0f * ab.y);
+    }
+  };
+  int pad_now = 0, pad_have = 0;  // rebuild count / the count at which this wave's rows were padded (kLmPadded, below)
+#if TMD_PROLOGUE_BATCH
+  // The table's sources (this thread's first slot: the whole table up to 8 classes) and the two words of the padding test
+  // belong to that batch too: staged behind the atom's loads, and looked at behind the barrier, they were two more dependent
+  // round trips in front of the first gather (with the class charges, three).  Nothing is waited for before all are requested.
+  int sty = 0;
   if (active) {
     pi = sorted[a];
     nn = nneigh[a];
-    trow = (unsigned)stype[a] << 8;
+    sty = stype[a];
     oi = order[a];
   }
-  // (only the rows of existing classes are ever read: ntypes x 32 entries instead of 32 x 32 — at 10^6 LJ atoms
-  // with 64 atoms per block the full table was 15 625 x 8 KB of staging)
-  for (int t = threadIdx.x; t < ntypes * kEntryTypes; t += blockDim.x) {
-    const int ti = t >> 5, tj = t & 31;
-    float2 ab = make_float2(0.f, 0.f);
-    if (tj < ntypes) ab = tab[ti * ntypes + tj];
-    stab[t] = make_float2(-12.0f * ab.x, 6.0f * ab.y);
+  if (lmode & kLmPadded) {
+    pad_now = lflags[F_NREBUILD];
+    pad_have = padgen[wave];
   }
+  {
+    float2 ab;
+    float qi, qj;
+    stage_load((int)threadIdx.x, ab, qi, qj);
+    // (requests above, uses below: the compiler would form the row offset beside the class's load and sink the table's loads
+    // into the branch of their store, each behind a wait of its own)
+    asm volatile("" : "+v"(sty), "+v"(ab.x), "+v"(ab.y), "+v"(qi), "+v"(qj));
+    stage_store((int)threadIdx.x, ab, qi, qj);
+  }
+  for (int t = threadIdx.x + blockDim.x; t < ntypes * kEntryTypes; t += blockDim.x) {
+    float2 ab;
+    float qi, qj;
+    stage_load(t, ab, qi, qj);
+    stage_store(t, ab, qi, qj);
+  }
+  trow = (unsigned)sty << kRowShift;
+#else
+  if (active) {
+    pi = sorted[a];
+    nn = nneigh[a];
+    trow = (unsigned)stype[a] << kRowShift;
+    oi = order[a];
+  }
+  for (int t = threadIdx.x; t < ntypes * kEntryTypes; t += blockDim.x) {
+    float2 ab;
+    float qi, qj;
+    stage_load(t, ab, qi, qj);
+    stage_store(t, ab, qi, qj);
+  }
+#endif
   __syncthreads();
 
   const int myiters = (nn - sub + LPA - 1) / LPA;  // entries kk < myiters are real for this lane
@@ -218,8 +292,12 @@ __device__ __forceinline__ void pair_fast_body(
   // launch still runs its tail checked (the entries it has just stored are for the launches that follow).
   bool padded = false;
   if (lmode & kLmPadded) {
-    const int now = __builtin_amdgcn_readfirstlane(lflags[F_NREBUILD]);
-    const int have = __builtin_amdgcn_readfirstlane(padgen[wave]);
+#if !TMD_PROLOGUE_BATCH
+    pad_now = lflags[F_NREBUILD];
+    pad_have = padgen[wave];
+#endif
+    const int now = __builtin_amdgcn_readfirstlane(pad_now);
+    const int have = __builtin_amdgcn_readfirstlane(pad_have);
     padded = have == now;
     if (!padded) {
       const unsigned pad = pad_entry_for(c, n, pi.x, pi.y, pi.z);
@@ -238,7 +316,7 @@ __device__ __forceinline__ void pair_fast_body(
       __builtin_amdgcn_make_buffer_rsrc(const_cast<float4 *>(sorted), 0, (n + 2) * 16, 0x00020000);  // (+ the two dummy records)
   const char *tbase = reinterpret_cast<const char *>(stab);
   const float two_krf = 2.0f * c.krf;
-  const float qi2k = pi.w * two_krf;
+  const float qi2k = pi.w * two_krf;  // (QTAB: dead, like pi.w)
   auto in_vgpr = [](float sv) {  // a uniform value the compiler can no longer keep in an SGPR
     float v;
     asm("v_mov_b32 %0, %1" : "=v"(v) : "s"(sv));
@@ -300,7 +378,8 @@ __device__ __forceinline__ void pair_fast_body(
 #pragma unroll
     for (int u = h0; u < h0 + HB; ++u) {
       const bool valid = UNCHECKED || (kk0 + u < myiters);  // padding words are garbage
-      const float pjw = __uint_as_float(raw[u].w);
+      float pjw = 0.f;
+      if constexpr (!QTAB) pjw = __uint_as_float(raw[u].w);
       const bool hit = valid && (r2[u] <= vr2max);
       float step = 1.f;
       if (ARITH_CUT) asm("v_fma_f32 %0, %1, %2, %3 clamp" : "=v"(step) : "v"(r2[u]), "v"(cut_h), "v"(cut_c0));
@@ -329,9 +408,16 @@ __device__ __forceinline__ void pair_fast_body(
       }
       float fs;  // (dE/dr) / r; rejected entries of a checked group may produce inf/NaN here, the select below discards them
       if (ELEC) {
-        const float qq = pi.w * pjw;
+        float qq, rq;
+        if constexpr (QTAB) {
+          const float2 qr = *reinterpret_cast<const float2 *>(tbase + tab[u] + kEntryTypes * sizeof(float2));
+          qq = qr.x, rq = qr.y;
+        } else {
+          qq = pi.w * pjw;
+          rq = qi2k * pjw;
+        }
         const float g = __builtin_fmaf(-qq, rinv[u], P);
-        fs = __builtin_fmaf(rinv2, g, qi2k * pjw);
+        fs = __builtin_fmaf(rinv2, g, rq);
         if (ENERGY) {  // krf = crf = 0: plain Coulomb
           const float eel = qq * __builtin_fmaf(vkrf, r2[u], rinv[u] - vcrf);
           e_el = ARITH_CUT ? __builtin_fmaf(step, eel, e_el) : e_el + (hit ? eel : 0.f);
@@ -351,12 +437,16 @@ __device__ __forceinline__ void pair_fast_body(
   };
 
   static_assert(UNROLL == 4, "one dwordx4 of list per lane and group");
+  using rec_t = std::conditional_t<QTAB, v3u, v4u>;  // a gathered record: {x, y, z} or {x, y, z, q}
   // issue the 4 gathers of the group whose list word is `w` and form its table offsets (unchecked: n <= 2^20, bits
   // 24..27 of an entry are zero; checked: padding words are garbage, the offset is masked)
-  auto issue = [&](auto unchecked, const v4u &w, v4u (&raw)[UNROLL], unsigned (&tab)[UNROLL]) {
+  auto issue = [&](auto unchecked, const v4u &w, rec_t (&raw)[UNROLL], unsigned (&tab)[UNROLL]) {
     const unsigned entry[UNROLL] = {w.x, w.y, w.z, w.w};
 #pragma unroll
-    for (int u = 0; u < UNROLL; ++u) raw[u] = __builtin_amdgcn_raw_buffer_load_b128(srsrc, entry[u] & kEntryOffMask, 0, 0);
+    for (int u = 0; u < UNROLL; ++u) {
+      if constexpr (QTAB) raw[u] = __builtin_amdgcn_raw_buffer_load_b96(srsrc, entry[u] & kEntryOffMask, 0, 0);
+      else raw[u] = __builtin_amdgcn_raw_buffer_load_b128(srsrc, entry[u] & kEntryOffMask, 0, 0);
+    }
 #pragma unroll
     for (int u = 0; u < UNROLL; ++u) tab[u] = trow | (decltype(unchecked)::value ? entry[u] >> 24 : (entry[u] >> 24) & 0xF8u);
   };
@@ -382,7 +472,7 @@ __device__ __forceinline__ void pair_fast_body(
   // that order against the compiler's preference.
   auto checked_loop = [&](auto image) {  // per-lane validity; not pipelined (the tail is short)
     for (; g < gall; ++g) {
-      v4u raw[UNROLL];
+      rec_t raw[UNROLL];
       unsigned tab[UNROLL];
       issue(checked_t{}, word, raw, tab);
       __builtin_amdgcn_sched_barrier(0);
@@ -402,7 +492,7 @@ __device__ __forceinline__ void pair_fast_body(
     // not fill the VALU pipe).  94 VGPRs: five waves per SIMD.
     if constexpr (!kPipelined) {  // (LJ-only systems: short lists, the plain loop at two waves more per SIMD)
       for (; g < gfull; ++g) {
-        v4u raw[UNROLL];
+        rec_t raw[UNROLL];
         unsigned tab[UNROLL];
         issue(unchecked_t{}, word, raw, tab);
         __builtin_amdgcn_sched_barrier(0);
@@ -411,7 +501,7 @@ __device__ __forceinline__ void pair_fast_body(
         group(fused_image{}, unchecked_t{}, tab, raw, g * UNROLL);
       }
     } else if (gfull > 0) {
-      v4u ra[UNROLL], rb[UNROLL];
+      rec_t ra[UNROLL], rb[UNROLL];
       unsigned ta[UNROLL], tb[UNROLL];
       issue(unchecked_t{}, word, ra, ta);
       __builtin_amdgcn_sched_barrier(0);
@@ -491,7 +581,7 @@ __device__ __forceinline__ void pair_fast_body(
   }
 }
 
-template <int LPA, bool LJ, bool ELEC, bool ENERGY, bool SWITCH, int FUSED = 0>
+template <int LPA, bool LJ, bool ELEC, bool ENERGY, bool SWITCH, int FUSED = 0, bool QTAB = false>
 // (LJ-only systems — liquid argon, short lists of ~90 entries — run the plain loop at more waves per SIMD: six, 10^6 atoms
 // 175.5 -> 168.5 us/step in round 3; seven since round 6, 139.8 -> 136-138; with charges the pipelined loop at 5 waves wins,
 // docs/history/round3.md)
@@ -500,10 +590,11 @@ __global__ __launch_bounds__(kFastThreads, fast_waves(ELEC, ENERGY, SWITCH)) voi
     int ntypes, const float2 *__restrict__ tab, const unsigned *__restrict__ nlist,
     const int *__restrict__ nneigh, int maxn, PairConsts<float> c, float *__restrict__ forces, int overwrite,
     double *__restrict__ energies, unsigned *publish, unsigned publish_value, const int *__restrict__ ext,
-    int *lflags, int lmode, const FusedStatic *__restrict__ fst, FusedStep fstep, int *__restrict__ padgen) {
-  pair_fast_body<LPA, LJ, ELEC, ENERGY, SWITCH, FUSED>(blockIdx.x, gridDim.x, n, sorted, stype, order, ntypes, tab, nlist, nneigh, maxn, c,
-                                                       forces, overwrite, energies, publish, publish_value, ext, lflags, lmode, fst,
-                                                       fstep, padgen);
+    int *lflags, int lmode, const FusedStatic *__restrict__ fst, FusedStep fstep, int *__restrict__ padgen,
+    const float *__restrict__ qclass) {
+  pair_fast_body<LPA, LJ, ELEC, ENERGY, SWITCH, FUSED, false, QTAB>(blockIdx.x, gridDim.x, n, sorted, stype, order, ntypes, tab, nlist, nneigh,
+                                                                    maxn, c, forces, overwrite, energies, publish, publish_value, ext, lflags,
+                                                                    lmode, fst, fstep, padgen, qclass);
 }
 
 // ---- replicas of a cell-list context in ONE launch (round 6) ----------------------------------------------------------------
@@ -518,9 +609,10 @@ __global__ __launch_bounds__(kFastThreads, fast_waves(ELEC, ENERGY, SWITCH)) voi
 // the headline variant spilled 88 bytes per lane — the step blocks read the replica's FusedStatic, a pointer out of the table,
 // with flat loads into VGPRs.  Read through the constant address space (md_step.h: load_uniform) the fields are in SGPRs as
 // in the plain kernel: 96 VGPRs, no scratch; C3 as ONE replica through this kernel 67.8 -> 61.x us/step, the plain kernel's.)
-template <int LPA, bool LJ, bool ELEC, bool ENERGY, bool SWITCH, int FUSED>
+template <int LPA, bool LJ, bool ELEC, bool ENERGY, bool SWITCH, int FUSED, bool QTAB = false>
 __global__ __launch_bounds__(kFastThreads, TMD_BATCH_WAVES) void list_pair_fast_f32_batch_kernel(
-    int n, int ntypes, const float2 *__restrict__ tab, PairConsts<float> c, const BatchRep *__restrict__ reps, BatchLaunch bl) {
+    int n, int ntypes, const float2 *__restrict__ tab, PairConsts<float> c, const BatchRep *__restrict__ reps, BatchLaunch bl,
+    const float *__restrict__ qclass) {
   static_assert(FUSED != 0, "the batched launch is an MD-step launch");
   const unsigned per_pair = (unsigned)bl.pair_blocks, per_step = (unsigned)bl.step_blocks;
   const unsigned all_pair = per_pair * (unsigned)bl.nrep;
@@ -549,10 +641,10 @@ __global__ __launch_bounds__(kFastThreads, TMD_BATCH_WAVES) void list_pair_fast_
   fs.near_host = (bits & kBlReports) ? S.hostpub + 1 + (fs.seq & 1u) : nullptr;
   fs.parity = (bits & kBlNextParity) ? 1 : 0;
   // (TABLE: the step blocks read the replica's FusedStatic through the constant address space, md_step.h: load_uniform)
-  pair_fast_body<LPA, LJ, ELEC, ENERGY, SWITCH, FUSED, true>(
+  pair_fast_body<LPA, LJ, ELEC, ENERGY, SWITCH, FUSED, true, QTAB>(
       is_pair ? local : per_pair + local, per_pair + per_step, n, S.sorted[cs], S.stype, S.order, ntypes, tab, S.nlist, S.nneigh, S.maxn, c,
       S.forces, 1, S.escratch, (bits & kBlPublish) ? S.hostpub : nullptr, bl.pub[r], S.ext, S.lflags, (int)(bits & kBlLmodeMask), S.fst, fs,
-      S.padgen);
+      S.padgen, qclass);
 }
 
 

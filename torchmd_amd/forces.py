@@ -1069,6 +1069,7 @@ class Forces:
             "fused_step_timeouts": int(st.fused_step_timeouts),
             "pme_evaluations": int(st.pme_evaluations),
             "pme_bytes": int(st.pme_bytes),
+            "charge_by_class": int(st.charge_by_class),
         }
 
     def enable_timing(self, pos, on=True, every=1, limit=0, skip=0, interior_only=False):
