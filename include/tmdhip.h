@@ -484,6 +484,40 @@ int tmdhip_restraint_apply(tmdhip_ctx *ctx, const void *pos_dev, const double *b
 /* The restraint energies of the last step of the last tmdhip_md_run: out_host double [R][2] = (position, distance).  One small
  * copy and a synchronisation of the stream; zeros without restraints. */
 int tmdhip_restraint_energy(tmdhip_ctx *ctx, double *out_host, void *stream);
+/* Generalized-Born implicit solvent, OBC2 (Onufriev, Bashford, Case 2004) with the ACE-type surface-area term, for contexts with
+ * open boundaries (added to ABI 11: new symbols only).  Per atom: intrinsic radius r_i (A), descreening scale s_i, and the
+ * context's charges.  rho_i = r_i - 0.09, sigma_j = s_j rho_j; every ordered pair i != j counts (bonded pairs too): no minimum
+ * image, no cutoff, no exclusions.
+ *   I_i = (1/2) sum_j t(r_ij; rho_i, sigma_j), psi = rho_i I_i, B_i = 1 / (1/rho_i - tanh(psi - 0.8 psi^2 + 4.85 psi^3) / r_i)
+ *   E_GB = -(k_e/2)(1/eps_in - 1/eps_out) sum_ij q_i q_j / sqrt(r^2 + B_i B_j exp(-r^2 / (4 B_i B_j)))   (i = j included)
+ *   E_SA = sum_i 4 pi gamma (r_i + r_probe)^2 (r_i / B_i)^6
+ * tmdhip_set_gb validates, uploads and synchronises; enable = 0 releases the state.  Refused before any launch: a null argument
+ * or a wrong struct size, a radius <= 0.09 or not finite, a scale < 0, a dielectric constant <= 0, a context with passive atoms,
+ * with virtual sites, with PME or with the reaction field (which already stands for the solvent); and by every evaluation, a
+ * box with a non-zero edge.
+ * With the model in place tmdhip_md_run integrates under the total force exactly as it does with restraints: the impulse
+ * dt a(x) / (1 - gamma dt) between launches, and after the last step a finishing launch (dt/2 a to the velocities, F to
+ * forces_dev, the energies).  Three pair passes with a per-atom close each; every pair is visited from both sides and every
+ * partial sum has one writer: no floating-point atomics, two calls on the same state give the same bits. */
+typedef struct tmdhip_gb_desc {
+  int32_t struct_size; /* = sizeof(tmdhip_gb_desc) */
+  int32_t enable;
+  const double *radii_host; /* [N] intrinsic radii, A */
+  const double *scale_host; /* [N] descreening scales */
+  double solute_dielectric, solvent_dielectric; /* eps_in, eps_out */
+  double surface_tension;   /* gamma, kcal/mol/A^2; 0: no surface-area term */
+  double probe_radius;      /* A */
+} tmdhip_gb_desc;
+int tmdhip_set_gb(tmdhip_ctx *ctx, const tmdhip_gb_desc *desc);
+/* One evaluation at pos_dev (real [R][N][3], the context's dtype); box_host [R][3] must be all zero.  Whatever is not NULL is
+ * served: forces_dev += F; vel_dev += kick F / m (needs mass_dev, real [N]; rows with m <= 0 are left alone); energies_dev
+ * (double [R][2]) = (GB, SA), overwritten.  A context without the model: nothing is launched, energies are zeroed. */
+int tmdhip_gb_apply(tmdhip_ctx *ctx, const void *pos_dev, const double *box_host, void *forces_dev, void *vel_dev,
+                    const void *mass_dev, double kick, double *energies_dev, void *stream);
+/* The (GB, SA) energies of the last step of the last tmdhip_md_run: out_host double [R][2]; zeros without the model. */
+int tmdhip_gb_energy(tmdhip_ctx *ctx, double *out_host, void *stream);
+/* The effective Born radii B_i of the last evaluation: out_host double [R][N] (zeros before the first one). */
+int tmdhip_gb_born_radii(tmdhip_ctx *ctx, double *out_host);
 /* Well-tempered metadynamics on one or two collective variables (added to ABI 11: new symbols only).
  *   CVs       kind 0, distance: r = |minimum image of (x_i - x_j)| (atoms[c][0..1]), not periodic, grid [grid_min, grid_max];
  *             kind 1, dihedral: the torsion of atoms[c][0..3] in radians with the sign of the bonded term, from the

@@ -8,7 +8,8 @@ virial: stochastic cell rescaling, one target per replica) and `torchmd_amd.Velo
 rescaling, one target temperature per replica) and `torchmd_amd.ReplicaExchange` / `torchmd_amd.temperature_ladder`
 (temperature replica exchange on that thermostat's ladder) and `torchmd_amd.Restraints` (harmonic position and distance
 restraints with one target per replica) and `torchmd_amd.Metadynamics` (well-tempered metadynamics on distance and
-dihedral collective variables); all imported on first use only,
+dihedral collective variables) and `torchmd_amd.GeneralizedBorn` (OBC2 generalized-Born / surface-area implicit solvent for
+systems with open boundaries); all imported on first use only,
 backed by hand-written HIP kernels in `torchmd_amd/lib/libtmdhip.so` (C ABI: include/tmdhip.h).
 """
 
@@ -45,12 +46,17 @@ def __getattr__(name):
         from .metadynamics import Metadynamics
 
         return Metadynamics
+    if name == "GeneralizedBorn":
+        from .implicit import GeneralizedBorn
+
+        return GeneralizedBorn
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 
 __all__ = [
     "CRescaleBarostat",
     "Forces",
+    "GeneralizedBorn",
     "Integrator",
     "Metadynamics",
     "MonteCarloBarostat",

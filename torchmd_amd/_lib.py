@@ -264,6 +264,19 @@ class RestraintDesc(C.Structure):
     ]
 
 
+class GbDesc(C.Structure):
+    _fields_ = [
+        ("struct_size", C.c_int32),
+        ("enable", C.c_int32),
+        ("radii_host", C.c_void_p),
+        ("scale_host", C.c_void_p),
+        ("solute_dielectric", C.c_double),
+        ("solvent_dielectric", C.c_double),
+        ("surface_tension", C.c_double),
+        ("probe_radius", C.c_double),
+    ]
+
+
 class MetadDesc(C.Structure):
     _fields_ = [
         ("struct_size", C.c_int32),
@@ -414,6 +427,13 @@ SIGNATURES = {
         [C.c_void_p, C.c_void_p, C.POINTER(C.c_double), C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p],
     ),
     "tmdhip_restraint_energy": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.c_void_p]),
+    "tmdhip_set_gb": (C.c_int, [C.c_void_p, C.POINTER(GbDesc)]),
+    "tmdhip_gb_apply": (
+        C.c_int,
+        [C.c_void_p, C.c_void_p, C.POINTER(C.c_double), C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p],
+    ),
+    "tmdhip_gb_energy": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.c_void_p]),
+    "tmdhip_gb_born_radii": (C.c_int, [C.c_void_p, C.POINTER(C.c_double)]),
     "tmdhip_set_metadynamics": (C.c_int, [C.c_void_p, C.POINTER(MetadDesc)]),
     "tmdhip_metad_apply": (
         C.c_int,

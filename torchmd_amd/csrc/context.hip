@@ -553,6 +553,7 @@ void tmdhip_destroy(tmdhip_ctx *ctx) {
   tmd::vsite_release(ctx);
   tmd::restraint_release(ctx);
   tmd::metad_release(ctx);
+  tmd::gb_release(ctx);
   tmd::virial_release(ctx);
   delete ctx;
 }

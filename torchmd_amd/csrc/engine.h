@@ -653,6 +653,8 @@ struct tmdhip_ctx {
   void *restraints = nullptr;
   // the metadynamics bias (tmdhip_set_metadynamics), metad.hip; null: off (no launch, nothing allocated)
   void *metad = nullptr;
+  // the generalized-Born implicit solvent (tmdhip_set_gb), gb.hip; null: off (no launch, nothing allocated)
+  void *gb = nullptr;
   // the molecule table and scratch of the pressure observable (tmdhip_set_molecules), virial.hip; null: not set
   void *virial = nullptr;
   // timing of the dominant kernel
@@ -881,6 +883,16 @@ int metad_impulse_each(tmdhip_ctx *ctx, const void *const *pos_each, const doubl
                        hipStream_t st);
 int metad_finish(tmdhip_ctx *ctx, const void *pos, const double *box_host, void *vel, void *forces, const void *mass, double kick,
                  hipStream_t st);
+// gb.hip (only called with ctx->gb set, except the release): the same four places, for the generalized-Born implicit solvent
+// (box_host is checked by gb_run_check: open boundaries only)
+void gb_release(tmdhip_ctx *ctx);
+int gb_run_check(tmdhip_ctx *ctx, const tmdhip_md_desc *d, double *impulse_kick, hipStream_t st);
+int gb_impulse(tmdhip_ctx *ctx, int rep0, int nrep, const void *pos, const double *box_host, void *vel, const void *mass, double kick,
+               hipStream_t st);
+int gb_impulse_each(tmdhip_ctx *ctx, const void *const *pos_each, const double *box_host, void *vel, const void *mass, double kick,
+                    hipStream_t st);
+int gb_finish(tmdhip_ctx *ctx, const void *pos, const double *box_host, void *vel, void *forces, const void *mass, double kick,
+              hipStream_t st);
 int64_t pme_evaluations(const tmdhip_ctx *ctx, int r);
 int64_t pme_bytes(const tmdhip_ctx *ctx);
 // md_loop.hip

@@ -619,6 +619,9 @@ class DomainSet:
         if engine_kwargs.get("metadynamics") is not None:
             raise ValueError("metadynamics cannot be domain-decomposed (a CV's atoms would straddle bricks, and atom indices change "
                              "at every migration)")
+        if engine_kwargs.get("implicit_solvent") is not None:
+            raise ValueError("implicit_solvent cannot be domain-decomposed (the generalized-Born sums run over all pairs of atoms, "
+                             "and a brick holds passive atoms)")
         self.dry = bool(dry)  # CPU tensors, no force engine (DryDomain): the plumbing of an N-rank run without a GPU
         self.grid = BrickGrid(box, world, grid)
         self.device, self.dtype = torch.device(device), dtype

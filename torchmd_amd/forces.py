@@ -226,6 +226,8 @@ class _Engine:
         self.rbuf = torch.zeros(nreplicas, 2, dtype=torch.float64, device=device)  # restraint energies (position, distance)
         self._restraint_version = None
         self.mbuf = torch.zeros(nreplicas, 3, dtype=torch.float64, device=device)  # metadynamics: (V, s_0, s_1) per replica
+        self.gbuf = torch.zeros(nreplicas, 2, dtype=torch.float64, device=device)  # implicit solvent: (GB, SA) per replica
+        self._gb_set = None
         _LIVE_ENGINES.add(self)
         del keep
 
@@ -255,6 +257,22 @@ class _Engine:
                                             C.c_void_p(forces.data_ptr()) if forces is not None else C.c_void_p(), C.c_void_p(),
                                             C.c_void_p(), 0.0, C.c_void_p(self.mbuf.data_ptr()) if want_energy else C.c_void_p(),
                                             C.c_void_p(torch.cuda.current_stream(pos.device).cuda_stream)), "tmdhip_metad_apply")
+
+    def sync_gb(self, gb):
+        """Hand a `implicit.GeneralizedBorn` to the context on first sight (tmdhip_set_gb)."""
+        if gb is None or self._gb_set is gb:
+            return
+        gb.upload(self.lib, self.ctx)
+        self._gb_set = gb
+
+    def apply_gb(self, gb, pos, boxes, forces, want_energy):
+        """forces += F_GB and / or (GB, SA) into `gbuf`, on the current stream (tmdhip_gb_apply)."""
+        if gb is None or (forces is None and not want_energy):
+            return
+        L.check(self.lib.tmdhip_gb_apply(self.ctx, C.c_void_p(pos.data_ptr()), boxes.ctypes.data_as(C.POINTER(C.c_double)),
+                                         C.c_void_p(forces.data_ptr()) if forces is not None else C.c_void_p(), C.c_void_p(),
+                                         C.c_void_p(), 0.0, C.c_void_p(self.gbuf.data_ptr()) if want_energy else C.c_void_p(),
+                                         C.c_void_p(torch.cuda.current_stream(pos.device).cuda_stream)), "tmdhip_gb_apply")
 
     def set_constraints(self, cs):
         """Hand a `constraints.ConstraintSet` to the context (tmdhip_set_constraints); None releases it."""
@@ -360,6 +378,13 @@ class Forces:
                           "metadynamics" entry and the total includes it, and `Integrator.step` integrates under the total
                           force and deposits a hill every `frequency` steps.  Not under `torch.vmap`, with `batch=`,
                           `barostat=`, `exchange=` or the domain decomposition.
+    implicit_solvent      a `implicit.GeneralizedBorn`: the OBC2 generalized-Born model with a surface-area term (DESIGN
+                          §21), for open boundaries (box [0, 0, 0]).  Its force is added behind the other two,
+                          `compute(returnDetails=True)` reports an "implicit_solvent" entry (GB + SA) and the total includes
+                          it, `minimize_fire` converges on the total and `Integrator.step` integrates under the total force.
+                          The GB sums run over every pair of atoms whether `cutoff` is None or not: the cutoff acts on the
+                          vacuum terms only.  Not under `torch.vmap`, with `batch=`, `virtual_sites=`, `pme=True`,
+                          `rfa=True`, a non-zero box, `barostat=`, `pressure()` / `virial()` or the domain decomposition.
     """
 
     bonded = ["bonds", "angles", "dihedrals", "impropers", "1-4"]
@@ -387,6 +412,7 @@ class Forces:
         pme_grid=None,
         virtual_sites=None,
         metadynamics=None,
+        implicit_solvent=None,
         restraints=None,
     ):
         self.par = parameters
@@ -482,9 +508,44 @@ class Forces:
                 raise ValueError("metadynamics must be a metadynamics.Metadynamics")
             metadynamics.check(self.natoms, torch.as_tensor(parameters.masses).detach().cpu().double().reshape(-1).numpy(), virtual_sites)
             metadynamics._forces = self
+        self.implicit_solvent = implicit_solvent
+        if implicit_solvent is not None:
+            from .implicit import GeneralizedBorn
+
+            if not isinstance(implicit_solvent, GeneralizedBorn):
+                raise ValueError("implicit_solvent must be an implicit.GeneralizedBorn")
+            implicit_solvent.check(self.natoms)
+            if virtual_sites is not None:
+                raise ValueError("implicit_solvent cannot be combined with virtual_sites=")
+            if self.pme:
+                raise ValueError("implicit_solvent cannot be combined with pme=True (a periodic method)")
+            if rfa:
+                raise ValueError("implicit_solvent cannot be combined with rfa=True: a reaction field already stands for the solvent")
         self._engines = {}
         self._box_cache = None
         self._ava_idx = None
+
+    def _gb_box(self, hbox):
+        """The generalized-Born model is for open boundaries: every box edge must be zero."""
+        if self.implicit_solvent is not None and np.any(np.asarray(hbox) != 0):
+            raise ValueError("implicit_solvent needs open boundaries: every box edge must be 0")
+
+    def born_radii(self, pos=None):
+        """The effective Born radii of the last evaluation with `implicit_solvent=`, [R, N] float64 (numpy); `pos` picks the
+        context (device, dtype, replicas) when there are several."""
+        if self.implicit_solvent is None:
+            raise ValueError("born_radii() needs implicit_solvent=")
+        if pos is not None:
+            eng = self._engine(pos.detach())
+        elif len(self._engines) == 1:
+            eng = next(iter(self._engines.values()))
+        else:
+            raise ValueError("born_radii(): no evaluation yet, or several contexts: pass the positions")
+        if eng._gb_set is None:
+            raise ValueError("born_radii(): no evaluation yet")
+        out = np.empty((eng.nreplicas, self.natoms), dtype=np.float64)
+        L.check(eng.lib.tmdhip_gb_born_radii(eng.ctx, out.ctypes.data_as(C.POINTER(C.c_double))), "tmdhip_gb_born_radii")
+        return out
 
     def _skin_weight_array(self):
         """Per-atom skin weights in (0, 1] as a numpy array, or None for the uniform skin."""
@@ -515,6 +576,8 @@ class Forces:
         neighbour list and zero force).  Used by the domain decomposition at every atom migration."""
         if self.virtual_sites is not None:
             raise ValueError("update_atoms is not available with virtual_sites")
+        if self.implicit_solvent is not None:
+            raise ValueError("update_atoms is not available with implicit_solvent")
         if any(t in self.energies for t in self.bonded) or len(self._excl_csr[1]):
             raise RuntimeError("update_atoms is only available for atomic systems")
         self.par = parameters
@@ -684,11 +747,13 @@ class Forces:
             if not forces.is_contiguous():
                 target, forces = forces, torch.empty_like(p)
         self._pme_box(self._host_box(box))
+        self._gb_box(self._host_box(box))
         eng = self._engine(p, exact)
         with torch.cuda.device(p.device):
             eng.sync_restraints(self.restraints)
             if self.metadynamics is not None:
                 self.metadynamics.sync(eng)
+            eng.sync_gb(self.implicit_solvent)
             eng.place_sites(p)  # first launch (no-op without virtual sites)
             for _ in range(4):
                 self._launch(eng, p, box, forces, want_energy, want_forces, count_pairs)
@@ -702,6 +767,8 @@ class Forces:
                 eng.apply_restraints(self.restraints, p, self._replica_boxes(box, p.shape[0]), forces if want_forces else None, want_energy)
             if self.metadynamics is not None and not count_pairs:
                 eng.apply_metad(self.metadynamics, p, self._replica_boxes(box, p.shape[0]), forces if want_forces else None, want_energy)
+            if self.implicit_solvent is not None and not count_pairs:
+                eng.apply_gb(self.implicit_solvent, p, self._replica_boxes(box, p.shape[0]), forces if want_forces else None, want_energy)
             if eng.vsites is not None and p.data_ptr() != pos.data_ptr():
                 pos.detach().copy_(p)  # (a non-contiguous `pos` was evaluated through a copy: the sites go back)
         if target is not None:
@@ -728,6 +795,7 @@ class Forces:
                 target, forces = forces, torch.empty_like(p)
         hbox = self._host_box(box)
         self._pme_box(hbox)
+        self._gb_box(hbox)
         eng = self._engine(p, exact)
         R = p.shape[0]
         boxes = hbox if len(hbox) == R else np.ascontiguousarray(np.stack([hbox[min(r, len(hbox) - 1)] for r in range(R)]))
@@ -737,6 +805,7 @@ class Forces:
             eng.sync_restraints(self.restraints)
             if self.metadynamics is not None:
                 self.metadynamics.sync(eng)
+            eng.sync_gb(self.implicit_solvent)
             eng.place_sites(p)  # first launch (no-op without virtual sites)
             for _ in range(4):
                 rc = L.check(
@@ -759,6 +828,9 @@ class Forces:
             if self.metadynamics is not None:
                 eng.apply_metad(self.metadynamics, p, np.ascontiguousarray(boxes, dtype=np.float64), forces, True)
                 self.metadynamics.report(eng.mbuf.cpu().numpy())
+            if self.implicit_solvent is not None:
+                eng.apply_gb(self.implicit_solvent, p, np.ascontiguousarray(boxes, dtype=np.float64), forces, True)
+                self.implicit_solvent.energy = eng.gbuf.cpu().numpy()
             if eng.vsites is not None and p.data_ptr() != pos.data_ptr():
                 pos.detach().copy_(p)  # (a non-contiguous `pos` was evaluated through a copy: the sites go back)
         if target is not None:
@@ -780,6 +852,8 @@ class Forces:
             raise ValueError("compute() with restraints cannot run under torch.vmap (their targets are per replica of the context)")
         if self.metadynamics is not None and _is_batched(pos):
             raise ValueError("compute() with metadynamics cannot run under torch.vmap (its grids are per replica of the context)")
+        if self.implicit_solvent is not None and _is_batched(pos):
+            raise ValueError("compute() with implicit_solvent cannot run under torch.vmap (its Born radii are per replica of the context)")
         if self.virtual_sites is not None:
             if _is_batched(pos):
                 raise ValueError("compute() with virtual_sites cannot run under torch.vmap (the sites are written into `pos` in place)")
@@ -835,6 +909,9 @@ class Forces:
         if self.metadynamics is not None:
             names.append("metadynamics")
             cols = np.concatenate([cols, self.metadynamics.energy.reshape(-1, 1)], axis=1)
+        if self.implicit_solvent is not None:
+            names.append("implicit_solvent")
+            cols = np.concatenate([cols, self.implicit_solvent.energy.sum(axis=1, keepdims=True)], axis=1)
 
         if not returnDetails:
             tot = cols.sum(axis=1)
@@ -885,6 +962,9 @@ class Forces:
         if want_energy and self.metadynamics is not None:
             vb = self._engine(pos.detach()).mbuf[:, 0]
             extra = vb if extra is None else extra + vb
+        if want_energy and self.implicit_solvent is not None:
+            gb = self._engine(pos.detach()).gbuf.sum(dim=1)
+            extra = gb if extra is None else extra + gb
         if self.external:
             ext_ene, ext_force = self.external.calculate(pos, box)
             forces += ext_force
@@ -903,12 +983,14 @@ class Forces:
             raise RuntimeError(f"systems.pos must have {self.natoms} atoms")
         hbox = self._host_box(system.box)
         self._pme_box(hbox)
+        self._gb_box(hbox)
         eng = self._engine(pos)
         if getattr(eng, "_constraints", None) is not constraints:
             eng.set_constraints(constraints)
         eng.sync_restraints(self.restraints)
         if self.metadynamics is not None:
             self.metadynamics.sync(eng)
+        eng.sync_gb(self.implicit_solvent)
         R = pos.shape[0]
         # the descriptor and the per-replica box array are kept between calls (a 20-step call is short enough for
         # the Python in front of its first launch to show)
@@ -975,6 +1057,8 @@ class Forces:
 
         if _is_batched(pos) or _is_batched(box):
             raise ValueError("the pressure cannot be evaluated under torch.vmap (its molecule table and lists are per replica of the context)")
+        if self.implicit_solvent is not None:
+            raise ValueError("the pressure and the virial are not available with implicit_solvent (open boundaries: there is no volume)")
         if getattr(self, "_nactive", None):
             raise ValueError("the pressure is not available for a brick of the domain decomposition (its context holds passive atoms)")
         L.require_device_tensor(pos, "pos")

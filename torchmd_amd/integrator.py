@@ -185,6 +185,17 @@ class Integrator:
         if exchange is not None:
             self._init_exchange(exchange)
         self._check_metadynamics()
+        self._check_implicit_solvent()
+
+    def _check_implicit_solvent(self):
+        """What is refused with a generalized-Born implicit solvent (ValueError): atom groups and any barostat (the model is
+        for open boundaries: there is no volume to change)."""
+        if getattr(self.forces, "implicit_solvent", None) is None:
+            return
+        if self.batch is not None:
+            raise ValueError("implicit_solvent does not support atom groups (batch=): its Born radii are per replica")
+        if self.barostat is not None:
+            raise ValueError("implicit_solvent cannot run under barostat=: open boundaries have no volume")
 
     def _check_metadynamics(self):
         """What is refused with a metadynamics bias (ValueError): atom groups, a barostat (the distance grid does not scale
@@ -508,6 +519,12 @@ class Integrator:
                 L.check(lib.tmdhip_metad_energy(eng.ctx, em.ctypes.data_as(C.POINTER(C.c_double)), _stream(dev)), "tmdhip_metad_energy")
                 self.forces.metadynamics.report(em)
                 tot = tot + em[:, 0]
+            gb = getattr(self.forces, "implicit_solvent", None)
+            if gb is not None:  # (GB, SA) of the finishing launch: one small copy
+                eg = np.empty((R, 2), dtype=np.float64)
+                L.check(lib.tmdhip_gb_energy(eng.ctx, eg.ctypes.data_as(C.POINTER(C.c_double)), _stream(dev)), "tmdhip_gb_energy")
+                gb.energy = eg
+                tot = tot + eg.sum(axis=1)
             pot = [float(v) for v in tot]
             Ekin = obs[:, L.NENERGY].copy()
             Ekin = Ekin.astype(np.dtype("float32") if s.pos.dtype == torch.float32 else np.float64)
@@ -552,6 +569,8 @@ class Integrator:
                 self.forces._restraint_energy = eng.rbuf.cpu().numpy()
             if ebuf is not None and getattr(self.forces, "metadynamics", None) is not None:
                 self.forces.metadynamics.report(eng.mbuf.cpu().numpy())
+            if ebuf is not None and getattr(self.forces, "implicit_solvent", None) is not None:
+                self.forces.implicit_solvent.energy = eng.gbuf.cpu().numpy()
         else:
             Ekin = ke.flatten().cpu().numpy()
         Ekin = Ekin.astype(np.dtype("float32") if s.pos.dtype == torch.float32 else np.float64)

@@ -20,6 +20,9 @@ restraint energy that `epot` contains.  With a `metadynamics:` mapping (the argu
 height, frequency, temperature, bias_factor, grid_min, grid_max, grid_bins, walkers) every monitor file gains a `bias`
 column (V(s(x)), inside `epot`) and one column per CV (`cv0`, `cv1`), and the hills log and the grid are written to
 `{output}_hills.npy` `[n,R,ncv+1]` and `{output}_bias_grid.npz` at the end.
+With `implicit_solvent: obc2` (the generalized-Born / surface-area model of DESIGN §21, open boundaries only; optional
+`gb_radii: file.npy` and `gb_scale: file.npy` replace the default tables, `solvent_dielectric` and `surface_tension` the default
+78.5 and 0.0054 kcal/mol/A^2) every monitor file gains an `implicit_solvent` column: the GB + SA energy that `epot` contains.
 With `pressure: true` every monitor file gains a `pressure` column (bar): the instantaneous pressure of the force field from the
 molecular virial, evaluated when a monitor row is written, with or without `barostat_pressure`.
 """
@@ -72,6 +75,11 @@ DEFAULTS = dict(
     restraints=None,  # None or an .npz file: harmonic position / distance restraints (pos_atom, pos_ref, pos_k, dist_pair, dist_r0, dist_k): DESIGN §17
     metadynamics=None,  # None or a mapping with the arguments of metadynamics.Metadynamics (cvs: [[kind, [atoms]], ...]): DESIGN §18
     pressure=False,  # True: every monitor file gains a `pressure` column (bar): the instantaneous pressure from the molecular virial: DESIGN §19
+    implicit_solvent=None,  # None or "obc2": generalized-Born / surface-area implicit solvent, open boundaries only: DESIGN §21
+    gb_radii=None,  # None (the defaults of GeneralizedBorn.from_parameters) or an .npy file with one intrinsic radius per atom (A)
+    gb_scale=None,  # None or an .npy file with one descreening scale per atom
+    solvent_dielectric=78.5,  # of implicit_solvent
+    surface_tension=0.0054,  # kcal/mol/A^2, of implicit_solvent; 0: no surface-area term
     virtual_sites=None,  # None or "tip4p": four-site waters O,H1,H2,M; geometry from the force field's `virtual_sites` section: DESIGN §12
 )
 
@@ -158,6 +166,15 @@ def get_args(arguments=None):
         args.metadynamics = None
     if args.metadynamics is not None and not isinstance(args.metadynamics, dict):
         raise ValueError("metadynamics must be a mapping with the arguments of Metadynamics (cvs, sigma, height, frequency, ...)")
+    for k in ("implicit_solvent", "gb_radii", "gb_scale"):
+        if isinstance(getattr(args, k), str) and getattr(args, k).lower() in ("none", "null", ""):
+            setattr(args, k, None)
+    if args.implicit_solvent is not None:
+        args.implicit_solvent = str(args.implicit_solvent).lower()
+        if args.implicit_solvent != "obc2":
+            raise ValueError(f"implicit_solvent must be None or 'obc2', got {args.implicit_solvent!r}")
+    args.solvent_dielectric = float(args.solvent_dielectric)
+    args.surface_tension = float(args.surface_tension)
     if isinstance(args.remove_com, str):
         args.remove_com = args.remove_com.lower() not in ("false", "0", "no", "off")
     args.remove_com = bool(args.remove_com)
@@ -276,6 +293,15 @@ def setup(args):
         from .metadynamics import Metadynamics
 
         extra["metadynamics"] = Metadynamics.from_config(args.metadynamics, args.replicas)
+    if args.implicit_solvent is not None:
+        from .implicit import GeneralizedBorn
+
+        kw = dict(solvent_dielectric=args.solvent_dielectric, surface_tension=args.surface_tension)
+        gb = GeneralizedBorn.from_parameters(parameters, **kw)
+        if args.gb_radii is not None or args.gb_scale is not None:
+            gb = GeneralizedBorn(np.load(args.gb_radii) if args.gb_radii is not None else gb.radii,
+                                 np.load(args.gb_scale) if args.gb_scale is not None else gb.scale, **kw)
+        extra["implicit_solvent"] = gb
     forces = Forces(parameters, terms=terms, external=external, cutoff=args.cutoff, rfa=args.rfa,
                     switch_dist=args.switch_dist, exclusions=tuple(args.exclusions), pme=args.pme,
                     ewald_tolerance=args.ewald_tolerance, pme_order=args.pme_order, pme_grid=args.pme_grid, **extra)
@@ -370,6 +396,8 @@ def dynamics(args, mol, system, forces):
     columns += ("rung",) if exchange is not None else ()
     restrained = getattr(forces, "restraints", None) is not None
     columns += ("restraints",) if restrained else ()
+    solvent = getattr(forces, "implicit_solvent", None)
+    columns += ("implicit_solvent",) if solvent is not None else ()
     metad = getattr(forces, "metadynamics", None)
     columns += ("bias",) + tuple(f"cv{c}" for c in range(metad.ncv)) if metad is not None else ()
     logs = [LogWriter(args.log_dir, columns, name=f"monitor_{k}.csv") for k in range(args.replicas)]
@@ -404,6 +432,8 @@ def dynamics(args, mol, system, forces):
                 row["rung"] = int(exchange.rungs[k]) if exchange.rungs is not None else k
             if restrained:  # the restraint energy inside `epot`, as of the last evaluation
                 row["restraints"] = float(forces._restraint_energy[k].sum())
+            if solvent is not None:  # the GB + SA energy inside `epot`, as of the last evaluation
+                row["implicit_solvent"] = float(solvent.energy[k].sum())
             if metad is not None:  # the bias energy inside `epot` and the CVs, as of the last evaluation
                 row["bias"] = float(metad.energy[k])
                 for c in range(metad.ncv):
