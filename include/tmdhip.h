@@ -518,6 +518,58 @@ int tmdhip_gb_apply(tmdhip_ctx *ctx, const void *pos_dev, const double *box_host
 int tmdhip_gb_energy(tmdhip_ctx *ctx, double *out_host, void *stream);
 /* The effective Born radii B_i of the last evaluation: out_host double [R][N] (zeros before the first one). */
 int tmdhip_gb_born_radii(tmdhip_ctx *ctx, double *out_host);
+/* Alchemical decoupling of a solute S from its environment E, one coupling (lambda_vdw, lambda_elec) per replica (added to
+ * ABI 11: new symbols only).  The context must have been created with charge 0 and an all-zero Lennard-Jones class for every
+ * atom of S, so that its own pair kernels return exactly 0 for the solute; what they leave out is computed here:
+ *   cross pairs (i in S, j in E) inside the engine's cutoff (the same minimum image and decision), A, B from the context's table
+ *   at the solute's true classes, sigma^6 = A / B:
+ *     s = r^6 + alpha sigma^6 (1 - lv);  U_lj = lv (A / s^2 - B / s) sw(r);  U_el = le qq g(r)   (g: plain or reaction field)
+ *     dU/dlv = (A / s^2 - B / s) sw - lv (-2 A / s^3 + B / s^2) alpha sigma^6 sw;  dU/dle = qq g(r)
+ *   intra: every S-S pair the context's exclusions do not name, at full strength with the context's pair formula, and the
+ *   charge part qq / (scee r) of the solute's 1-4 pairs (the bonded kernel reads the context's charges, which are 0).
+ * tmdhip_set_alchemical validates, uploads and synchronises; enable = 0 releases the state.  Calling it again moves the
+ * couplings.  Refused before any launch: a null argument or a wrong struct size, an index out of range or given twice, a lambda
+ * outside [0, 1], a replica with lambda_elec != 0 and lambda_vdw != 1 (the charges have no soft core), alpha < 0, a solute
+ * that is not closed under the topology (an exclusion of the context, or a listed bond, angle, torsion or 1-4 pair, that
+ * joins S to E), a solute the context counts itself, a cross pair with A > 0 >= B, the repulsion / repulsioncg terms, and a
+ * context with PME, the generalized-Born model, virtual sites or passive atoms.
+ * With the state in place tmdhip_md_run integrates under the total force as it does with restraints: the impulse
+ * dt a(x) / (1 - gamma dt) between launches and a finishing launch (dt/2 a to the velocities, F to forces_dev, the energies).
+ * Every force has one writer and every sum a fixed order: no floating-point atomics, two calls give the same bits. */
+typedef struct tmdhip_alchemical_desc {
+  int32_t struct_size; /* = sizeof(tmdhip_alchemical_desc) */
+  int32_t enable;
+  int32_t natoms;    /* atoms of the solute */
+  int32_t nreplicas; /* = the context's */
+  const int32_t *atoms_host;      /* [natoms] indices of the solute */
+  const double *charges_host;     /* [natoms] its true charges (e), rounded to the context's dtype */
+  const int32_t *classes_host;    /* [natoms] its true Lennard-Jones classes in the context's table */
+  const double *lambda_vdw_host;  /* [nreplicas] */
+  const double *lambda_elec_host; /* [nreplicas] */
+  double alpha;
+  int32_t n14;                 /* the solute's 1-4 pairs whose charge part is given back (0: none) */
+  int32_t nbonds;              /* topology for the closure check only (NULL: not checked) */
+  const int32_t *pair14_host;  /* [n14][2] */
+  const double *scee14_host;   /* [n14] */
+  const int32_t *bond_idx_host;    /* [nbonds][2] */
+  const int32_t *angle_idx_host;   /* [nangles][3] */
+  const int32_t *torsion_idx_host; /* [ntorsions][4]: proper and improper */
+  int32_t nangles, ntorsions;
+} tmdhip_alchemical_desc;
+int tmdhip_set_alchemical(tmdhip_ctx *ctx, const tmdhip_alchemical_desc *desc);
+/* One evaluation at pos_dev (real [R][N][3]) in the boxes box_host [R][3]: tmdhip_restraint_apply's contract.  Whatever is not
+ * NULL is served: forces_dev += F; vel_dev += kick F / m (needs mass_dev; rows with m <= 0 are left alone); energies_dev
+ * (double [R][5]) = (cross LJ, cross electrostatics, intra, dU/dlambda_vdw, dU/dlambda_elec), overwritten.  Rows of
+ * environment atoms with no solute atom inside the cutoff are not written.  A context without the state: nothing is launched,
+ * energies are zeroed. */
+int tmdhip_alchemical_apply(tmdhip_ctx *ctx, const void *pos_dev, const double *box_host, void *forces_dev, void *vel_dev,
+                            const void *mass_dev, double kick, double *energies_dev, void *stream);
+/* The five numbers of the last step of the last tmdhip_md_run: out_host double [R][5]; zeros without the state. */
+int tmdhip_alchemical_energy(tmdhip_ctx *ctx, double *out_host, void *stream);
+/* The cross energy of every replica's configuration at nstates (1 .. 32) other couplings states_host [nstates][2] =
+ * (lambda_vdw, lambda_elec), in one pass that shares the distance work: out_host double [R][nstates].  Synchronises the stream. */
+int tmdhip_alchemical_states(tmdhip_ctx *ctx, const void *pos_dev, const double *box_host, int32_t nstates, const double *states_host,
+                             double *out_host, void *stream);
 /* Well-tempered metadynamics on one or two collective variables (added to ABI 11: new symbols only).
  *   CVs       kind 0, distance: r = |minimum image of (x_i - x_j)| (atoms[c][0..1]), not periodic, grid [grid_min, grid_max];
  *             kind 1, dihedral: the torsion of atoms[c][0..3] in radians with the sign of the bonded term, from the

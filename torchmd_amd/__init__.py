@@ -9,7 +9,8 @@ rescaling, one target temperature per replica) and `torchmd_amd.ReplicaExchange`
 (temperature replica exchange on that thermostat's ladder) and `torchmd_amd.Restraints` (harmonic position and distance
 restraints with one target per replica) and `torchmd_amd.Metadynamics` (well-tempered metadynamics on distance and
 dihedral collective variables) and `torchmd_amd.GeneralizedBorn` (OBC2 generalized-Born / surface-area implicit solvent for
-systems with open boundaries); all imported on first use only,
+systems with open boundaries) and `torchmd_amd.Alchemical` (alchemical decoupling of a solute: soft-core pairs with one coupling
+per replica, dU/dlambda and foreign energies); all imported on first use only,
 backed by hand-written HIP kernels in `torchmd_amd/lib/libtmdhip.so` (C ABI: include/tmdhip.h).
 """
 
@@ -46,6 +47,10 @@ def __getattr__(name):
         from .metadynamics import Metadynamics
 
         return Metadynamics
+    if name == "Alchemical":
+        from .alchemy import Alchemical
+
+        return Alchemical
     if name == "GeneralizedBorn":
         from .implicit import GeneralizedBorn
 
@@ -54,6 +59,7 @@ def __getattr__(name):
 
 
 __all__ = [
+    "Alchemical",
     "CRescaleBarostat",
     "Forces",
     "GeneralizedBorn",

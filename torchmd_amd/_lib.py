@@ -277,6 +277,30 @@ class GbDesc(C.Structure):
     ]
 
 
+class AlchemicalDesc(C.Structure):
+    _fields_ = [
+        ("struct_size", C.c_int32),
+        ("enable", C.c_int32),
+        ("natoms", C.c_int32),
+        ("nreplicas", C.c_int32),
+        ("atoms_host", C.c_void_p),
+        ("charges_host", C.c_void_p),
+        ("classes_host", C.c_void_p),
+        ("lambda_vdw_host", C.c_void_p),
+        ("lambda_elec_host", C.c_void_p),
+        ("alpha", C.c_double),
+        ("n14", C.c_int32),
+        ("nbonds", C.c_int32),
+        ("pair14_host", C.c_void_p),
+        ("scee14_host", C.c_void_p),
+        ("bond_idx_host", C.c_void_p),
+        ("angle_idx_host", C.c_void_p),
+        ("torsion_idx_host", C.c_void_p),
+        ("nangles", C.c_int32),
+        ("ntorsions", C.c_int32),
+    ]
+
+
 class MetadDesc(C.Structure):
     _fields_ = [
         ("struct_size", C.c_int32),
@@ -434,6 +458,16 @@ SIGNATURES = {
     ),
     "tmdhip_gb_energy": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.c_void_p]),
     "tmdhip_gb_born_radii": (C.c_int, [C.c_void_p, C.POINTER(C.c_double)]),
+    "tmdhip_set_alchemical": (C.c_int, [C.c_void_p, C.POINTER(AlchemicalDesc)]),
+    "tmdhip_alchemical_apply": (
+        C.c_int,
+        [C.c_void_p, C.c_void_p, C.POINTER(C.c_double), C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p],
+    ),
+    "tmdhip_alchemical_energy": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.c_void_p]),
+    "tmdhip_alchemical_states": (
+        C.c_int,
+        [C.c_void_p, C.c_void_p, C.POINTER(C.c_double), C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_void_p],
+    ),
     "tmdhip_set_metadynamics": (C.c_int, [C.c_void_p, C.POINTER(MetadDesc)]),
     "tmdhip_metad_apply": (
         C.c_int,

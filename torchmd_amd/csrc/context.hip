@@ -554,6 +554,7 @@ void tmdhip_destroy(tmdhip_ctx *ctx) {
   tmd::restraint_release(ctx);
   tmd::metad_release(ctx);
   tmd::gb_release(ctx);
+  tmd::alchemy_release(ctx);
   tmd::virial_release(ctx);
   delete ctx;
 }

@@ -655,6 +655,8 @@ struct tmdhip_ctx {
   void *metad = nullptr;
   // the generalized-Born implicit solvent (tmdhip_set_gb), gb.hip; null: off (no launch, nothing allocated)
   void *gb = nullptr;
+  // alchemical decoupling of a solute (tmdhip_set_alchemical), alchemy.hip; null: off (no launch, nothing allocated)
+  void *alchemy = nullptr;
   // the molecule table and scratch of the pressure observable (tmdhip_set_molecules), virial.hip; null: not set
   void *virial = nullptr;
   // timing of the dominant kernel
@@ -893,6 +895,15 @@ int gb_impulse_each(tmdhip_ctx *ctx, const void *const *pos_each, const double *
                     hipStream_t st);
 int gb_finish(tmdhip_ctx *ctx, const void *pos, const double *box_host, void *vel, void *forces, const void *mass, double kick,
               hipStream_t st);
+// alchemy.hip (only called with ctx->alchemy set, except the release): the same four places, for the alchemical solute
+void alchemy_release(tmdhip_ctx *ctx);
+int alchemy_run_check(tmdhip_ctx *ctx, const tmdhip_md_desc *d, double *impulse_kick, hipStream_t st);
+int alchemy_impulse(tmdhip_ctx *ctx, int rep0, int nrep, const void *pos, const double *box_host, void *vel, const void *mass, double kick,
+                    hipStream_t st);
+int alchemy_impulse_each(tmdhip_ctx *ctx, const void *const *pos_each, const double *box_host, void *vel, const void *mass, double kick,
+                         hipStream_t st);
+int alchemy_finish(tmdhip_ctx *ctx, const void *pos, const double *box_host, void *vel, void *forces, const void *mass, double kick,
+                   hipStream_t st);
 int64_t pme_evaluations(const tmdhip_ctx *ctx, int r);
 int64_t pme_bytes(const tmdhip_ctx *ctx);
 // md_loop.hip

@@ -438,6 +438,7 @@ struct MdRun {
   const bool restrained;
   const bool biased;  // the metadynamics bias (metad.hip): the same impulse, a launch of its own
   const bool solvated;  // the generalized-Born implicit solvent (gb.hip): the same impulse, behind the other two
+  const bool alchemical;  // the alchemical solute (alchemy.hip): the same impulse, last
   double impulse_kick = 0;
   std::vector<const void *> impulse_pos;  // a batched iteration: where each replica's positions live, for ONE impulse launch
 
@@ -445,7 +446,7 @@ struct MdRun {
       : ctx(ctx_), d(d_), st(st_), n(ctx_->d.natoms), nrep((int)ctx_->rep.size()), stride((size_t)ctx_->d.natoms * 3),
         langevin(d_->vcoeff_dev != nullptr), cur(nrep), owed(nrep, 0), stepped(nrep, 0), finalized(nrep, 0),
         home_all((R *)d_->pos_dev), bcur((R *)d_->pos_dev), restrained(ctx_->restraints != nullptr), biased(ctx_->metad != nullptr),
-        solvated(ctx_->gb != nullptr) {
+        solvated(ctx_->gb != nullptr), alchemical(ctx_->alchemy != nullptr) {
     const char *e_min = std::getenv("TMDHIP_DEBUG_CHAIN_MIN_ENTRIES"), *e_near = std::getenv("TMDHIP_DEBUG_CHAIN_NEAR"),
                *e_batch = std::getenv("TMDHIP_BATCH_REPLICAS");
     chain_skip_on = !env_is_zero("TMDHIP_CHAIN_SKIP") && !ctx->no_chain_skip_once;
@@ -493,6 +494,7 @@ struct MdRun {
     if (restrained) TMD_TRY(restraint_run_check(ctx, d, &impulse_kick, st));
     if (biased) TMD_TRY(metad_run_check(ctx, d, &impulse_kick, st));
     if (solvated) TMD_TRY(gb_run_check(ctx, d, &impulse_kick, st));
+    if (alchemical) TMD_TRY(alchemy_run_check(ctx, d, &impulse_kick, st));
     TMD_TRY(snapshot_unless_first_kernel_takes_it());
     for (it = 0; it <= d->niter; ++it) {
       first = it < d->niter;
@@ -516,7 +518,8 @@ struct MdRun {
     TMD_TRY(copy_home());
     if (restrained) TMD_TRY(finish_restraints());
     if (biased) TMD_TRY(finish_metad());
-    return solvated ? finish_gb() : 0;
+    if (solvated) TMD_TRY(finish_gb());
+    return alchemical ? finish_alchemy() : 0;
   }
 
   // Restraints, the last step of the call: dt/2 a_r for the velocities, F_r for the caller's forces (total on return, and the
@@ -539,6 +542,14 @@ struct MdRun {
   // The generalized-Born model, the last step of the call: the same three things (gb.hip)
   int finish_gb() {
     TMD_TRY(gb_finish(ctx, d->pos_dev, d->box_host, d->vel_dev, d->forces_dev, d->mass_dev, 0.5 * d->dt, st));
+    ctx->ke_from_run = nullptr;
+    ctx->run_published_seq = 0;
+    return 0;
+  }
+
+  // The alchemical solute, the last step of the call: the same three things (alchemy.hip)
+  int finish_alchemy() {
+    TMD_TRY(alchemy_finish(ctx, d->pos_dev, d->box_host, d->vel_dev, d->forces_dev, d->mass_dev, 0.5 * d->dt, st));
     ctx->ke_from_run = nullptr;
     ctx->run_published_seq = 0;
     return 0;
@@ -601,6 +612,8 @@ struct MdRun {
       TMD_TRY(restraint_impulse(ctx, 0, nrep, pos, d->box_host, d->vel_dev, d->mass_dev, impulse_kick, st));
     if (biased && it + 1 < d->niter) TMD_TRY(metad_impulse(ctx, 0, nrep, pos, d->box_host, d->vel_dev, d->mass_dev, impulse_kick, st));
     if (solvated && it + 1 < d->niter) TMD_TRY(gb_impulse(ctx, 0, nrep, pos, d->box_host, d->vel_dev, d->mass_dev, impulse_kick, st));
+    if (alchemical && it + 1 < d->niter)
+      TMD_TRY(alchemy_impulse(ctx, 0, nrep, pos, d->box_host, d->vel_dev, d->mass_dev, impulse_kick, st));
     int flags_c = TMDHIP_WANT_FORCES;
     double *en = nullptr;
     if (wants_energy()) {
@@ -787,7 +800,7 @@ struct MdRun {
     const int r = s.r;
     R *pos = cur[r];
     // (positions x_{it+1}, velocities v_{it+1/2} on every path: the step behind this launch turns the impulse into a_r's kicks)
-    if ((restrained || biased || solvated) && it + 1 < d->niter) {
+    if ((restrained || biased || solvated || alchemical) && it + 1 < d->niter) {
       if (batching) {  // (one launch for all replicas in front of finish_batch's)
         impulse_pos.resize(nrep);
         impulse_pos[r] = pos;
@@ -795,6 +808,7 @@ struct MdRun {
         if (restrained) TMD_TRY(restraint_impulse(ctx, r, 1, pos, s.box, (R *)d->vel_dev + r * stride, d->mass_dev, impulse_kick, st));
         if (biased) TMD_TRY(metad_impulse(ctx, r, 1, pos, s.box, (R *)d->vel_dev + r * stride, d->mass_dev, impulse_kick, st));
         if (solvated) TMD_TRY(gb_impulse(ctx, r, 1, pos, s.box, (R *)d->vel_dev + r * stride, d->mass_dev, impulse_kick, st));
+        if (alchemical) TMD_TRY(alchemy_impulse(ctx, r, 1, pos, s.box, (R *)d->vel_dev + r * stride, d->mass_dev, impulse_kick, st));
       }
     }
     int flags_c = TMDHIP_WANT_FORCES;
@@ -915,6 +929,8 @@ struct MdRun {
       TMD_TRY(metad_impulse_each(ctx, impulse_pos.data(), d->box_host, d->vel_dev, d->mass_dev, impulse_kick, st));
     if (solvated && it + 1 < d->niter)
       TMD_TRY(gb_impulse_each(ctx, impulse_pos.data(), d->box_host, d->vel_dev, d->mass_dev, impulse_kick, st));
+    if (alchemical && it + 1 < d->niter)
+      TMD_TRY(alchemy_impulse_each(ctx, impulse_pos.data(), d->box_host, d->vel_dev, d->mass_dev, impulse_kick, st));
     {  // the rebuild chains the host has not left out: one launch per kernel for all of them
       std::vector<int> reps, par;
       std::vector<const float *> ps;

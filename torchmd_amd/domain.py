@@ -622,6 +622,9 @@ class DomainSet:
         if engine_kwargs.get("implicit_solvent") is not None:
             raise ValueError("implicit_solvent cannot be domain-decomposed (the generalized-Born sums run over all pairs of atoms, "
                              "and a brick holds passive atoms)")
+        if engine_kwargs.get("alchemical") is not None:
+            raise ValueError("alchemical= cannot be domain-decomposed (the solute's atoms would straddle bricks, and atom indices "
+                             "change at every migration)")
         self.dry = bool(dry)  # CPU tensors, no force engine (DryDomain): the plumbing of an N-rank run without a GPU
         self.grid = BrickGrid(box, world, grid)
         self.device, self.dtype = torch.device(device), dtype

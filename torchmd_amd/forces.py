@@ -107,6 +107,11 @@ class _Engine:
             A_np, B_np = _np_real(A, dtype), _np_real(B, dtype)
             types = par.mapped_atom_types.detach().cpu().numpy().astype(np.int64)
             A_np, B_np, types, self.type_map = merge_lj_types(A_np, B_np, types)
+            if owner.alchemical is not None:
+                # the solute moves into an all-zero class of its own, appended behind the merged ones (alchemy.py)
+                from .alchemy import append_null_class
+
+                A_np, B_np, types, self.alch_classes = append_null_class(A_np, B_np, types, owner.alchemical.atoms)
             self.ntypes = int(A_np.shape[0])
             d.ntypes = self.ntypes
             d.types_host = ptr(np.ascontiguousarray(types.astype(np.int32)))
@@ -116,7 +121,14 @@ class _Engine:
             self.ntypes = 1
             d.ntypes = 1
             d.types_host = ptr(np.zeros(n, dtype=np.int32))
-        d.charges_host = ptr(_np_real(par.charges, dtype))
+            if owner.alchemical is not None:
+                self.alch_classes = np.zeros(len(owner.alchemical.atoms), dtype=np.int32)
+        q_np = _np_real(par.charges, dtype)
+        if owner.alchemical is not None:  # the context holds the solute with charge 0: its pair kernels return exactly 0 for it
+            self.alch_charges = q_np.reshape(-1)[owner.alchemical.atoms].astype(np.float64)
+            q_np = q_np.copy()
+            q_np.reshape(-1)[owner.alchemical.atoms] = 0
+        d.charges_host = ptr(q_np)
         off, idx = owner._excl_csr
         d.excl_offsets_host = ptr(off)
         d.excl_index_host = ptr(idx if len(idx) else np.zeros(1, dtype=np.int32))
@@ -228,6 +240,8 @@ class _Engine:
         self.mbuf = torch.zeros(nreplicas, 3, dtype=torch.float64, device=device)  # metadynamics: (V, s_0, s_1) per replica
         self.gbuf = torch.zeros(nreplicas, 2, dtype=torch.float64, device=device)  # implicit solvent: (GB, SA) per replica
         self._gb_set = None
+        self.abuf = torch.zeros(nreplicas, 5, dtype=torch.float64, device=device)  # alchemical: (cross LJ, cross el, intra, dU/dlv, dU/dle)
+        self._alch_version = None
         _LIVE_ENGINES.add(self)
         del keep
 
@@ -273,6 +287,26 @@ class _Engine:
                                          C.c_void_p(forces.data_ptr()) if forces is not None else C.c_void_p(), C.c_void_p(),
                                          C.c_void_p(), 0.0, C.c_void_p(self.gbuf.data_ptr()) if want_energy else C.c_void_p(),
                                          C.c_void_p(torch.cuda.current_stream(pos.device).cuda_stream)), "tmdhip_gb_apply")
+
+    def sync_alchemical(self, owner):
+        """Hand the owner's `alchemy.Alchemical` to the context when this context's copy is older (tmdhip_set_alchemical)."""
+        al = owner.alchemical
+        if al is None or self._alch_version == (id(al), al.version):
+            return
+        np_dtype = np.float32 if self.dtype == torch.float32 else np.float64
+        pair14, scee14 = al.solute_14(owner.par, owner.energies, np_dtype)
+        al.upload(self.lib, self.ctx, self.nreplicas, self.alch_charges, self.alch_classes, pair14, scee14,
+                  al.topology(owner.par, owner.energies))
+        self._alch_version = (id(al), al.version)
+
+    def apply_alchemical(self, al, pos, boxes, forces, want_energy):
+        """forces += F and / or the five numbers into `abuf`, on the current stream (tmdhip_alchemical_apply)."""
+        if al is None or (forces is None and not want_energy):
+            return
+        L.check(self.lib.tmdhip_alchemical_apply(self.ctx, C.c_void_p(pos.data_ptr()), boxes.ctypes.data_as(C.POINTER(C.c_double)),
+                                                 C.c_void_p(forces.data_ptr()) if forces is not None else C.c_void_p(), C.c_void_p(),
+                                                 C.c_void_p(), 0.0, C.c_void_p(self.abuf.data_ptr()) if want_energy else C.c_void_p(),
+                                                 C.c_void_p(torch.cuda.current_stream(pos.device).cuda_stream)), "tmdhip_alchemical_apply")
 
     def set_constraints(self, cs):
         """Hand a `constraints.ConstraintSet` to the context (tmdhip_set_constraints); None releases it."""
@@ -385,6 +419,13 @@ class Forces:
                           The GB sums run over every pair of atoms whether `cutoff` is None or not: the cutoff acts on the
                           vacuum terms only.  Not under `torch.vmap`, with `batch=`, `virtual_sites=`, `pme=True`,
                           `rfa=True`, a non-zero box, `barostat=`, `pressure()` / `virial()` or the domain decomposition.
+    alchemical            an `alchemy.Alchemical`: a solute whose pairs with every other atom are scaled by one coupling
+                          (lambda_vdw, lambda_elec) per replica, with soft-core Lennard-Jones.  The pairs inside
+                          the solute and its bonded terms stay at full strength.  `compute(returnDetails=True)` reports an
+                          "alchemical" entry (cross + intra) and the total includes it; `alchemical_terms()` returns the parts
+                          and dU/dlambda, `alchemical_energies()` the cross energy at other couplings.  Not under
+                          `torch.vmap`, with `batch=`, `virtual_sites=`, `pme=True`, `implicit_solvent=`, `barostat=`,
+                          `pressure()` / `virial()`, the repulsion terms or the domain decomposition.
     """
 
     bonded = ["bonds", "angles", "dihedrals", "impropers", "1-4"]
@@ -413,6 +454,7 @@ class Forces:
         virtual_sites=None,
         metadynamics=None,
         implicit_solvent=None,
+        alchemical=None,
         restraints=None,
     ):
         self.par = parameters
@@ -521,9 +563,81 @@ class Forces:
                 raise ValueError("implicit_solvent cannot be combined with pme=True (a periodic method)")
             if rfa:
                 raise ValueError("implicit_solvent cannot be combined with rfa=True: a reaction field already stands for the solvent")
+        self.alchemical = alchemical
+        if alchemical is not None:
+            from .alchemy import Alchemical
+
+            if not isinstance(alchemical, Alchemical):
+                raise ValueError("alchemical must be an alchemy.Alchemical")
+            if virtual_sites is not None:
+                raise ValueError("alchemical= cannot be combined with virtual_sites=")
+            if self.pme:
+                raise ValueError("alchemical= cannot be combined with pme=True (the reciprocal sum has no coupling parameter)")
+            if implicit_solvent is not None:
+                raise ValueError("alchemical= cannot be combined with implicit_solvent=")
+            tables = None
+            if "lj" in self.energies:
+                A, B = self._lj_tables()
+                tables = (torch.as_tensor(A).detach().cpu().double().numpy(), torch.as_tensor(B).detach().cpu().double().numpy(),
+                          parameters.mapped_atom_types.detach().cpu().numpy())
+            alchemical.check(self.natoms, parameters, self.energies, self._excl_csr, tables)
         self._engines = {}
         self._box_cache = None
         self._ava_idx = None
+
+    def _alch_engine(self, pos):
+        if self.alchemical is None:
+            raise ValueError("this needs alchemical=")
+        if pos is not None:
+            return self._engine(pos.detach())
+        if len(self._engines) == 1:
+            return next(iter(self._engines.values()))
+        raise ValueError("no evaluation yet, or several contexts: pass the positions")
+
+    def alchemical_terms(self, pos=None):
+        """(cross LJ, cross electrostatics, intra, dU/dlambda_vdw, dU/dlambda_elec) per replica of the last evaluation (a
+        `compute()` or the last step of `Integrator.step`), [R, 5] float64 (numpy); `pos` picks the context when there are
+        several."""
+        self._alch_engine(pos)
+        if self.alchemical.energy is None:
+            raise ValueError("alchemical_terms(): no evaluation yet")
+        return self.alchemical.energy.copy()
+
+    def alchemical_energies(self, pos, box, states):
+        """The cross (solute-environment) energy of every replica's configuration at other couplings: `states` [K, 2] =
+        (lambda_vdw, lambda_elec) -> [R, K] float64 (numpy), in one pass per 32 states that shares the distance work.  The
+        energy of a frame at state k is the frame's total minus its own cross energy plus column k."""
+        from .alchemy import MAX_STATES, check_lambdas
+
+        if self.alchemical is None:
+            raise ValueError("alchemical_energies() needs alchemical=")
+        if _is_batched(pos):
+            raise ValueError("alchemical_energies() cannot run under torch.vmap")
+        st = np.ascontiguousarray(np.asarray(states, dtype=np.float64))
+        if st.ndim != 2 or st.shape[1] != 2 or len(st) == 0:
+            raise ValueError("alchemical_energies(): states must be [K, 2] = (lambda_vdw, lambda_elec)")
+        check_lambdas(st[:, 0], st[:, 1], "alchemical_energies()")
+        L.require_device_tensor(pos, "pos")
+        p = pos.detach()
+        if not p.is_contiguous():
+            p = p.contiguous()
+        if p.dim() != 3 or p.shape[1] != self.natoms:
+            raise RuntimeError(f"pos must have shape (nreplicas, {self.natoms}, 3), got {tuple(p.shape)}")
+        eng = self._engine(p)
+        R = p.shape[0]
+        boxes = self._replica_boxes(box, R)
+        out = np.empty((R, len(st)), dtype=np.float64)
+        with torch.cuda.device(p.device):
+            eng.sync_alchemical(self)
+            stream = C.c_void_p(torch.cuda.current_stream(p.device).cuda_stream)
+            for k0 in range(0, len(st), MAX_STATES):
+                part = np.ascontiguousarray(st[k0 : k0 + MAX_STATES])
+                got = np.empty((R, len(part)), dtype=np.float64)
+                L.check(eng.lib.tmdhip_alchemical_states(eng.ctx, C.c_void_p(p.data_ptr()), boxes.ctypes.data_as(C.POINTER(C.c_double)),
+                                                         len(part), part.ctypes.data_as(C.POINTER(C.c_double)),
+                                                         got.ctypes.data_as(C.POINTER(C.c_double)), stream), "tmdhip_alchemical_states")
+                out[:, k0 : k0 + len(part)] = got
+        return out
 
     def _gb_box(self, hbox):
         """The generalized-Born model is for open boundaries: every box edge must be zero."""
@@ -578,6 +692,8 @@ class Forces:
             raise ValueError("update_atoms is not available with virtual_sites")
         if self.implicit_solvent is not None:
             raise ValueError("update_atoms is not available with implicit_solvent")
+        if self.alchemical is not None:
+            raise ValueError("update_atoms is not available with alchemical=")
         if any(t in self.energies for t in self.bonded) or len(self._excl_csr[1]):
             raise RuntimeError("update_atoms is only available for atomic systems")
         self.par = parameters
@@ -754,6 +870,7 @@ class Forces:
             if self.metadynamics is not None:
                 self.metadynamics.sync(eng)
             eng.sync_gb(self.implicit_solvent)
+            eng.sync_alchemical(self)
             eng.place_sites(p)  # first launch (no-op without virtual sites)
             for _ in range(4):
                 self._launch(eng, p, box, forces, want_energy, want_forces, count_pairs)
@@ -769,6 +886,8 @@ class Forces:
                 eng.apply_metad(self.metadynamics, p, self._replica_boxes(box, p.shape[0]), forces if want_forces else None, want_energy)
             if self.implicit_solvent is not None and not count_pairs:
                 eng.apply_gb(self.implicit_solvent, p, self._replica_boxes(box, p.shape[0]), forces if want_forces else None, want_energy)
+            if self.alchemical is not None and not count_pairs:
+                eng.apply_alchemical(self.alchemical, p, self._replica_boxes(box, p.shape[0]), forces if want_forces else None, want_energy)
             if eng.vsites is not None and p.data_ptr() != pos.data_ptr():
                 pos.detach().copy_(p)  # (a non-contiguous `pos` was evaluated through a copy: the sites go back)
         if target is not None:
@@ -806,6 +925,7 @@ class Forces:
             if self.metadynamics is not None:
                 self.metadynamics.sync(eng)
             eng.sync_gb(self.implicit_solvent)
+            eng.sync_alchemical(self)
             eng.place_sites(p)  # first launch (no-op without virtual sites)
             for _ in range(4):
                 rc = L.check(
@@ -831,6 +951,9 @@ class Forces:
             if self.implicit_solvent is not None:
                 eng.apply_gb(self.implicit_solvent, p, np.ascontiguousarray(boxes, dtype=np.float64), forces, True)
                 self.implicit_solvent.energy = eng.gbuf.cpu().numpy()
+            if self.alchemical is not None:
+                eng.apply_alchemical(self.alchemical, p, np.ascontiguousarray(boxes, dtype=np.float64), forces, True)
+                self.alchemical.energy = eng.abuf.cpu().numpy()
             if eng.vsites is not None and p.data_ptr() != pos.data_ptr():
                 pos.detach().copy_(p)  # (a non-contiguous `pos` was evaluated through a copy: the sites go back)
         if target is not None:
@@ -854,6 +977,8 @@ class Forces:
             raise ValueError("compute() with metadynamics cannot run under torch.vmap (its grids are per replica of the context)")
         if self.implicit_solvent is not None and _is_batched(pos):
             raise ValueError("compute() with implicit_solvent cannot run under torch.vmap (its Born radii are per replica of the context)")
+        if self.alchemical is not None and _is_batched(pos):
+            raise ValueError("compute() with alchemical= cannot run under torch.vmap (its couplings are per replica of the context)")
         if self.virtual_sites is not None:
             if _is_batched(pos):
                 raise ValueError("compute() with virtual_sites cannot run under torch.vmap (the sites are written into `pos` in place)")
@@ -912,6 +1037,9 @@ class Forces:
         if self.implicit_solvent is not None:
             names.append("implicit_solvent")
             cols = np.concatenate([cols, self.implicit_solvent.energy.sum(axis=1, keepdims=True)], axis=1)
+        if self.alchemical is not None:  # cross + intra
+            names.append("alchemical")
+            cols = np.concatenate([cols, self.alchemical.energy[:, :3].sum(axis=1, keepdims=True)], axis=1)
 
         if not returnDetails:
             tot = cols.sum(axis=1)
@@ -965,6 +1093,9 @@ class Forces:
         if want_energy and self.implicit_solvent is not None:
             gb = self._engine(pos.detach()).gbuf.sum(dim=1)
             extra = gb if extra is None else extra + gb
+        if want_energy and self.alchemical is not None:
+            ab = self._engine(pos.detach()).abuf[:, :3].sum(dim=1)
+            extra = ab if extra is None else extra + ab
         if self.external:
             ext_ene, ext_force = self.external.calculate(pos, box)
             forces += ext_force
@@ -991,6 +1122,7 @@ class Forces:
         if self.metadynamics is not None:
             self.metadynamics.sync(eng)
         eng.sync_gb(self.implicit_solvent)
+        eng.sync_alchemical(self)
         R = pos.shape[0]
         # the descriptor and the per-replica box array are kept between calls (a 20-step call is short enough for
         # the Python in front of its first launch to show)
@@ -1059,6 +1191,8 @@ class Forces:
             raise ValueError("the pressure cannot be evaluated under torch.vmap (its molecule table and lists are per replica of the context)")
         if self.implicit_solvent is not None:
             raise ValueError("the pressure and the virial are not available with implicit_solvent (open boundaries: there is no volume)")
+        if self.alchemical is not None:
+            raise ValueError("the pressure and the virial are not available with alchemical= (the virial lacks the solute's term)")
         if getattr(self, "_nactive", None):
             raise ValueError("the pressure is not available for a brick of the domain decomposition (its context holds passive atoms)")
         L.require_device_tensor(pos, "pos")

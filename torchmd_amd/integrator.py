@@ -186,6 +186,17 @@ class Integrator:
             self._init_exchange(exchange)
         self._check_metadynamics()
         self._check_implicit_solvent()
+        self._check_alchemical()
+
+    def _check_alchemical(self):
+        """What is refused with an alchemical solute (ValueError): atom groups and any barostat (the virial lacks the solute's
+        term; NPT is a follow-up)."""
+        if getattr(self.forces, "alchemical", None) is None:
+            return
+        if self.batch is not None:
+            raise ValueError("alchemical= does not support atom groups (batch=): its couplings are per replica")
+        if self.barostat is not None:
+            raise ValueError("alchemical= cannot run under barostat=: the virial lacks the solute's term")
 
     def _check_implicit_solvent(self):
         """What is refused with a generalized-Born implicit solvent (ValueError): atom groups and any barostat (the model is
@@ -525,6 +536,12 @@ class Integrator:
                 L.check(lib.tmdhip_gb_energy(eng.ctx, eg.ctypes.data_as(C.POINTER(C.c_double)), _stream(dev)), "tmdhip_gb_energy")
                 gb.energy = eg
                 tot = tot + eg.sum(axis=1)
+            al = getattr(self.forces, "alchemical", None)
+            if al is not None:  # the five numbers of the finishing launch: one small copy
+                ea = np.empty((R, 5), dtype=np.float64)
+                L.check(lib.tmdhip_alchemical_energy(eng.ctx, ea.ctypes.data_as(C.POINTER(C.c_double)), _stream(dev)), "tmdhip_alchemical_energy")
+                al.energy = ea
+                tot = tot + ea[:, :3].sum(axis=1)
             pot = [float(v) for v in tot]
             Ekin = obs[:, L.NENERGY].copy()
             Ekin = Ekin.astype(np.dtype("float32") if s.pos.dtype == torch.float32 else np.float64)
@@ -571,6 +588,8 @@ class Integrator:
                 self.forces.metadynamics.report(eng.mbuf.cpu().numpy())
             if ebuf is not None and getattr(self.forces, "implicit_solvent", None) is not None:
                 self.forces.implicit_solvent.energy = eng.gbuf.cpu().numpy()
+            if ebuf is not None and getattr(self.forces, "alchemical", None) is not None:
+                self.forces.alchemical.energy = eng.abuf.cpu().numpy()
         else:
             Ekin = ke.flatten().cpu().numpy()
         Ekin = Ekin.astype(np.dtype("float32") if s.pos.dtype == torch.float32 else np.float64)

@@ -23,6 +23,9 @@ column (V(s(x)), inside `epot`) and one column per CV (`cv0`, `cv1`), and the hi
 With `implicit_solvent: obc2` (the generalized-Born / surface-area model of DESIGN §21, open boundaries only; optional
 `gb_radii: file.npy` and `gb_scale: file.npy` replace the default tables, `solvent_dielectric` and `surface_tension` the default
 78.5 and 0.0054 kcal/mol/A^2) every monitor file gains an `implicit_solvent` column: the GB + SA energy that `epot` contains.
+With an `alchemical:` mapping (atoms, lambda_vdw, lambda_elec, alpha, and optionally states: [[lambda_vdw, lambda_elec], ...];
+DESIGN §22) every monitor file gains the columns `alchemical` (the cross + intra energy inside `epot`), `dudl_vdw` and `dudl_elec`, and
+with `states` the cross energy of every saved frame at those couplings is written to `{output}_states_{k}.npy` `[frames, K]`.
 With `pressure: true` every monitor file gains a `pressure` column (bar): the instantaneous pressure of the force field from the
 molecular virial, evaluated when a monitor row is written, with or without `barostat_pressure`.
 """
@@ -75,6 +78,7 @@ DEFAULTS = dict(
     restraints=None,  # None or an .npz file: harmonic position / distance restraints (pos_atom, pos_ref, pos_k, dist_pair, dist_r0, dist_k): DESIGN §17
     metadynamics=None,  # None or a mapping with the arguments of metadynamics.Metadynamics (cvs: [[kind, [atoms]], ...]): DESIGN §18
     pressure=False,  # True: every monitor file gains a `pressure` column (bar): the instantaneous pressure from the molecular virial: DESIGN §19
+    alchemical=None,  # None or a mapping with the arguments of alchemy.Alchemical (atoms, lambda_vdw, lambda_elec, alpha) and `states`: DESIGN §22
     implicit_solvent=None,  # None or "obc2": generalized-Born / surface-area implicit solvent, open boundaries only: DESIGN §21
     gb_radii=None,  # None (the defaults of GeneralizedBorn.from_parameters) or an .npy file with one intrinsic radius per atom (A)
     gb_scale=None,  # None or an .npy file with one descreening scale per atom
@@ -166,6 +170,10 @@ def get_args(arguments=None):
         args.metadynamics = None
     if args.metadynamics is not None and not isinstance(args.metadynamics, dict):
         raise ValueError("metadynamics must be a mapping with the arguments of Metadynamics (cvs, sigma, height, frequency, ...)")
+    if isinstance(args.alchemical, str):
+        args.alchemical = None if args.alchemical.lower() in ("none", "null", "") else yaml.safe_load(args.alchemical)
+    if args.alchemical is not None and not isinstance(args.alchemical, dict):
+        raise ValueError("alchemical must be a mapping with the arguments of Alchemical (atoms, lambda_vdw, lambda_elec, alpha, states)")
     for k in ("implicit_solvent", "gb_radii", "gb_scale"):
         if isinstance(getattr(args, k), str) and getattr(args, k).lower() in ("none", "null", ""):
             setattr(args, k, None)
@@ -302,10 +310,17 @@ def setup(args):
             gb = GeneralizedBorn(np.load(args.gb_radii) if args.gb_radii is not None else gb.radii,
                                  np.load(args.gb_scale) if args.gb_scale is not None else gb.scale, **kw)
         extra["implicit_solvent"] = gb
+    if args.alchemical is not None:
+        from .alchemy import Alchemical
+
+        extra["alchemical"] = Alchemical.from_config(args.alchemical)
     forces = Forces(parameters, terms=terms, external=external, cutoff=args.cutoff, rfa=args.rfa,
                     switch_dist=args.switch_dist, exclusions=tuple(args.exclusions), pme=args.pme,
                     ewald_tolerance=args.ewald_tolerance, pme_order=args.pme_order, pme_grid=args.pme_grid, **extra)
     return mol, system, forces
+
+
+ALCHEMICAL_COLUMNS = ("alchemical", "dudl_vdw", "dudl_elec")  # of every monitor file with an `alchemical:` mapping
 
 
 def tip4p_sites(ff, mol):
@@ -398,6 +413,10 @@ def dynamics(args, mol, system, forces):
     columns += ("restraints",) if restrained else ()
     solvent = getattr(forces, "implicit_solvent", None)
     columns += ("implicit_solvent",) if solvent is not None else ()
+    alch = getattr(forces, "alchemical", None)
+    columns += ALCHEMICAL_COLUMNS if alch is not None else ()
+    states = np.asarray(args.alchemical["states"], dtype=np.float64).reshape(-1, 2) if (alch is not None and args.alchemical.get("states")) else None
+    foreign = []  # [frames][R, K] cross energies at `states`
     metad = getattr(forces, "metadynamics", None)
     columns += ("bias",) + tuple(f"cv{c}" for c in range(metad.ncv)) if metad is not None else ()
     logs = [LogWriter(args.log_dir, columns, name=f"monitor_{k}.csv") for k in range(args.replicas)]
@@ -417,11 +436,15 @@ def dynamics(args, mol, system, forces):
         if barostat is not None:
             boxes.append(torch.diagonal(system.box, dim1=-2, dim2=-1).to("cpu", torch.float64).numpy().copy())
         pressure = integrator.pressure() if args.pressure else None  # (of the wrapped positions: molecules are whole)
+        if states is not None:
+            foreign.append(forces.alchemical_energies(system.pos, system.box, states))
         for k in range(args.replicas):
             if (i * args.output_period) % args.save_period == 0 or i == nper:
                 np.save(os.path.join(args.log_dir, f"{name}_{k}{ext or '.npy'}"), stager.frames(k))
                 if barostat is not None:
                     np.save(os.path.join(args.log_dir, f"{name}_box_{k}{ext or '.npy'}"), np.stack([b[k] for b in boxes]))
+                if states is not None:
+                    np.save(os.path.join(args.log_dir, f"{name}_states_{k}.npy"), np.stack([e[k] for e in foreign]))
             row = {"iter": i * args.output_period, "ns": FS2NS * i * args.output_period * args.timestep,
                    "epot": Epot[k], "ekin": float(Ekin[k]), "etot": Epot[k] + float(Ekin[k]), "T": float(T[k])}
             if barostat is not None:
@@ -434,6 +457,9 @@ def dynamics(args, mol, system, forces):
                 row["restraints"] = float(forces._restraint_energy[k].sum())
             if solvent is not None:  # the GB + SA energy inside `epot`, as of the last evaluation
                 row["implicit_solvent"] = float(solvent.energy[k].sum())
+            if alch is not None:  # the cross + intra energy inside `epot` and dU/dlambda, as of the last evaluation
+                row["alchemical"] = float(alch.energy[k, :3].sum())
+                row["dudl_vdw"], row["dudl_elec"] = float(alch.energy[k, 3]), float(alch.energy[k, 4])
             if metad is not None:  # the bias energy inside `epot` and the CVs, as of the last evaluation
                 row["bias"] = float(metad.energy[k])
                 for c in range(metad.ncv):
