@@ -398,9 +398,9 @@ def test_public_surface_and_refusals():
     integ.forces = f
     integ.batch, integ.barostat = torch.zeros(4676, dtype=torch.long), None
     with pytest.raises(ValueError, match="batch"):
-        integ._check_implicit_solvent()
+        integ._check_side_terms()
     integ.batch, integ.barostat = None, Duck()
     with pytest.raises(ValueError, match="barostat"):
-        integ._check_implicit_solvent()
+        integ._check_side_terms()
     integ.barostat = None
-    integ._check_implicit_solvent()
+    integ._check_side_terms()

@@ -563,7 +563,7 @@ def test_water_solute_end_points_and_the_charge_table(prec):
         assert alch.stats(s1.pos)["charge_by_class"] == plain.stats(s0.pos)["charge_by_class"] == 1
 
 
-def _by_hand(case, prec, al, cuts, langevin, algorithm="auto"):
+def _by_hand(case, prec, al, cuts, langevin, algorithm="auto", restraints=None):
     """The truth: tmdhip_first_vv, the total force of an evaluation (the alchemical part added in force mode),
     tmdhip_(langevin_)second_vv."""
     from torchmd_amd import _lib as L
@@ -572,7 +572,7 @@ def _by_hand(case, prec, al, cuts, langevin, algorithm="auto"):
 
     mol, pos, box, par, vel0, R, kw = case
     s = _water_system(mol, pos, box, prec, R, vel0)
-    f = Forces(par, terms=WATER_TERMS, alchemical=al, algorithm=algorithm, **kw)
+    f = Forces(par, terms=WATER_TERMS, alchemical=al, algorithm=algorithm, restraints=restraints, **kw)
     torch.manual_seed(77)
     integ = Integrator(s, f, 1.0, _dev(), **(dict(gamma=50.0, T=300.0) if langevin else {}))
     integ._check_layout()
@@ -590,13 +590,13 @@ def _by_hand(case, prec, al, cuts, langevin, algorithm="auto"):
     return s.pos.cpu().double().numpy(), s.vel.cpu().double().numpy()
 
 
-def _under_test(case, prec, al, cuts, langevin, algorithm="auto"):
+def _under_test(case, prec, al, cuts, langevin, algorithm="auto", restraints=None):
     from torchmd_amd.forces import Forces
     from torchmd_amd.integrator import Integrator
 
     mol, pos, box, par, vel0, R, kw = case
     s = _water_system(mol, pos, box, prec, R, vel0)
-    f = Forces(par, terms=WATER_TERMS, alchemical=al, algorithm=algorithm, **kw)
+    f = Forces(par, terms=WATER_TERMS, alchemical=al, algorithm=algorithm, restraints=restraints, **kw)
     f.compute(s.pos, s.box, s.forces)
     torch.manual_seed(77)
     integ = Integrator(s, f, 1.0, _dev(), **(dict(gamma=50.0, T=300.0) if langevin else {}))
@@ -663,6 +663,78 @@ def test_trajectory_fp32_fused_batched(langevin, monkeypatch):
     cp, cv = _by_hand((mol, pos, box, par32, vel0, R, kw), "f32", Alchemical(SOLUTE_WATER, [0.6, 1.0, 0.1], [0.0, 0.4, 0.0]), CUTS, langevin)
     assert np.abs(cp - tp).max() > 10 * 2 * noise_p and np.abs(cv - tv).max() > 10 * 2 * noise_v
     _check_return("f32", out, f, s)
+
+
+# ----------------------------------------------------------------------------- two side terms at once
+RESTRAINED = [SOLUTE_WATER[0], 0]  # an oxygen of the solute and one of the environment
+RESTRAINT_K = (20.0, 40.0, 0.0)  # kcal/mol/A^2, one strength per replica
+
+
+def _held(pos, k=RESTRAINT_K):
+    """Position restraints that hold the two oxygens 0.5 A off their start, with one strength per replica."""
+    from torchmd_amd import Restraints
+
+    return Restraints(3).add_position(RESTRAINED, pos[RESTRAINED] + np.array([0.5, 0.0, 0.0]), np.repeat(np.array(k)[:, None], 2, axis=1))
+
+
+def _check_both_reported(f, s):
+    d = f.compute(s.pos, s.box, torch.zeros_like(s.pos), returnDetails=True)[0]
+    assert d["alchemical"] != 0.0 and d["restraints"] != 0.0, d
+
+
+@pytest.mark.parametrize("langevin", [False, True], ids=["nve", "langevin"])
+@pytest.mark.parametrize("algorithm", ["celllist", "allpairs"])
+def test_two_side_terms_trajectory_fp64(algorithm, langevin, monkeypatch):
+    """An alchemical solute and restraints together: every active side term is launched at the per-replica dispatch site of
+    tmdhip_md_run (cell list) and at the replicas-together one (all pairs).  The control leaves the restraints out."""
+    from torchmd_amd import Alchemical
+
+    monkeypatch.setenv("TMDHIP_VSKIN", "0")
+    mol, pos, box, par = _water("f64", 12 if algorithm == "celllist" else 6)
+    R = 3
+    case = (mol, pos, box, par, _vel0(mol, R), R, dict(cutoff=CUT, rfa=True, switch_dist=SWD))
+    lam = ([0.5, 1.0, 0.0], [0.0, 0.5, 0.0])
+    tp, tv = _by_hand(case, "f64", Alchemical(SOLUTE_WATER, *lam), CUTS, langevin, algorithm, _held(pos))
+    p, v, out, f, s = _under_test(case, "f64", Alchemical(SOLUTE_WATER, *lam), CUTS, langevin, algorithm, _held(pos))
+    assert f.stats(s.pos)["algorithm"] == algorithm
+    bar_p, bar_v = 64 * EPS64 * 10 * np.abs(tp).max(), 64 * EPS64 * 10 * np.abs(tv).max()
+    print(f"fp64 {algorithm} {'Langevin' if langevin else 'NVE'}, two terms: |dpos| = {np.abs(p - tp).max():.2e} (bar {bar_p:.2e}), "
+          f"|dvel| = {np.abs(v - tv).max():.2e} (bar {bar_v:.2e})")
+    assert np.abs(p - tp).max() <= bar_p and np.abs(v - tv).max() <= bar_v
+    cp, cv = _by_hand(case, "f64", Alchemical(SOLUTE_WATER, *lam), CUTS, langevin, algorithm, _held(pos, (0.0, 0.0, 0.0)))
+    assert np.abs(cp - tp).max() > 10 * bar_p and np.abs(cv - tv).max() > 10 * bar_v
+    _check_return("f64", out, f, s)
+    _check_both_reported(f, s)
+
+
+@pytest.mark.parametrize("langevin", [False, True], ids=["nve", "langevin"])
+def test_two_side_terms_trajectory_fp32_fused_batched(langevin, monkeypatch):
+    """The same through the batched pair + step launch: one impulse launch per active side term serves all replicas."""
+    from torchmd_amd import Alchemical
+
+    monkeypatch.setenv("TMDHIP_VSKIN", "0")
+    R = 3
+    mol, pos, box, par32 = _water("f32", 12)
+    _, _, _, par64 = _water("f64", 12)
+    vel0 = _vel0(mol, R)
+    kw = dict(cutoff=CUT, rfa=True, switch_dist=SWD)
+    lam = ([0.5, 1.0, 0.0], [0.0, 0.5, 0.0])
+    tp, tv = _by_hand((mol, pos, box, par64, vel0, R, kw), "f64", Alchemical(SOLUTE_WATER, *lam), CUTS, langevin, restraints=_held(pos))
+    hp, hv = _by_hand((mol, pos, box, par32, vel0, R, kw), "f32", Alchemical(SOLUTE_WATER, *lam), CUTS, langevin, restraints=_held(pos))
+    p, v, out, f, s = _under_test((mol, pos, box, par32, vel0, R, kw), "f32", Alchemical(SOLUTE_WATER, *lam), CUTS, langevin,
+                                  restraints=_held(pos))
+    noise_p, noise_v = np.abs(hp - tp).max(), np.abs(hv - tv).max()
+    dp, dv = np.abs(p - tp).max(), np.abs(v - tv).max()
+    print(f"fp32 fused R=3 {'Langevin' if langevin else 'NVE'}, two terms: |dpos| = {dp:.2e} (by hand {noise_p:.2e}), "
+          f"|dvel| = {dv:.2e} (by hand {noise_v:.2e})")
+    st = [f.stats(s.pos, r) for r in range(R)]
+    assert all(x["steps_in_pair_launch"] >= 5 for x in st) and st[0]["batched_launches"] >= 5, st
+    assert dp <= 2 * noise_p and dv <= 2 * noise_v
+    cp, cv = _by_hand((mol, pos, box, par32, vel0, R, kw), "f32", Alchemical(SOLUTE_WATER, *lam), CUTS, langevin,
+                      restraints=_held(pos, (0.0, 0.0, 0.0)))
+    assert np.abs(cp - tp).max() > 10 * 2 * noise_p and np.abs(cv - tv).max() > 10 * 2 * noise_v
+    _check_return("f32", out, f, s)
+    _check_both_reported(f, s)
 
 
 # ----------------------------------------------------------------------------- invariants

@@ -556,7 +556,7 @@ def test_library_refusals_launch_nothing():
     boxes = np.array([[30.0, 0.0, 0.0]])
     ptr = lambda t: C.c_void_p(t.data_ptr())  # noqa: E731
     st = C.c_void_p(torch.cuda.current_stream(_dev()).cuda_stream)
-    eng.sync_gb(gb)
+    gb.sync(eng)
     assert lib.tmdhip_gb_apply(eng.ctx, ptr(p), boxes.ctypes.data_as(C.POINTER(C.c_double)), ptr(frc), None, None, 0.0, None, st) < 0
     assert "open boundaries" in L.last_error()
     v, mt = torch.zeros_like(p), torch.full((65,), 12.0, dtype=torch.float64, device=_dev())

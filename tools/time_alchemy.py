@@ -56,7 +56,7 @@ for nwat in (10, 100):  # neighbouring waters around the box centre: solutes of 
         for rep in range(5):  # the launches of one application alone (forces += F, no energies), back to back
             torch.cuda.synchronize(); t0 = time.perf_counter()
             for _ in range(100):
-                eng.apply_alchemical(f.alchemical, s.pos, boxes, F, False)
+                eng.apply_side(f.alchemical, s.pos, boxes, F, False)
             torch.cuda.synchronize(); t.append((time.perf_counter() - t0) / 100)
         f.alchemical_energies(s.pos, s.box, states)
         te = []

@@ -587,3 +587,36 @@ def require_device_tensor(t, name):
             f"`{name}` lives on '{t.device}': torchmd_amd evaluates the hot path with HIP kernels on a ROCm "
             "device only (device='cuda'); there is no CPU fallback. Use the reference torchmd for CPU runs."
         )
+
+
+class SideTerm:
+    """What `Restraints`, `Metadynamics`, `GeneralizedBorn` and `Alchemical` have in common: a force term outside the pair /
+    bonded engine ("Adding a side term").  `Forces`, `Integrator`, run.py and the domain decomposition loop over
+    `forces.SIDE_TERMS` and ask only for what stands here.  A term also provides `sync(eng, owner)`: make the context of the
+    engine `eng` hold this object's tables (`owner`: the `Forces`)."""
+
+    side_name = None  # the key of `compute(returnDetails=True)`, and the default monitor column of run.py
+    side_width = 0  # doubles per replica of the energy row
+    side_potential = slice(None)  # the columns of the row that sum into the potential energy
+    side_apply = side_energy = None  # the C entry points tmdhip_*_apply and tmdhip_*_energy
+    # the message of the ValueError for "vmap", "batch", "barostat", "exchange", "update_atoms", "pressure", "domain"; absent: allowed
+    refusals = {}
+    energy = None  # the row [R, side_width] of the last evaluation that wanted energies, host
+
+    def refusal(self, what):
+        return self.refusals.get(what)
+
+    def potential(self, row):
+        """[R] from an energy row [R, side_width] (numpy or torch): what the term adds to the potential energy."""
+        return row[:, self.side_potential].sum(axis=1)
+
+    def store(self, row):
+        """Take the host copy of an evaluation's energy row."""
+        self.energy = row
+
+    def monitor_columns(self):
+        return (self.side_name,)
+
+    def monitor_row(self, k):
+        """{column: value} of replica k for run.py's monitor file, as of the last evaluation."""
+        return {self.side_name: float(self.energy[k, self.side_potential].sum())}

@@ -74,10 +74,23 @@ def check_closed(atoms, natoms, tuples):
                              "solute must be closed under the topology")
 
 
-class Alchemical:
+class Alchemical(L.SideTerm):
     """`atoms`: the indices of the solute.  `lambda_vdw`, `lambda_elec`: scalars or one value per replica.  `alpha`: the
     soft-core parameter (>= 0).  ValueError: an index given twice or negative, a lambda outside [0, 1], a replica with
     lambda_elec != 0 and lambda_vdw != 1, alpha < 0."""
+
+    side_name, side_width = "alchemical", 5  # (cross LJ, cross electrostatics, intra, dU/dlambda_vdw, dU/dlambda_elec)
+    side_potential = slice(0, 3)  # cross + intra
+    side_apply, side_energy = "tmdhip_alchemical_apply", "tmdhip_alchemical_energy"
+    refusals = {
+        "vmap": "compute() with alchemical= cannot run under torch.vmap (its couplings are per replica of the context)",
+        "batch": "alchemical= does not support atom groups (batch=): its couplings are per replica",
+        "barostat": "alchemical= cannot run under barostat=: the virial lacks the solute's term",
+        "update_atoms": "update_atoms is not available with alchemical=",
+        "pressure": "the pressure and the virial are not available with alchemical= (the virial lacks the solute's term)",
+        "domain": "alchemical= cannot be domain-decomposed (the solute's atoms would straddle bricks, and atom indices "
+                  "change at every migration)",
+    }
 
     def __init__(self, atoms, lambda_vdw=1.0, lambda_elec=1.0, alpha=0.5):
         a = np.atleast_1d(np.asarray(atoms))
@@ -175,6 +188,22 @@ class Alchemical:
         d.n14, d.nbonds, d.nangles, d.ntorsions = len(keep[5]), len(keep[7]), len(keep[8]), len(tors)
         L.check(lib.tmdhip_set_alchemical(ctx, C.byref(d)), "tmdhip_set_alchemical")
         del keep
+
+    def sync(self, eng, owner):
+        """Hand the solute to the context of `eng` when its copy is older (tmdhip_set_alchemical); `owner`: the `Forces`."""
+        if eng.side_seen.get(self.side_name) == (id(self), self.version):
+            return
+        np_dtype = np.float32 if L.dtype_code(eng.dtype) == L.F32 else np.float64
+        pair14, scee14 = self.solute_14(owner.par, owner.energies, np_dtype)
+        self.upload(eng.lib, eng.ctx, eng.nreplicas, eng.alch_charges, eng.alch_classes, pair14, scee14,
+                    self.topology(owner.par, owner.energies))
+        eng.side_seen[self.side_name] = (id(self), self.version)
+
+    def monitor_columns(self):
+        return ("alchemical", "dudl_vdw", "dudl_elec")
+
+    def monitor_row(self, k):
+        return {"alchemical": float(self.energy[k, :3].sum()), "dudl_vdw": float(self.energy[k, 3]), "dudl_elec": float(self.energy[k, 4])}
 
     @classmethod
     def from_config(cls, cfg):

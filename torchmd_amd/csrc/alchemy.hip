@@ -488,17 +488,22 @@ int launch(tmdhip_ctx *ctx, AlchState *S, int rep0, int nrep, const void *pos, c
   return 0;
 }
 
-int state_check(const tmdhip_ctx *ctx, const AlchState *S) {
+static_assert(kSideWidth[kSideAlchemy] == 5, "alch_fold_kernel writes five doubles per replica");
+AlchState *state_of(tmdhip_ctx *ctx) { return (AlchState *)ctx->side[kSideAlchemy].state; }
+
+int state_check(tmdhip_ctx *ctx) {
+  const AlchState *S = state_of(ctx);
   // (what tmdhip_set_alchemical refused may have been switched on since)
-  if (S->natoms != ctx->d.natoms || S->nrep != (int)ctx->rep.size() || ctx->nactive < ctx->d.natoms || ctx->vsites || ctx->pme || ctx->gb)
+  if (S->natoms != ctx->d.natoms || S->nrep != (int)ctx->rep.size() || ctx->nactive < ctx->d.natoms || ctx->vsites || ctx->pme ||
+      ctx->side[kSideGb].state)
     return fail("alchemical: the context has changed since tmdhip_set_alchemical (atoms, passive atoms, virtual sites, PME or GB)");
   return 0;
 }
 
 int launch_any(tmdhip_ctx *ctx, int rep0, int nrep, const void *pos, const void *const *pos_each, const double *box_host, void *forces,
                void *vel, const void *mass, double kick, double *out, hipStream_t st) {
-  AlchState *S = (AlchState *)ctx->alchemy;
-  TMD_TRY(state_check(ctx, S));
+  AlchState *S = state_of(ctx);
+  TMD_TRY(state_check(ctx));
   return ctx->d.dtype == TMDHIP_F32 ? launch<float>(ctx, S, rep0, nrep, pos, pos_each, box_host, forces, vel, mass, kick, out, st)
                                     : launch<double>(ctx, S, rep0, nrep, pos, pos_each, box_host, forces, vel, mass, kick, out, st);
 }
@@ -535,42 +540,19 @@ int download(std::vector<T> &dst, const DevBuf &b, size_t count) {
   return 0;
 }
 
-}  // namespace
+int run_check(tmdhip_ctx *ctx, const char *, const double *, const void *, hipStream_t) { return state_check(ctx); }
 
-namespace tmd {
+double *run_energy(tmdhip_ctx *ctx) { return state_of(ctx)->energy.as<double>(); }
 
-void alchemy_release(tmdhip_ctx *ctx) {
-  AlchState *S = (AlchState *)ctx->alchemy;
+void release(tmdhip_ctx *ctx) {
+  AlchState *S = state_of(ctx);
   if (!S) return;
   S->release();
   delete S;
-  ctx->alchemy = nullptr;
+  ctx->side[kSideAlchemy] = SideTerm{};
 }
 
-int alchemy_run_check(tmdhip_ctx *ctx, const tmdhip_md_desc *d, double *impulse_kick, hipStream_t) {
-  const double gdt = d->vcoeff_dev ? d->gamma * d->dt : 0.0;
-  if (!(1.0 - gdt > 0.0)) return fail("tmdhip_md_run: alchemical decoupling needs 1 - gamma dt > 0 (the impulse is dt a / (1 - gamma dt))");
-  *impulse_kick = d->dt / (1.0 - gdt);
-  return state_check(ctx, (AlchState *)ctx->alchemy);
-}
-
-int alchemy_impulse(tmdhip_ctx *ctx, int rep0, int nrep, const void *pos, const double *box_host, void *vel, const void *mass,
-                    double kick, hipStream_t st) {
-  return launch_any(ctx, rep0, nrep, pos, nullptr, box_host, nullptr, vel, mass, kick, nullptr, st);
-}
-
-int alchemy_impulse_each(tmdhip_ctx *ctx, const void *const *pos_each, const double *box_host, void *vel, const void *mass, double kick,
-                         hipStream_t st) {
-  return launch_any(ctx, 0, (int)ctx->rep.size(), nullptr, pos_each, box_host, nullptr, vel, mass, kick, nullptr, st);
-}
-
-int alchemy_finish(tmdhip_ctx *ctx, const void *pos, const double *box_host, void *vel, void *forces, const void *mass, double kick,
-                   hipStream_t st) {
-  AlchState *S = (AlchState *)ctx->alchemy;
-  return launch_any(ctx, 0, S->nrep, pos, nullptr, box_host, forces, vel, mass, kick, S->energy.as<double>(), st);
-}
-
-}  // namespace tmd
+}  // namespace
 
 extern "C" {
 
@@ -579,7 +561,7 @@ int tmdhip_set_alchemical(tmdhip_ctx *ctx, const tmdhip_alchemical_desc *desc) {
   if (desc->struct_size != (int32_t)sizeof(tmdhip_alchemical_desc)) return fail("tmdhip_set_alchemical: tmdhip_alchemical_desc size mismatch (ABI)");
   if (!desc->enable) {
     TMD_HIP(hipDeviceSynchronize());  // (a launch that reads the tables may still be in flight)
-    alchemy_release(ctx);
+    release(ctx);
     return 0;
   }
   const int n = ctx->d.natoms, nrep = (int)ctx->rep.size(), ns = desc->natoms, T = ctx->d.ntypes;
@@ -587,7 +569,7 @@ int tmdhip_set_alchemical(tmdhip_ctx *ctx, const tmdhip_alchemical_desc *desc) {
   if (ctx->nactive < n) return fail("tmdhip_set_alchemical: not for a context with passive atoms (a brick of the domain decomposition)");
   if (ctx->vsites) return fail("tmdhip_set_alchemical: not for a context with virtual sites");
   if (ctx->pme) return fail("tmdhip_set_alchemical: not with PME (the reciprocal sum has no coupling parameter)");
-  if (ctx->gb) return fail("tmdhip_set_alchemical: not with the generalized-Born model");
+  if (ctx->side[kSideGb].state) return fail("tmdhip_set_alchemical: not with the generalized-Born model");
   if (ctx->d.terms & (TMDHIP_TERM_REPULSION | TMDHIP_TERM_REPULSIONCG))
     return fail("tmdhip_set_alchemical: not with the repulsion / repulsioncg terms");
   const std::string why = alch_validate(n, nrep, ns, desc->atoms_host, desc->lambda_vdw_host, desc->lambda_elec_host, desc->alpha);
@@ -614,7 +596,7 @@ int tmdhip_set_alchemical(tmdhip_ctx *ctx, const tmdhip_alchemical_desc *desc) {
     if (!(desc->scee14_host[p] > 0.0) || !std::isfinite(desc->scee14_host[p])) return fail("tmdhip_set_alchemical: every scee must be finite and positive");
   const std::vector<int32_t> pair14(desc->pair14_host, desc->pair14_host + 2 * desc->n14);
   const std::vector<double> scee(desc->scee14_host, desc->scee14_host + desc->n14);
-  if (AlchState *S = (AlchState *)ctx->alchemy) {
+  if (AlchState *S = state_of(ctx)) {
     // the couplings alone have moved (Alchemical.set_lambdas): they travel as kernel arguments, so nothing on the device changes,
     // nothing is synchronised and launches already enqueued keep the couplings they were enqueued with
     if (S->natoms == n && S->nrep == nrep && S->alpha == desc->alpha && S->atoms_h == atoms && S->cls_h == cls && S->qs_h == qs &&
@@ -685,8 +667,8 @@ int tmdhip_set_alchemical(tmdhip_ctx *ctx, const tmdhip_alchemical_desc *desc) {
                    desc->scee14_host, [](double a, double b) { return a * b; }, off, ent);
   for (const AlchEntry &e : ent)
     if (e.kind == 0 && e.A != 0.0 && !(e.B > 0.0)) return fail("tmdhip_set_alchemical: a solute-solute pair has A != 0 and B <= 0");
-  AlchState *S = (AlchState *)ctx->alchemy;
-  if (!S) ctx->alchemy = S = new AlchState;
+  AlchState *S = state_of(ctx);
+  if (!S) ctx->side[kSideAlchemy] = SideTerm{S = new AlchState, "alchemical decoupling needs", launch_any, run_check, run_energy, release};
   S->nrep = nrep, S->natoms = n, S->ns = ns;
   S->nbA = (n + kTile - 1) / kTile;
   S->nbS = (ns + kTile - 1) / kTile;
@@ -717,11 +699,11 @@ int tmdhip_set_alchemical(tmdhip_ctx *ctx, const tmdhip_alchemical_desc *desc) {
   if (rc == 0) rc = S->sph.ensure(sizeof(double) * 4 * (size_t)nrep);
   if (rc == 0) rc = S->spart.ensure(sizeof(double) * (kMaxStates + 1) * (size_t)nrep * S->nbA);
   if (rc == 0) rc = S->sout.ensure(sizeof(double) * kMaxStates * (size_t)nrep);
-  if (rc == 0) rc = S->energy.ensure(sizeof(double) * 5 * (size_t)nrep);
+  if (rc == 0) rc = S->energy.ensure(sizeof(double) * kSideWidth[kSideAlchemy] * (size_t)nrep);
   if (rc == 0 && hipMemset(S->energy.p, 0, S->energy.bytes) != hipSuccess) rc = fail("tmdhip_set_alchemical: hipMemset failed");
   if (rc == 0 && hipMemset(S->part.p, 0, S->part.bytes) != hipSuccess) rc = fail("tmdhip_set_alchemical: hipMemset failed");
   if (rc != 0) {
-    alchemy_release(ctx);
+    release(ctx);
     return rc;
   }
   TMD_HIP(hipDeviceSynchronize());
@@ -730,37 +712,18 @@ int tmdhip_set_alchemical(tmdhip_ctx *ctx, const tmdhip_alchemical_desc *desc) {
 
 int tmdhip_alchemical_apply(tmdhip_ctx *ctx, const void *pos_dev, const double *box_host, void *forces_dev, void *vel_dev,
                             const void *mass_dev, double kick, double *energies_dev, void *stream) {
-  if (!ctx) return fail("tmdhip_alchemical_apply: null context");
-  hipStream_t st = (hipStream_t)stream;
-  if (!ctx->alchemy) {
-    if (energies_dev) TMD_HIP(hipMemsetAsync(energies_dev, 0, sizeof(double) * 5 * ctx->rep.size(), st));
-    return 0;
-  }
-  if (!pos_dev || !box_host) return fail("tmdhip_alchemical_apply: null positions or boxes");
-  if (vel_dev && !mass_dev) return fail("tmdhip_alchemical_apply: velocities need masses");
-  if (vel_dev && !std::isfinite(kick)) return fail("tmdhip_alchemical_apply: the kick must be finite");
-  if (!forces_dev && !vel_dev && !energies_dev) return 0;
-  return launch_any(ctx, 0, (int)ctx->rep.size(), pos_dev, nullptr, box_host, forces_dev, vel_dev, mass_dev, kick, energies_dev, st);
+  return side_apply(ctx, kSideAlchemy, "tmdhip_alchemical_apply", pos_dev, box_host, forces_dev, vel_dev, mass_dev, kick, energies_dev,
+                    stream);
 }
 
 int tmdhip_alchemical_energy(tmdhip_ctx *ctx, double *out_host, void *stream) {
-  if (!ctx || !out_host) return fail("tmdhip_alchemical_energy: null argument");
-  const size_t count = 5 * ctx->rep.size();
-  AlchState *S = (AlchState *)ctx->alchemy;
-  if (!S) {
-    for (size_t k = 0; k < count; ++k) out_host[k] = 0.0;
-    return 0;
-  }
-  hipStream_t st = (hipStream_t)stream;
-  TMD_HIP(hipMemcpyAsync(out_host, S->energy.p, sizeof(double) * count, hipMemcpyDeviceToHost, st));
-  TMD_HIP(hipStreamSynchronize(st));
-  return 0;
+  return side_energy(ctx, kSideAlchemy, "tmdhip_alchemical_energy", out_host, stream);
 }
 
 int tmdhip_alchemical_states(tmdhip_ctx *ctx, const void *pos_dev, const double *box_host, int32_t nstates, const double *states_host,
                              double *out_host, void *stream) {
   if (!ctx || !pos_dev || !box_host || !states_host || !out_host) return fail("tmdhip_alchemical_states: null argument");
-  AlchState *S = (AlchState *)ctx->alchemy;
+  AlchState *S = state_of(ctx);
   if (!S) return fail("tmdhip_alchemical_states: the context has no alchemical state (tmdhip_set_alchemical)");
   if (nstates < 1 || nstates > kMaxStates) return fail("tmdhip_alchemical_states: between 1 and 32 states per call");
   StateArgs A;
@@ -772,7 +735,7 @@ int tmdhip_alchemical_states(tmdhip_ctx *ctx, const void *pos_dev, const double 
       return fail("tmdhip_alchemical_states: every lambda must lie in [0, 1]");
     if (A.lam_e[k] != 0.0 && A.lam_v[k] != 1.0) return fail("tmdhip_alchemical_states: lambda_elec must be 0 or lambda_vdw must be 1");
   }
-  TMD_TRY(state_check(ctx, S));
+  TMD_TRY(state_check(ctx));
   hipStream_t st = (hipStream_t)stream;
   TMD_TRY(ctx->d.dtype == TMDHIP_F32 ? launch_states<float>(ctx, S, pos_dev, box_host, A, st)
                                      : launch_states<double>(ctx, S, pos_dev, box_host, A, st));

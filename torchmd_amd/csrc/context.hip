@@ -426,6 +426,39 @@ template int compute_list<float>(tmdhip_ctx *, Replica &, const void *, const do
 template int compute_list<double>(tmdhip_ctx *, Replica &, const void *, const double *, void *, double *, int, hipStream_t,
                                   const FusedLaunchT<double> *, ListOnlyOut *);
 
+int side_apply(tmdhip_ctx *ctx, int which, const char *fn, const void *pos_dev, const double *box_host, void *forces_dev, void *vel_dev,
+               const void *mass_dev, double kick, double *energies_dev, void *stream) {
+  const std::string who(fn);
+  if (!ctx) return fail(who + ": null context");
+  hipStream_t st = (hipStream_t)stream;
+  const SideTerm &t = ctx->side[which];
+  const int nrep = (int)ctx->rep.size();
+  if (!t.state) {
+    if (energies_dev) TMD_HIP(hipMemsetAsync(energies_dev, 0, sizeof(double) * kSideWidth[which] * nrep, st));
+    return 0;
+  }
+  if (!pos_dev || !box_host) return fail(who + ": null positions or boxes");
+  if (vel_dev && !mass_dev) return fail(who + ": velocities need masses");
+  if (vel_dev && !std::isfinite(kick)) return fail(who + ": the kick must be finite");
+  if (!forces_dev && !vel_dev && !energies_dev) return 0;
+  TMD_TRY(t.run_check(ctx, fn, box_host, vel_dev ? mass_dev : nullptr, st));
+  return t.launch(ctx, 0, nrep, pos_dev, nullptr, box_host, forces_dev, vel_dev, mass_dev, kick, energies_dev, st);
+}
+
+int side_energy(tmdhip_ctx *ctx, int which, const char *fn, double *out_host, void *stream) {
+  if (!ctx || !out_host) return fail(std::string(fn) + ": null argument");
+  const size_t count = kSideWidth[which] * ctx->rep.size();
+  const SideTerm &t = ctx->side[which];
+  if (!t.state) {
+    std::fill(out_host, out_host + count, 0.0);
+    return 0;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  TMD_HIP(hipMemcpyAsync(out_host, t.run_energy(ctx), sizeof(double) * count, hipMemcpyDeviceToHost, st));
+  TMD_HIP(hipStreamSynchronize(st));
+  return 0;
+}
+
 }  // namespace tmd
 
 using namespace tmd;
@@ -551,10 +584,8 @@ void tmdhip_destroy(tmdhip_ctx *ctx) {
   tmd::pme_release(ctx);
   tmd::cons_release(ctx);
   tmd::vsite_release(ctx);
-  tmd::restraint_release(ctx);
-  tmd::metad_release(ctx);
-  tmd::gb_release(ctx);
-  tmd::alchemy_release(ctx);
+  for (tmd::SideTerm &t : ctx->side)
+    if (t.state) t.release(ctx);
   tmd::virial_release(ctx);
   delete ctx;
 }

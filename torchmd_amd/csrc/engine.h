@@ -577,6 +577,27 @@ struct Replica {
   }
 };
 
+// A side term: a force outside the pair / bonded engine.  tmdhip_md_run applies it as the impulse dt / (1 - gamma dt) to the
+// half-step velocities between two launches; a finishing launch adds dt/2 a, adds the force to the caller's array and writes
+// the energy row ("Adding a side term").  The order of the slots is the launch order and part of the contract:
+// velocity increments are floating-point adds, so another order changes bits.
+enum { kSideRestraints, kSideMetad, kSideGb, kSideAlchemy, kSideTerms };
+// doubles per replica of a term's energy row (known while the term is off: tmdhip_*_apply / _energy zero the row then)
+constexpr int kSideWidth[kSideTerms] = {2, 3, 2, 5};
+struct SideTerm {
+  void *state = nullptr;  // null: off (no launch, nothing allocated); the term's tmdhip_set_* fills the slot, its release clears it
+  const char *needs = nullptr;  // for messages: "restraints need", "metadynamics needs", ...
+  // replicas rep0 .. rep0 + nrep - 1; forces / vel point at the rows of replica rep0, box_host at its box; the positions are
+  // [nrep][N][3] at `pos`, or, with `pos_each`, one array per replica.  Whatever is not null is served: forces += F,
+  // vel += kick F / m, out (double [R][kSideWidth], indexed by the replica's number) = the energies.
+  int (*launch)(tmdhip_ctx *ctx, int rep0, int nrep, const void *pos, const void *const *pos_each, const double *box_host, void *forces,
+                void *vel, const void *mass, double kick, double *out, hipStream_t st);
+  // what the term alone refuses before a run or an evaluation named `who`; mass_dev is null where no velocity is touched
+  int (*run_check)(tmdhip_ctx *ctx, const char *who, const double *box_host, const void *mass_dev, hipStream_t st);
+  double *(*run_energy)(tmdhip_ctx *ctx);  // the device row [R][kSideWidth] that the finishing launch of tmdhip_md_run writes
+  void (*release)(tmdhip_ctx *ctx);
+};
+
 }  // namespace tmd
 
 struct tmdhip_ctx {
@@ -649,14 +670,8 @@ struct tmdhip_ctx {
   void *cons = nullptr;
   // virtual sites the context's own launches serve (tmdhip_set_vsites), vsite.hip; null: none
   void *vsites = nullptr;
-  // harmonic restraints (tmdhip_set_restraints), restraint.hip; null: off (no launch, nothing allocated)
-  void *restraints = nullptr;
-  // the metadynamics bias (tmdhip_set_metadynamics), metad.hip; null: off (no launch, nothing allocated)
-  void *metad = nullptr;
-  // the generalized-Born implicit solvent (tmdhip_set_gb), gb.hip; null: off (no launch, nothing allocated)
-  void *gb = nullptr;
-  // alchemical decoupling of a solute (tmdhip_set_alchemical), alchemy.hip; null: off (no launch, nothing allocated)
-  void *alchemy = nullptr;
+  // the force terms outside the pair / bonded engine (SideTerm above), in launch order
+  tmd::SideTerm side[tmd::kSideTerms];
   // the molecule table and scratch of the pressure observable (tmdhip_set_molecules), virial.hip; null: not set
   void *virial = nullptr;
   // timing of the dominant kernel
@@ -861,49 +876,12 @@ void launch_cons_step(const tmdhip_ctx *ctx, const MdStepArgs<R> &a, const PairC
                       bool check, int nrep, hipStream_t st);
 // vsite.hip
 void vsite_release(tmdhip_ctx *ctx);
-// restraint.hip (only called with ctx->restraints set, except the release)
-void restraint_release(tmdhip_ctx *ctx);
-// what tmdhip_md_run refuses with restraints; on success *impulse_kick = dt / (1 - gamma dt) (gamma = 0 without Langevin)
-int restraint_run_check(tmdhip_ctx *ctx, const tmdhip_md_desc *d, double *impulse_kick, hipStream_t st);
-// vel += kick F_r(pos) / m for replicas rep0 .. rep0 + nrep - 1, whose rows pos / vel point at; box_host: of replica rep0 on
-int restraint_impulse(tmdhip_ctx *ctx, int rep0, int nrep, const void *pos, const double *box_host, void *vel, const void *mass,
-                      double kick, hipStream_t st);
-// the same for all replicas in one launch per 16, replica r's positions at pos_each[r] (the batched pair + step launch)
-int restraint_impulse_each(tmdhip_ctx *ctx, const void *const *pos_each, const double *box_host, void *vel, const void *mass, double kick,
-                           hipStream_t st);
-// after the last step of a call, all replicas: vel += kick F_r / m, forces += F_r, the context's energies [R][2]
-int restraint_finish(tmdhip_ctx *ctx, const void *pos, const double *box_host, void *vel, void *forces, const void *mass, double kick,
-                     hipStream_t st);
-// metad.hip (only called with ctx->metad set, except the release): the same four places, for the metadynamics bias
 // virial.hip
 void virial_release(tmdhip_ctx *ctx);
-void metad_release(tmdhip_ctx *ctx);
-int metad_run_check(tmdhip_ctx *ctx, const tmdhip_md_desc *d, double *impulse_kick, hipStream_t st);
-int metad_impulse(tmdhip_ctx *ctx, int rep0, int nrep, const void *pos, const double *box_host, void *vel, const void *mass, double kick,
-                  hipStream_t st);
-int metad_impulse_each(tmdhip_ctx *ctx, const void *const *pos_each, const double *box_host, void *vel, const void *mass, double kick,
-                       hipStream_t st);
-int metad_finish(tmdhip_ctx *ctx, const void *pos, const double *box_host, void *vel, void *forces, const void *mass, double kick,
-                 hipStream_t st);
-// gb.hip (only called with ctx->gb set, except the release): the same four places, for the generalized-Born implicit solvent
-// (box_host is checked by gb_run_check: open boundaries only)
-void gb_release(tmdhip_ctx *ctx);
-int gb_run_check(tmdhip_ctx *ctx, const tmdhip_md_desc *d, double *impulse_kick, hipStream_t st);
-int gb_impulse(tmdhip_ctx *ctx, int rep0, int nrep, const void *pos, const double *box_host, void *vel, const void *mass, double kick,
-               hipStream_t st);
-int gb_impulse_each(tmdhip_ctx *ctx, const void *const *pos_each, const double *box_host, void *vel, const void *mass, double kick,
-                    hipStream_t st);
-int gb_finish(tmdhip_ctx *ctx, const void *pos, const double *box_host, void *vel, void *forces, const void *mass, double kick,
-              hipStream_t st);
-// alchemy.hip (only called with ctx->alchemy set, except the release): the same four places, for the alchemical solute
-void alchemy_release(tmdhip_ctx *ctx);
-int alchemy_run_check(tmdhip_ctx *ctx, const tmdhip_md_desc *d, double *impulse_kick, hipStream_t st);
-int alchemy_impulse(tmdhip_ctx *ctx, int rep0, int nrep, const void *pos, const double *box_host, void *vel, const void *mass, double kick,
-                    hipStream_t st);
-int alchemy_impulse_each(tmdhip_ctx *ctx, const void *const *pos_each, const double *box_host, void *vel, const void *mass, double kick,
-                         hipStream_t st);
-int alchemy_finish(tmdhip_ctx *ctx, const void *pos, const double *box_host, void *vel, void *forces, const void *mass, double kick,
-                   hipStream_t st);
+// context.hip: what the C entry points tmdhip_*_apply / tmdhip_*_energy of the side terms share (`fn`: the entry point's name)
+int side_apply(tmdhip_ctx *ctx, int which, const char *fn, const void *pos_dev, const double *box_host, void *forces_dev, void *vel_dev,
+               const void *mass_dev, double kick, double *energies_dev, void *stream);
+int side_energy(tmdhip_ctx *ctx, int which, const char *fn, double *out_host, void *stream);
 int64_t pme_evaluations(const tmdhip_ctx *ctx, int r);
 int64_t pme_bytes(const tmdhip_ctx *ctx);
 // md_loop.hip

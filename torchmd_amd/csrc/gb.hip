@@ -278,9 +278,13 @@ int launch(tmdhip_ctx *ctx, GbState *S, int rep0, int nrep, const void *pos, con
   return 0;
 }
 
-int launch_any(tmdhip_ctx *ctx, int rep0, int nrep, const void *pos, const void *const *pos_each, void *forces, void *vel,
+static_assert(kSideWidth[kSideGb] == 2, "gb_fold_kernel writes (GB, SA) per replica");
+GbState *state_of(tmdhip_ctx *ctx) { return (GbState *)ctx->side[kSideGb].state; }
+
+// (no box: check_boxes has seen that every edge is zero)
+int launch_any(tmdhip_ctx *ctx, int rep0, int nrep, const void *pos, const void *const *pos_each, const double *, void *forces, void *vel,
                const void *mass, double kick, double *out, hipStream_t st) {
-  GbState *S = (GbState *)ctx->gb;
+  GbState *S = state_of(ctx);
   // (what tmdhip_set_gb refused may have been switched on since)
   if (S->natoms != ctx->d.natoms || S->nrep != (int)ctx->rep.size() || ctx->nactive < ctx->d.natoms || ctx->vsites || ctx->pme)
     return fail("generalized Born: the context has changed since tmdhip_set_gb (atoms, passive atoms, virtual sites or PME)");
@@ -289,8 +293,8 @@ int launch_any(tmdhip_ctx *ctx, int rep0, int nrep, const void *pos, const void 
 }
 
 // open boundaries only: every edge of every replica's box is zero
-int check_boxes(const char *who, const double *box_host, int nrep) {
-  for (int k = 0; k < 3 * nrep; ++k)
+int check_boxes(tmdhip_ctx *ctx, const char *who, const double *box_host, const void *, hipStream_t) {
+  for (size_t k = 0; k < 3 * ctx->rep.size(); ++k)
     if (box_host[k] != 0.0) return fail(std::string(who) + ": the generalized-Born model needs open boundaries (every box edge 0)");
   return 0;
 }
@@ -302,41 +306,17 @@ int upload(DevBuf &b, const std::vector<T> &src) {
   return 0;
 }
 
-}  // namespace
+double *run_energy(tmdhip_ctx *ctx) { return state_of(ctx)->energy.as<double>(); }
 
-namespace tmd {
-
-void gb_release(tmdhip_ctx *ctx) {
-  GbState *S = (GbState *)ctx->gb;
+void release(tmdhip_ctx *ctx) {
+  GbState *S = state_of(ctx);
   if (!S) return;
   S->release();
   delete S;
-  ctx->gb = nullptr;
+  ctx->side[kSideGb] = SideTerm{};
 }
 
-int gb_run_check(tmdhip_ctx *ctx, const tmdhip_md_desc *d, double *impulse_kick, hipStream_t) {
-  const double gdt = d->vcoeff_dev ? d->gamma * d->dt : 0.0;
-  if (!(1.0 - gdt > 0.0)) return fail("tmdhip_md_run: the generalized-Born model needs 1 - gamma dt > 0 (the impulse is dt a / (1 - gamma dt))");
-  *impulse_kick = d->dt / (1.0 - gdt);
-  return check_boxes("tmdhip_md_run", d->box_host, (int)ctx->rep.size());
-}
-
-int gb_impulse(tmdhip_ctx *ctx, int rep0, int nrep, const void *pos, const double *, void *vel, const void *mass, double kick,
-               hipStream_t st) {
-  return launch_any(ctx, rep0, nrep, pos, nullptr, nullptr, vel, mass, kick, nullptr, st);
-}
-
-int gb_impulse_each(tmdhip_ctx *ctx, const void *const *pos_each, const double *, void *vel, const void *mass, double kick,
-                    hipStream_t st) {
-  return launch_any(ctx, 0, (int)ctx->rep.size(), nullptr, pos_each, nullptr, vel, mass, kick, nullptr, st);
-}
-
-int gb_finish(tmdhip_ctx *ctx, const void *pos, const double *, void *vel, void *forces, const void *mass, double kick, hipStream_t st) {
-  GbState *S = (GbState *)ctx->gb;
-  return launch_any(ctx, 0, S->nrep, pos, nullptr, forces, vel, mass, kick, S->energy.as<double>(), st);
-}
-
-}  // namespace tmd
+}  // namespace
 
 extern "C" {
 
@@ -345,7 +325,7 @@ int tmdhip_set_gb(tmdhip_ctx *ctx, const tmdhip_gb_desc *desc) {
   if (desc->struct_size != (int32_t)sizeof(tmdhip_gb_desc)) return fail("tmdhip_set_gb: tmdhip_gb_desc size mismatch (ABI)");
   if (!desc->enable) {
     TMD_HIP(hipDeviceSynchronize());  // (a launch that reads the tables may still be in flight)
-    gb_release(ctx);
+    release(ctx);
     return 0;
   }
   const int n = ctx->d.natoms, nrep = (int)ctx->rep.size();
@@ -367,8 +347,8 @@ int tmdhip_set_gb(tmdhip_ctx *ctx, const tmdhip_gb_desc *desc) {
       return fail("tmdhip_set_gb: the scale of atom " + std::to_string(i) + " must be finite and not negative");
   }
   TMD_HIP(hipDeviceSynchronize());  // (a launch that reads the old tables may still be in flight)
-  GbState *S = (GbState *)ctx->gb;
-  if (!S) ctx->gb = S = new GbState;
+  GbState *S = state_of(ctx);
+  if (!S) ctx->side[kSideGb] = SideTerm{S = new GbState, "the generalized-Born model needs", launch_any, check_boxes, run_energy, release};
   S->nrep = nrep;
   S->natoms = n;
   S->nb = (n + kTile - 1) / kTile;
@@ -405,11 +385,11 @@ int tmdhip_set_gb(tmdhip_ctx *ctx, const tmdhip_gb_desc *desc) {
   if (rc == 0) rc = S->born_r.ensure((size_t)ctx->real_size * rn);
   if (rc == 0) rc = S->b_r.ensure((size_t)ctx->real_size * rn);
   if (rc == 0) rc = S->epart.ensure(sizeof(double) * (size_t)nrep * (S->nsplit * S->nb + S->nb));
-  if (rc == 0) rc = S->energy.ensure(sizeof(double) * 2 * (size_t)nrep);
+  if (rc == 0) rc = S->energy.ensure(sizeof(double) * kSideWidth[kSideGb] * (size_t)nrep);
   if (rc == 0 && hipMemset(S->energy.p, 0, S->energy.bytes) != hipSuccess) rc = fail("tmdhip_set_gb: hipMemset failed");
   if (rc == 0 && hipMemset(S->born.p, 0, S->born.bytes) != hipSuccess) rc = fail("tmdhip_set_gb: hipMemset failed");
   if (rc != 0) {
-    gb_release(ctx);
+    release(ctx);
     return rc;
   }
   TMD_HIP(hipDeviceSynchronize());
@@ -418,36 +398,16 @@ int tmdhip_set_gb(tmdhip_ctx *ctx, const tmdhip_gb_desc *desc) {
 
 int tmdhip_gb_apply(tmdhip_ctx *ctx, const void *pos_dev, const double *box_host, void *forces_dev, void *vel_dev, const void *mass_dev,
                     double kick, double *energies_dev, void *stream) {
-  if (!ctx) return fail("tmdhip_gb_apply: null context");
-  hipStream_t st = (hipStream_t)stream;
-  if (!ctx->gb) {
-    if (energies_dev) TMD_HIP(hipMemsetAsync(energies_dev, 0, sizeof(double) * 2 * ctx->rep.size(), st));
-    return 0;
-  }
-  if (!pos_dev || !box_host) return fail("tmdhip_gb_apply: null positions or boxes");
-  if (vel_dev && !mass_dev) return fail("tmdhip_gb_apply: velocities need masses");
-  if (vel_dev && !std::isfinite(kick)) return fail("tmdhip_gb_apply: the kick must be finite");
-  TMD_TRY(check_boxes("tmdhip_gb_apply", box_host, (int)ctx->rep.size()));
-  return launch_any(ctx, 0, (int)ctx->rep.size(), pos_dev, nullptr, forces_dev, vel_dev, mass_dev, kick, energies_dev, st);
+  return side_apply(ctx, kSideGb, "tmdhip_gb_apply", pos_dev, box_host, forces_dev, vel_dev, mass_dev, kick, energies_dev, stream);
 }
 
 int tmdhip_gb_energy(tmdhip_ctx *ctx, double *out_host, void *stream) {
-  if (!ctx || !out_host) return fail("tmdhip_gb_energy: null argument");
-  const size_t count = 2 * ctx->rep.size();
-  GbState *S = (GbState *)ctx->gb;
-  if (!S) {
-    for (size_t k = 0; k < count; ++k) out_host[k] = 0.0;
-    return 0;
-  }
-  hipStream_t st = (hipStream_t)stream;
-  TMD_HIP(hipMemcpyAsync(out_host, S->energy.p, sizeof(double) * count, hipMemcpyDeviceToHost, st));
-  TMD_HIP(hipStreamSynchronize(st));
-  return 0;
+  return side_energy(ctx, kSideGb, "tmdhip_gb_energy", out_host, stream);
 }
 
 int tmdhip_gb_born_radii(tmdhip_ctx *ctx, double *out_host) {
   if (!ctx || !out_host) return fail("tmdhip_gb_born_radii: null argument");
-  GbState *S = (GbState *)ctx->gb;
+  GbState *S = state_of(ctx);
   if (!S) return fail("tmdhip_gb_born_radii: the context has no generalized-Born state (tmdhip_set_gb)");
   TMD_HIP(hipDeviceSynchronize());
   TMD_HIP(hipMemcpy(out_host, S->born.p, sizeof(double) * (size_t)S->nrep * S->natoms, hipMemcpyDeviceToHost));

@@ -434,19 +434,17 @@ struct MdRun {
   int batch_bonded = 0;
   int it = 0;
   bool first = true, second = false;
-  // restraints (restraint.hip): the impulse dt / (1 - gamma dt) that stands for a_r in the step that follows a force launch
-  const bool restrained;
-  const bool biased;  // the metadynamics bias (metad.hip): the same impulse, a launch of its own
-  const bool solvated;  // the generalized-Born implicit solvent (gb.hip): the same impulse, behind the other two
-  const bool alchemical;  // the alchemical solute (alchemy.hip): the same impulse, last
+  // the side terms (SideTerm, engine.h): the impulse dt / (1 - gamma dt) that stands for their acceleration in the step that
+  // follows a force launch, one launch per active term in the order of the table
+  bool any_side = false;
   double impulse_kick = 0;
   std::vector<const void *> impulse_pos;  // a batched iteration: where each replica's positions live, for ONE impulse launch
 
   MdRun(tmdhip_ctx *ctx_, const tmdhip_md_desc *d_, hipStream_t st_)
       : ctx(ctx_), d(d_), st(st_), n(ctx_->d.natoms), nrep((int)ctx_->rep.size()), stride((size_t)ctx_->d.natoms * 3),
         langevin(d_->vcoeff_dev != nullptr), cur(nrep), owed(nrep, 0), stepped(nrep, 0), finalized(nrep, 0),
-        home_all((R *)d_->pos_dev), bcur((R *)d_->pos_dev), restrained(ctx_->restraints != nullptr), biased(ctx_->metad != nullptr),
-        solvated(ctx_->gb != nullptr), alchemical(ctx_->alchemy != nullptr) {
+        home_all((R *)d_->pos_dev), bcur((R *)d_->pos_dev) {
+    for (const SideTerm &t : ctx->side) any_side = any_side || t.state;
     const char *e_min = std::getenv("TMDHIP_DEBUG_CHAIN_MIN_ENTRIES"), *e_near = std::getenv("TMDHIP_DEBUG_CHAIN_NEAR"),
                *e_batch = std::getenv("TMDHIP_BATCH_REPLICAS");
     chain_skip_on = !env_is_zero("TMDHIP_CHAIN_SKIP") && !ctx->no_chain_skip_once;
@@ -491,10 +489,7 @@ struct MdRun {
   }
 
   int run() {
-    if (restrained) TMD_TRY(restraint_run_check(ctx, d, &impulse_kick, st));
-    if (biased) TMD_TRY(metad_run_check(ctx, d, &impulse_kick, st));
-    if (solvated) TMD_TRY(gb_run_check(ctx, d, &impulse_kick, st));
-    if (alchemical) TMD_TRY(alchemy_run_check(ctx, d, &impulse_kick, st));
+    if (any_side) TMD_TRY(check_side_terms());
     TMD_TRY(snapshot_unless_first_kernel_takes_it());
     for (it = 0; it <= d->niter; ++it) {
       first = it < d->niter;
@@ -516,42 +511,38 @@ struct MdRun {
       }
     }
     TMD_TRY(copy_home());
-    if (restrained) TMD_TRY(finish_restraints());
-    if (biased) TMD_TRY(finish_metad());
-    if (solvated) TMD_TRY(finish_gb());
-    return alchemical ? finish_alchemy() : 0;
+    return any_side ? finish_side_terms() : 0;
   }
 
-  // Restraints, the last step of the call: dt/2 a_r for the velocities, F_r for the caller's forces (total on return, and the
-  // next call's first half kick is right), the restraint energies.  The kinetic energy the last launch summed is stale.
-  int finish_restraints() {
-    TMD_TRY(restraint_finish(ctx, d->pos_dev, d->box_host, d->vel_dev, d->forces_dev, d->mass_dev, 0.5 * d->dt, st));
-    ctx->ke_from_run = nullptr;
-    ctx->run_published_seq = 0;
+  // What a run with side terms refuses: 1 - gamma dt <= 0 (in the name of the first active term), and what each term checks
+  // itself (masses, boxes, state).  Sets impulse_kick = dt / (1 - gamma dt), gamma = 0 without Langevin.
+  int check_side_terms() {
+    const double gdt = langevin ? d->gamma * d->dt : 0.0;
+    for (const SideTerm &t : ctx->side) {
+      if (!t.state) continue;
+      if (!(1.0 - gdt > 0.0))
+        return fail(std::string("tmdhip_md_run: ") + t.needs + " 1 - gamma dt > 0 (the impulse is dt a / (1 - gamma dt))");
+      TMD_TRY(t.run_check(ctx, "tmdhip_md_run", d->box_host, d->mass_dev, st));
+    }
+    impulse_kick = d->dt / (1.0 - gdt);
     return 0;
   }
 
-  // The metadynamics bias, the last step of the call: the same three things (metad.hip)
-  int finish_metad() {
-    TMD_TRY(metad_finish(ctx, d->pos_dev, d->box_host, d->vel_dev, d->forces_dev, d->mass_dev, 0.5 * d->dt, st));
-    ctx->ke_from_run = nullptr;
-    ctx->run_published_seq = 0;
+  // vel += impulse_kick F / m of every active side term, for replicas rep0 .. rep0 + n_rep - 1 (arguments as SideTerm::launch)
+  int side_impulses(int rep0, int n_rep, const void *pos, const void *const *pos_each, const double *box_host, void *vel) {
+    for (const SideTerm &t : ctx->side)
+      if (t.state) TMD_TRY(t.launch(ctx, rep0, n_rep, pos, pos_each, box_host, nullptr, vel, d->mass_dev, impulse_kick, nullptr, st));
     return 0;
   }
 
-  // The generalized-Born model, the last step of the call: the same three things (gb.hip)
-  int finish_gb() {
-    TMD_TRY(gb_finish(ctx, d->pos_dev, d->box_host, d->vel_dev, d->forces_dev, d->mass_dev, 0.5 * d->dt, st));
-    ctx->ke_from_run = nullptr;
+  // The side terms, the last step of the call: dt/2 a for the velocities, F for the caller's forces (total on return, and the
+  // next call's first half kick is right), the term's energies.  The kinetic energy the last launch summed is stale.
+  int finish_side_terms() {
+    ctx->ke_from_run = nullptr;  // (before the first kick: a launch that fails leaves nothing stale published)
     ctx->run_published_seq = 0;
-    return 0;
-  }
-
-  // The alchemical solute, the last step of the call: the same three things (alchemy.hip)
-  int finish_alchemy() {
-    TMD_TRY(alchemy_finish(ctx, d->pos_dev, d->box_host, d->vel_dev, d->forces_dev, d->mass_dev, 0.5 * d->dt, st));
-    ctx->ke_from_run = nullptr;
-    ctx->run_published_seq = 0;
+    for (const SideTerm &t : ctx->side)
+      if (t.state)
+        TMD_TRY(t.launch(ctx, 0, nrep, d->pos_dev, nullptr, d->box_host, d->forces_dev, d->vel_dev, d->mass_dev, 0.5 * d->dt, t.run_energy(ctx), st));
     return 0;
   }
 
@@ -608,12 +599,7 @@ struct MdRun {
     TMD_HIP(hipGetLastError());
     if (!first) return 0;
     R *pos = bcur;
-    if (restrained && it + 1 < d->niter)
-      TMD_TRY(restraint_impulse(ctx, 0, nrep, pos, d->box_host, d->vel_dev, d->mass_dev, impulse_kick, st));
-    if (biased && it + 1 < d->niter) TMD_TRY(metad_impulse(ctx, 0, nrep, pos, d->box_host, d->vel_dev, d->mass_dev, impulse_kick, st));
-    if (solvated && it + 1 < d->niter) TMD_TRY(gb_impulse(ctx, 0, nrep, pos, d->box_host, d->vel_dev, d->mass_dev, impulse_kick, st));
-    if (alchemical && it + 1 < d->niter)
-      TMD_TRY(alchemy_impulse(ctx, 0, nrep, pos, d->box_host, d->vel_dev, d->mass_dev, impulse_kick, st));
+    if (any_side && it + 1 < d->niter) TMD_TRY(side_impulses(0, nrep, pos, nullptr, d->box_host, d->vel_dev));
     int flags_c = TMDHIP_WANT_FORCES;
     double *en = nullptr;
     if (wants_energy()) {
@@ -800,15 +786,12 @@ struct MdRun {
     const int r = s.r;
     R *pos = cur[r];
     // (positions x_{it+1}, velocities v_{it+1/2} on every path: the step behind this launch turns the impulse into a_r's kicks)
-    if ((restrained || biased || solvated || alchemical) && it + 1 < d->niter) {
+    if (any_side && it + 1 < d->niter) {
       if (batching) {  // (one launch for all replicas in front of finish_batch's)
         impulse_pos.resize(nrep);
         impulse_pos[r] = pos;
       } else {
-        if (restrained) TMD_TRY(restraint_impulse(ctx, r, 1, pos, s.box, (R *)d->vel_dev + r * stride, d->mass_dev, impulse_kick, st));
-        if (biased) TMD_TRY(metad_impulse(ctx, r, 1, pos, s.box, (R *)d->vel_dev + r * stride, d->mass_dev, impulse_kick, st));
-        if (solvated) TMD_TRY(gb_impulse(ctx, r, 1, pos, s.box, (R *)d->vel_dev + r * stride, d->mass_dev, impulse_kick, st));
-        if (alchemical) TMD_TRY(alchemy_impulse(ctx, r, 1, pos, s.box, (R *)d->vel_dev + r * stride, d->mass_dev, impulse_kick, st));
+        TMD_TRY(side_impulses(r, 1, pos, nullptr, s.box, (R *)d->vel_dev + r * stride));
       }
     }
     int flags_c = TMDHIP_WANT_FORCES;
@@ -923,14 +906,8 @@ struct MdRun {
 
   int finish_batch() {
     const bool want_e = wants_energy();
-    if (restrained && it + 1 < d->niter)
-      TMD_TRY(restraint_impulse_each(ctx, impulse_pos.data(), d->box_host, d->vel_dev, d->mass_dev, impulse_kick, st));
-    if (biased && it + 1 < d->niter)
-      TMD_TRY(metad_impulse_each(ctx, impulse_pos.data(), d->box_host, d->vel_dev, d->mass_dev, impulse_kick, st));
-    if (solvated && it + 1 < d->niter)
-      TMD_TRY(gb_impulse_each(ctx, impulse_pos.data(), d->box_host, d->vel_dev, d->mass_dev, impulse_kick, st));
-    if (alchemical && it + 1 < d->niter)
-      TMD_TRY(alchemy_impulse_each(ctx, impulse_pos.data(), d->box_host, d->vel_dev, d->mass_dev, impulse_kick, st));
+    // (all replicas in one launch per term and 16 replicas, replica r's positions at impulse_pos[r])
+    if (any_side && it + 1 < d->niter) TMD_TRY(side_impulses(0, nrep, nullptr, impulse_pos.data(), d->box_host, d->vel_dev));
     {  // the rebuild chains the host has not left out: one launch per kernel for all of them
       std::vector<int> reps, par;
       std::vector<const float *> ps;

@@ -168,9 +168,12 @@ int launch(MetadState *S, int rep0, int nrep, const void *pos, const void *const
   return 0;
 }
 
+static_assert(kSideWidth[kSideMetad] == kOut, "the bias kernel reports kOut doubles per replica");
+MetadState *state_of(tmdhip_ctx *ctx) { return (MetadState *)ctx->side[kSideMetad].state; }
+
 int launch_any(tmdhip_ctx *ctx, int rep0, int nrep, const void *pos, const void *const *pos_each, const double *box_host, void *forces,
                void *vel, const void *mass, double kick, double *out, hipStream_t st) {
-  MetadState *S = (MetadState *)ctx->metad;
+  MetadState *S = state_of(ctx);
   return ctx->d.dtype == TMDHIP_F32 ? launch<float>(S, rep0, nrep, pos, pos_each, box_host, forces, vel, mass, kick, out, st)
                                     : launch<double>(S, rep0, nrep, pos, pos_each, box_host, forces, vel, mass, kick, out, st);
 }
@@ -197,9 +200,9 @@ int launch_deposit(MetadState *S, const void *pos, const double *box_host, doubl
 }
 
 // a CV atom without mass has no acceleration: refused where masses are first seen (one read-back per mass array)
-int check_masses(tmdhip_ctx *ctx, const void *mass_dev, hipStream_t st) {
-  MetadState *S = (MetadState *)ctx->metad;
-  if (S->mass_checked == mass_dev) return 0;
+int check_masses(tmdhip_ctx *ctx, const char *, const double *, const void *mass_dev, hipStream_t st) {
+  MetadState *S = state_of(ctx);
+  if (!mass_dev || S->mass_checked == mass_dev) return 0;
   std::vector<char> host((size_t)ctx->real_size * S->natoms);
   TMD_HIP(hipMemcpyAsync(host.data(), mass_dev, host.size(), hipMemcpyDeviceToHost, st));
   TMD_HIP(hipStreamSynchronize(st));
@@ -212,43 +215,18 @@ int check_masses(tmdhip_ctx *ctx, const void *mass_dev, hipStream_t st) {
   return 0;
 }
 
-}  // namespace
+double *run_energy(tmdhip_ctx *ctx) { return state_of(ctx)->last.as<double>(); }
 
-namespace tmd {
-
-void metad_release(tmdhip_ctx *ctx) {
-  MetadState *S = (MetadState *)ctx->metad;
+void release(tmdhip_ctx *ctx) {
+  MetadState *S = state_of(ctx);
   if (!S) return;
   S->grid.release();
   S->last.release();
   delete S;
-  ctx->metad = nullptr;
+  ctx->side[kSideMetad] = SideTerm{};
 }
 
-int metad_run_check(tmdhip_ctx *ctx, const tmdhip_md_desc *d, double *impulse_kick, hipStream_t st) {
-  const double gdt = d->vcoeff_dev ? d->gamma * d->dt : 0.0;
-  if (!(1.0 - gdt > 0.0)) return fail("tmdhip_md_run: metadynamics needs 1 - gamma dt > 0 (the impulse is dt a_b / (1 - gamma dt))");
-  *impulse_kick = d->dt / (1.0 - gdt);
-  return check_masses(ctx, d->mass_dev, st);
-}
-
-int metad_impulse(tmdhip_ctx *ctx, int rep0, int nrep, const void *pos, const double *box_host, void *vel, const void *mass, double kick,
-                  hipStream_t st) {
-  return launch_any(ctx, rep0, nrep, pos, nullptr, box_host, nullptr, vel, mass, kick, nullptr, st);
-}
-
-int metad_impulse_each(tmdhip_ctx *ctx, const void *const *pos_each, const double *box_host, void *vel, const void *mass, double kick,
-                       hipStream_t st) {
-  return launch_any(ctx, 0, (int)ctx->rep.size(), nullptr, pos_each, box_host, nullptr, vel, mass, kick, nullptr, st);
-}
-
-int metad_finish(tmdhip_ctx *ctx, const void *pos, const double *box_host, void *vel, void *forces, const void *mass, double kick,
-                 hipStream_t st) {
-  MetadState *S = (MetadState *)ctx->metad;
-  return launch_any(ctx, 0, S->nrep, pos, nullptr, box_host, forces, vel, mass, kick, S->last.as<double>(), st);
-}
-
-}  // namespace tmd
+}  // namespace
 
 extern "C" {
 
@@ -257,7 +235,7 @@ int tmdhip_set_metadynamics(tmdhip_ctx *ctx, const tmdhip_metad_desc *desc) {
   if (desc->struct_size != (int32_t)sizeof(tmdhip_metad_desc)) return fail("tmdhip_set_metadynamics: tmdhip_metad_desc size mismatch (ABI)");
   if (!desc->enable) {
     TMD_HIP(hipDeviceSynchronize());  // (a launch that reads the grid may still be in flight)
-    metad_release(ctx);
+    release(ctx);
     return 0;
   }
   const int n = ctx->d.natoms, nrep = (int)ctx->rep.size();
@@ -273,9 +251,9 @@ int tmdhip_set_metadynamics(tmdhip_ctx *ctx, const tmdhip_metad_desc *desc) {
         return fail("tmdhip_set_metadynamics: atom " + std::to_string(D.row_atom[t]) + " is a virtual site (use its parents)");
   }
   TMD_HIP(hipDeviceSynchronize());  // (a launch that reads the old grid may still be in flight)
-  metad_release(ctx);
+  release(ctx);
   MetadState *S = new MetadState;
-  ctx->metad = S;
+  ctx->side[kSideMetad] = SideTerm{S, "metadynamics needs", launch_any, check_masses, run_energy, release};
   S->nrep = nrep;
   S->natoms = n;
   S->shared = desc->shared ? 1 : 0;
@@ -287,7 +265,7 @@ int tmdhip_set_metadynamics(tmdhip_ctx *ctx, const tmdhip_metad_desc *desc) {
   if (rc == 0 && (hipMemset(S->grid.p, 0, S->grid.bytes) != hipSuccess || hipMemset(S->last.p, 0, S->last.bytes) != hipSuccess))
     rc = fail("tmdhip_set_metadynamics: hipMemset failed");
   if (rc != 0) {
-    metad_release(ctx);
+    release(ctx);
     return rc;
   }
   TMD_HIP(hipDeviceSynchronize());
@@ -296,24 +274,13 @@ int tmdhip_set_metadynamics(tmdhip_ctx *ctx, const tmdhip_metad_desc *desc) {
 
 int tmdhip_metad_apply(tmdhip_ctx *ctx, const void *pos_dev, const double *box_host, void *forces_dev, void *vel_dev, const void *mass_dev,
                        double kick, double *out_dev, void *stream) {
-  if (!ctx) return fail("tmdhip_metad_apply: null context");
-  hipStream_t st = (hipStream_t)stream;
-  if (!ctx->metad) {
-    if (out_dev) TMD_HIP(hipMemsetAsync(out_dev, 0, sizeof(double) * kOut * ctx->rep.size(), st));
-    return 0;
-  }
-  if (!pos_dev || !box_host) return fail("tmdhip_metad_apply: null positions or boxes");
-  if (vel_dev && !mass_dev) return fail("tmdhip_metad_apply: velocities need masses");
-  if (vel_dev && !std::isfinite(kick)) return fail("tmdhip_metad_apply: the kick must be finite");
-  if (!forces_dev && !vel_dev && !out_dev) return 0;
-  if (vel_dev) TMD_TRY(check_masses(ctx, mass_dev, st));
-  return launch_any(ctx, 0, (int)ctx->rep.size(), pos_dev, nullptr, box_host, forces_dev, vel_dev, mass_dev, kick, out_dev, st);
+  return side_apply(ctx, kSideMetad, "tmdhip_metad_apply", pos_dev, box_host, forces_dev, vel_dev, mass_dev, kick, out_dev, stream);
 }
 
 int tmdhip_metad_deposit(tmdhip_ctx *ctx, const void *pos_dev, const double *box_host, double height, double kdt, int plain,
                          double *log_row_dev, void *stream) {
   if (!ctx) return fail("tmdhip_metad_deposit: null context");
-  MetadState *S = (MetadState *)ctx->metad;
+  MetadState *S = state_of(ctx);
   if (!S) return fail("tmdhip_metad_deposit: the context has no metadynamics (tmdhip_set_metadynamics)");
   if (!pos_dev || !box_host || !log_row_dev) return fail("tmdhip_metad_deposit: null positions, boxes or log row");
   if (!(height > 0.0) || !std::isfinite(height)) return fail("tmdhip_metad_deposit: the height must be finite and positive");
@@ -324,22 +291,12 @@ int tmdhip_metad_deposit(tmdhip_ctx *ctx, const void *pos_dev, const double *box
 }
 
 int tmdhip_metad_energy(tmdhip_ctx *ctx, double *out_host, void *stream) {
-  if (!ctx || !out_host) return fail("tmdhip_metad_energy: null argument");
-  const size_t count = kOut * ctx->rep.size();
-  MetadState *S = (MetadState *)ctx->metad;
-  if (!S) {
-    for (size_t k = 0; k < count; ++k) out_host[k] = 0.0;
-    return 0;
-  }
-  hipStream_t st = (hipStream_t)stream;
-  TMD_HIP(hipMemcpyAsync(out_host, S->last.p, sizeof(double) * count, hipMemcpyDeviceToHost, st));
-  TMD_HIP(hipStreamSynchronize(st));
-  return 0;
+  return side_energy(ctx, kSideMetad, "tmdhip_metad_energy", out_host, stream);
 }
 
 int tmdhip_metad_get_grid(tmdhip_ctx *ctx, double *out_host, int64_t count) {
   if (!ctx || !out_host) return fail("tmdhip_metad_get_grid: null argument");
-  MetadState *S = (MetadState *)ctx->metad;
+  MetadState *S = state_of(ctx);
   if (!S) return fail("tmdhip_metad_get_grid: the context has no metadynamics");
   if (count != (int64_t)S->grid_doubles()) return fail("tmdhip_metad_get_grid: the grid holds " + std::to_string(S->grid_doubles()) + " doubles");
   TMD_HIP(hipDeviceSynchronize());
@@ -349,7 +306,7 @@ int tmdhip_metad_get_grid(tmdhip_ctx *ctx, double *out_host, int64_t count) {
 
 int tmdhip_metad_set_grid(tmdhip_ctx *ctx, const double *in_host, int64_t count) {
   if (!ctx || !in_host) return fail("tmdhip_metad_set_grid: null argument");
-  MetadState *S = (MetadState *)ctx->metad;
+  MetadState *S = state_of(ctx);
   if (!S) return fail("tmdhip_metad_set_grid: the context has no metadynamics");
   if (count != (int64_t)S->grid_doubles()) return fail("tmdhip_metad_set_grid: the grid holds " + std::to_string(S->grid_doubles()) + " doubles");
   TMD_HIP(hipDeviceSynchronize());

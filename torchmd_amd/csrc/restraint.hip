@@ -163,17 +163,20 @@ int launch(RestraintState *S, int rep0, int nrep, const void *pos, const void *c
   return 0;
 }
 
+static_assert(kSideWidth[kSideRestraints] == 2, "restraint_fold_kernel writes (position, distance) per replica");
+RestraintState *state_of(tmdhip_ctx *ctx) { return (RestraintState *)ctx->side[kSideRestraints].state; }
+
 int launch_any(tmdhip_ctx *ctx, int rep0, int nrep, const void *pos, const void *const *pos_each, const double *box_host, void *forces,
                void *vel, const void *mass, double kick, double *out, hipStream_t st) {
-  RestraintState *S = (RestraintState *)ctx->restraints;
+  RestraintState *S = state_of(ctx);
   return ctx->d.dtype == TMDHIP_F32 ? launch<float>(S, rep0, nrep, pos, pos_each, box_host, forces, vel, mass, kick, out, st)
                                     : launch<double>(S, rep0, nrep, pos, pos_each, box_host, forces, vel, mass, kick, out, st);
 }
 
 // a restrained atom without mass has no acceleration: refused where masses are first seen (one read-back per mass array)
-int check_masses(tmdhip_ctx *ctx, const void *mass_dev, hipStream_t st) {
-  RestraintState *S = (RestraintState *)ctx->restraints;
-  if (S->mass_checked == mass_dev) return 0;
+int check_masses(tmdhip_ctx *ctx, const char *, const double *, const void *mass_dev, hipStream_t st) {
+  RestraintState *S = state_of(ctx);
+  if (!mass_dev || S->mass_checked == mass_dev) return 0;
   std::vector<char> host((size_t)ctx->real_size * S->natoms);
   TMD_HIP(hipMemcpyAsync(host.data(), mass_dev, host.size(), hipMemcpyDeviceToHost, st));
   TMD_HIP(hipStreamSynchronize(st));
@@ -185,6 +188,16 @@ int check_masses(tmdhip_ctx *ctx, const void *mass_dev, hipStream_t st) {
   return 0;
 }
 
+double *run_energy(tmdhip_ctx *ctx) { return state_of(ctx)->energy.as<double>(); }
+
+void release(tmdhip_ctx *ctx) {
+  RestraintState *S = state_of(ctx);
+  if (!S) return;
+  S->release();
+  delete S;
+  ctx->side[kSideRestraints] = SideTerm{};
+}
+
 template <typename T>
 int upload(DevBuf &b, const T *src, size_t count) {
   TMD_TRY(b.ensure(std::max<size_t>(sizeof(T) * count, 16)));
@@ -194,41 +207,6 @@ int upload(DevBuf &b, const T *src, size_t count) {
 
 }  // namespace
 
-namespace tmd {
-
-void restraint_release(tmdhip_ctx *ctx) {
-  RestraintState *S = (RestraintState *)ctx->restraints;
-  if (!S) return;
-  S->release();
-  delete S;
-  ctx->restraints = nullptr;
-}
-
-int restraint_run_check(tmdhip_ctx *ctx, const tmdhip_md_desc *d, double *impulse_kick, hipStream_t st) {
-  const double gdt = d->vcoeff_dev ? d->gamma * d->dt : 0.0;
-  if (!(1.0 - gdt > 0.0)) return fail("tmdhip_md_run: restraints need 1 - gamma dt > 0 (the impulse is dt a_r / (1 - gamma dt))");
-  *impulse_kick = d->dt / (1.0 - gdt);
-  return check_masses(ctx, d->mass_dev, st);
-}
-
-int restraint_impulse(tmdhip_ctx *ctx, int rep0, int nrep, const void *pos, const double *box_host, void *vel, const void *mass,
-                      double kick, hipStream_t st) {
-  return launch_any(ctx, rep0, nrep, pos, nullptr, box_host, nullptr, vel, mass, kick, nullptr, st);
-}
-
-int restraint_impulse_each(tmdhip_ctx *ctx, const void *const *pos_each, const double *box_host, void *vel, const void *mass, double kick,
-                           hipStream_t st) {
-  return launch_any(ctx, 0, (int)ctx->rep.size(), nullptr, pos_each, box_host, nullptr, vel, mass, kick, nullptr, st);
-}
-
-int restraint_finish(tmdhip_ctx *ctx, const void *pos, const double *box_host, void *vel, void *forces, const void *mass, double kick,
-                     hipStream_t st) {
-  RestraintState *S = (RestraintState *)ctx->restraints;
-  return launch_any(ctx, 0, S->nrep, pos, nullptr, box_host, forces, vel, mass, kick, S->energy.as<double>(), st);
-}
-
-}  // namespace tmd
-
 extern "C" {
 
 int tmdhip_set_restraints(tmdhip_ctx *ctx, const tmdhip_restraint_desc *desc) {
@@ -236,7 +214,7 @@ int tmdhip_set_restraints(tmdhip_ctx *ctx, const tmdhip_restraint_desc *desc) {
   if (desc->struct_size != (int32_t)sizeof(tmdhip_restraint_desc)) return fail("tmdhip_set_restraints: tmdhip_restraint_desc size mismatch (ABI)");
   if (!desc->enable || (desc->npos == 0 && desc->ndist == 0)) {
     TMD_HIP(hipDeviceSynchronize());  // (a launch that reads the tables may still be in flight)
-    restraint_release(ctx);
+    release(ctx);
     return 0;
   }
   const int n = ctx->d.natoms, nrep = (int)ctx->rep.size();
@@ -255,8 +233,8 @@ int tmdhip_set_restraints(tmdhip_ctx *ctx, const tmdhip_restraint_desc *desc) {
         return fail("tmdhip_set_restraints: atom " + std::to_string(s) + " is a virtual site (restrain its parents)");
   }
   TMD_HIP(hipDeviceSynchronize());  // (a launch that reads the old tables may still be in flight)
-  RestraintState *S = (RestraintState *)ctx->restraints;
-  if (!S) ctx->restraints = S = new RestraintState;
+  RestraintState *S = state_of(ctx);
+  if (!S) ctx->side[kSideRestraints] = SideTerm{S = new RestraintState, "restraints need", launch_any, check_masses, run_energy, release};
   const bool same_atoms = S->atom_h == atoms;
   S->nrep = nrep;
   S->natoms = n;
@@ -275,12 +253,12 @@ int tmdhip_set_restraints(tmdhip_ctx *ctx, const tmdhip_restraint_desc *desc) {
   if (rc == 0) rc = upload(S->dist_r0, desc->dist_r0_host, nd);
   if (rc == 0) rc = upload(S->dist_k, desc->dist_k_host, nd);
   if (rc == 0) rc = S->partials.ensure(sizeof(double) * 2 * (size_t)nrep * S->nblocks);
-  if (rc == 0 && S->energy.bytes < sizeof(double) * 2 * (size_t)nrep) {
-    rc = S->energy.ensure(sizeof(double) * 2 * (size_t)nrep);
+  if (rc == 0 && S->energy.bytes < sizeof(double) * kSideWidth[kSideRestraints] * (size_t)nrep) {
+    rc = S->energy.ensure(sizeof(double) * kSideWidth[kSideRestraints] * (size_t)nrep);
     if (rc == 0 && hipMemset(S->energy.p, 0, S->energy.bytes) != hipSuccess) rc = fail("tmdhip_set_restraints: hipMemset failed");
   }
   if (rc != 0) {
-    restraint_release(ctx);
+    release(ctx);
     return rc;
   }
   TMD_HIP(hipDeviceSynchronize());
@@ -289,32 +267,12 @@ int tmdhip_set_restraints(tmdhip_ctx *ctx, const tmdhip_restraint_desc *desc) {
 
 int tmdhip_restraint_apply(tmdhip_ctx *ctx, const void *pos_dev, const double *box_host, void *forces_dev, void *vel_dev,
                            const void *mass_dev, double kick, double *energies_dev, void *stream) {
-  if (!ctx) return fail("tmdhip_restraint_apply: null context");
-  hipStream_t st = (hipStream_t)stream;
-  if (!ctx->restraints) {
-    if (energies_dev) TMD_HIP(hipMemsetAsync(energies_dev, 0, sizeof(double) * 2 * ctx->rep.size(), st));
-    return 0;
-  }
-  if (!pos_dev || !box_host) return fail("tmdhip_restraint_apply: null positions or boxes");
-  if (vel_dev && !mass_dev) return fail("tmdhip_restraint_apply: velocities need masses");
-  if (vel_dev && !std::isfinite(kick)) return fail("tmdhip_restraint_apply: the kick must be finite");
-  if (!forces_dev && !vel_dev && !energies_dev) return 0;
-  if (vel_dev) TMD_TRY(check_masses(ctx, mass_dev, st));
-  return launch_any(ctx, 0, (int)ctx->rep.size(), pos_dev, nullptr, box_host, forces_dev, vel_dev, mass_dev, kick, energies_dev, st);
+  return side_apply(ctx, kSideRestraints, "tmdhip_restraint_apply", pos_dev, box_host, forces_dev, vel_dev, mass_dev, kick, energies_dev,
+                    stream);
 }
 
 int tmdhip_restraint_energy(tmdhip_ctx *ctx, double *out_host, void *stream) {
-  if (!ctx || !out_host) return fail("tmdhip_restraint_energy: null argument");
-  const size_t count = 2 * ctx->rep.size();
-  RestraintState *S = (RestraintState *)ctx->restraints;
-  if (!S) {
-    for (size_t k = 0; k < count; ++k) out_host[k] = 0.0;
-    return 0;
-  }
-  hipStream_t st = (hipStream_t)stream;
-  TMD_HIP(hipMemcpyAsync(out_host, S->energy.p, sizeof(double) * count, hipMemcpyDeviceToHost, st));
-  TMD_HIP(hipStreamSynchronize(st));
-  return 0;
+  return side_energy(ctx, kSideRestraints, "tmdhip_restraint_energy", out_host, stream);
 }
 
 }  // extern "C"

@@ -613,18 +613,12 @@ class DomainSet:
             raise ValueError("PME electrostatics cannot be domain-decomposed (no distributed FFT)")
         if engine_kwargs.get("virtual_sites") is not None:
             raise ValueError("virtual sites cannot be domain-decomposed (a site and its parents would straddle bricks)")
-        if engine_kwargs.get("restraints") is not None:
-            raise ValueError("restraints cannot be domain-decomposed (a pair's atoms would straddle bricks, and atom indices change "
-                             "at every migration)")
-        if engine_kwargs.get("metadynamics") is not None:
-            raise ValueError("metadynamics cannot be domain-decomposed (a CV's atoms would straddle bricks, and atom indices change "
-                             "at every migration)")
-        if engine_kwargs.get("implicit_solvent") is not None:
-            raise ValueError("implicit_solvent cannot be domain-decomposed (the generalized-Born sums run over all pairs of atoms, "
-                             "and a brick holds passive atoms)")
-        if engine_kwargs.get("alchemical") is not None:
-            raise ValueError("alchemical= cannot be domain-decomposed (the solute's atoms would straddle bricks, and atom indices "
-                             "change at every migration)")
+        from .forces import SIDE_TERMS
+
+        for name in SIDE_TERMS:
+            if engine_kwargs.get(name) is not None:
+                why = getattr(engine_kwargs[name], "refusal", lambda what: None)("domain")
+                raise ValueError(why or f"{name} cannot be domain-decomposed")
         self.dry = bool(dry)  # CPU tensors, no force engine (DryDomain): the plumbing of an N-rank run without a GPU
         self.grid = BrickGrid(box, world, grid)
         self.device, self.dtype = torch.device(device), dtype

@@ -51,6 +51,16 @@ def build_exclusion_csr(natoms, pairs):
 
 _LIVE_ENGINES = weakref.WeakSet()
 
+# The attributes of a `Forces` that hold its side terms (`_lib.SideTerm`: Restraints, Metadynamics, GeneralizedBorn, Alchemical),
+# in the order of the library's table (engine.h).  The order is fixed: it is the launch order, and the order in which the energies
+# are added to the potential; both are floating-point sums, so another order changes bits.
+SIDE_TERMS = ("restraints", "metadynamics", "implicit_solvent", "alchemical")
+
+
+def active_side_terms(forces):
+    """The side terms of any force object (one without the attributes has none), in the order of SIDE_TERMS."""
+    return [t for t in (getattr(forces, a, None) for a in SIDE_TERMS) if t is not None]
+
 
 @atexit.register
 def _close_all_engines():
@@ -235,78 +245,46 @@ class _Engine:
         self.comb = torch.zeros(nreplicas * (L.NENERGY + 1), dtype=torch.float64, device=device)
         self.ebuf = self.comb[: nreplicas * L.NENERGY].view(nreplicas, L.NENERGY)
         self.kebuf = self.comb[nreplicas * L.NENERGY:]
-        self.rbuf = torch.zeros(nreplicas, 2, dtype=torch.float64, device=device)  # restraint energies (position, distance)
-        self._restraint_version = None
-        self.mbuf = torch.zeros(nreplicas, 3, dtype=torch.float64, device=device)  # metadynamics: (V, s_0, s_1) per replica
-        self.gbuf = torch.zeros(nreplicas, 2, dtype=torch.float64, device=device)  # implicit solvent: (GB, SA) per replica
-        self._gb_set = None
-        self.abuf = torch.zeros(nreplicas, 5, dtype=torch.float64, device=device)  # alchemical: (cross LJ, cross el, intra, dU/dlv, dU/dle)
-        self._alch_version = None
+        # the side terms (SIDE_TERMS): the energy row [R, side_width] of each, allocated on first use, and what the term's
+        # `sync` has last handed to this context
+        self.side_buf = {}
+        self.side_seen = {}
         _LIVE_ENGINES.add(self)
         del keep
 
+    def side_row(self, term):
+        """The device row [R, side_width] (float64) that `apply_side` fills with the term's energies."""
+        buf = self.side_buf.get(term.side_name)
+        if buf is None:
+            buf = self.side_buf[term.side_name] = torch.zeros(self.nreplicas, term.side_width, dtype=torch.float64, device=self.comb.device)
+        return buf
+
+    def apply_side(self, term, pos, boxes, forces, want_energy):
+        """forces += the term's force and / or its energies into `side_row(term)`, on the current stream (tmdhip_*_apply)."""
+        if forces is None and not want_energy:
+            return
+        L.check(getattr(self.lib, term.side_apply)(self.ctx, C.c_void_p(pos.data_ptr()), boxes.ctypes.data_as(C.POINTER(C.c_double)),
+                                                   C.c_void_p(forces.data_ptr()) if forces is not None else C.c_void_p(), C.c_void_p(),
+                                                   C.c_void_p(), 0.0,
+                                                   C.c_void_p(self.side_row(term).data_ptr()) if want_energy else C.c_void_p(),
+                                                   C.c_void_p(torch.cuda.current_stream(pos.device).cuda_stream)), term.side_apply)
+
+    # The names under which the tests of a single term drive it through the engine (tests/test_gpu_restraints.py,
+    # tests/test_gpu_alchemy.py): the same calls as above, spelled for one term.
     def sync_restraints(self, rs):
-        """Upload the tables of a `restraints.Restraints` when this context's copy is older (tmdhip_set_restraints)."""
-        if rs is None or self._restraint_version == (id(rs), rs.version):
-            return
-        if rs.nreplicas != self.nreplicas:
-            raise ValueError(f"restraints were made for {rs.nreplicas} replicas, the positions have {self.nreplicas}")
-        rs.upload(self.lib, self.ctx)
-        self._restraint_version = (id(rs), rs.version)
-
-    def apply_restraints(self, rs, pos, boxes, forces, want_energy):
-        """forces += F_r and / or the restraint energies into `rbuf`, on the current stream (tmdhip_restraint_apply)."""
-        if rs is None or (forces is None and not want_energy):
-            return
-        L.check(self.lib.tmdhip_restraint_apply(self.ctx, C.c_void_p(pos.data_ptr()), boxes.ctypes.data_as(C.POINTER(C.c_double)),
-                                                C.c_void_p(forces.data_ptr()) if forces is not None else C.c_void_p(), C.c_void_p(),
-                                                C.c_void_p(), 0.0, C.c_void_p(self.rbuf.data_ptr()) if want_energy else C.c_void_p(),
-                                                C.c_void_p(torch.cuda.current_stream(pos.device).cuda_stream)), "tmdhip_restraint_apply")
-
-    def apply_metad(self, md, pos, boxes, forces, want_energy):
-        """forces += F_b and / or (V, CVs) into `mbuf`, on the current stream (tmdhip_metad_apply)."""
-        if md is None or (forces is None and not want_energy):
-            return
-        L.check(self.lib.tmdhip_metad_apply(self.ctx, C.c_void_p(pos.data_ptr()), boxes.ctypes.data_as(C.POINTER(C.c_double)),
-                                            C.c_void_p(forces.data_ptr()) if forces is not None else C.c_void_p(), C.c_void_p(),
-                                            C.c_void_p(), 0.0, C.c_void_p(self.mbuf.data_ptr()) if want_energy else C.c_void_p(),
-                                            C.c_void_p(torch.cuda.current_stream(pos.device).cuda_stream)), "tmdhip_metad_apply")
-
-    def sync_gb(self, gb):
-        """Hand a `implicit.GeneralizedBorn` to the context on first sight (tmdhip_set_gb)."""
-        if gb is None or self._gb_set is gb:
-            return
-        gb.upload(self.lib, self.ctx)
-        self._gb_set = gb
-
-    def apply_gb(self, gb, pos, boxes, forces, want_energy):
-        """forces += F_GB and / or (GB, SA) into `gbuf`, on the current stream (tmdhip_gb_apply)."""
-        if gb is None or (forces is None and not want_energy):
-            return
-        L.check(self.lib.tmdhip_gb_apply(self.ctx, C.c_void_p(pos.data_ptr()), boxes.ctypes.data_as(C.POINTER(C.c_double)),
-                                         C.c_void_p(forces.data_ptr()) if forces is not None else C.c_void_p(), C.c_void_p(),
-                                         C.c_void_p(), 0.0, C.c_void_p(self.gbuf.data_ptr()) if want_energy else C.c_void_p(),
-                                         C.c_void_p(torch.cuda.current_stream(pos.device).cuda_stream)), "tmdhip_gb_apply")
+        if rs is not None:
+            rs.sync(self)
 
     def sync_alchemical(self, owner):
-        """Hand the owner's `alchemy.Alchemical` to the context when this context's copy is older (tmdhip_set_alchemical)."""
-        al = owner.alchemical
-        if al is None or self._alch_version == (id(al), al.version):
-            return
-        np_dtype = np.float32 if self.dtype == torch.float32 else np.float64
-        pair14, scee14 = al.solute_14(owner.par, owner.energies, np_dtype)
-        al.upload(self.lib, self.ctx, self.nreplicas, self.alch_charges, self.alch_classes, pair14, scee14,
-                  al.topology(owner.par, owner.energies))
-        self._alch_version = (id(al), al.version)
+        if owner.alchemical is not None:
+            owner.alchemical.sync(self, owner)
 
     def apply_alchemical(self, al, pos, boxes, forces, want_energy):
-        """forces += F and / or the five numbers into `abuf`, on the current stream (tmdhip_alchemical_apply)."""
-        if al is None or (forces is None and not want_energy):
-            return
-        L.check(self.lib.tmdhip_alchemical_apply(self.ctx, C.c_void_p(pos.data_ptr()), boxes.ctypes.data_as(C.POINTER(C.c_double)),
-                                                 C.c_void_p(forces.data_ptr()) if forces is not None else C.c_void_p(), C.c_void_p(),
-                                                 C.c_void_p(), 0.0, C.c_void_p(self.abuf.data_ptr()) if want_energy else C.c_void_p(),
-                                                 C.c_void_p(torch.cuda.current_stream(pos.device).cuda_stream)), "tmdhip_alchemical_apply")
+        self.apply_side(al, pos, boxes, forces, want_energy)
+
+    @property
+    def abuf(self):
+        return self.side_buf["alchemical"]
 
     def set_constraints(self, cs):
         """Hand a `constraints.ConstraintSet` to the context (tmdhip_set_constraints); None releases it."""
@@ -541,7 +519,6 @@ class Forces:
             if not isinstance(restraints, Restraints):
                 raise ValueError("restraints must be a restraints.Restraints")
             restraints.check(self.natoms, torch.as_tensor(parameters.masses).detach().cpu().double().reshape(-1).numpy(), virtual_sites)
-        self._restraint_energy = None  # [R, 2] (position, distance) of the last synchronous evaluation, host
         self.metadynamics = metadynamics
         if metadynamics is not None:
             from .metadynamics import Metadynamics
@@ -581,9 +558,25 @@ class Forces:
                 tables = (torch.as_tensor(A).detach().cpu().double().numpy(), torch.as_tensor(B).detach().cpu().double().numpy(),
                           parameters.mapped_atom_types.detach().cpu().numpy())
             alchemical.check(self.natoms, parameters, self.energies, self._excl_csr, tables)
+        self._side_potential = {}  # {side_name: [R]} of the last synchronous evaluation, host
         self._engines = {}
         self._box_cache = None
         self._ava_idx = None
+
+    def _active_side_terms(self):
+        """The side terms this object holds, in the order of SIDE_TERMS."""
+        return active_side_terms(self)
+
+    def _refuse_side_terms(self, what):
+        """ValueError with the message of the first side term that cannot go with `what` (SideTerm.refusals)."""
+        for t in self._active_side_terms():
+            if t.refusal(what):
+                raise ValueError(t.refusal(what))
+
+    @property
+    def _restraint_energy(self):
+        """[R, 2] (position, distance) of the last evaluation that wanted energies, host."""
+        return self.restraints.energy if self.restraints is not None else None
 
     def _alch_engine(self, pos):
         if self.alchemical is None:
@@ -628,7 +621,7 @@ class Forces:
         boxes = self._replica_boxes(box, R)
         out = np.empty((R, len(st)), dtype=np.float64)
         with torch.cuda.device(p.device):
-            eng.sync_alchemical(self)
+            self.alchemical.sync(eng, self)
             stream = C.c_void_p(torch.cuda.current_stream(p.device).cuda_stream)
             for k0 in range(0, len(st), MAX_STATES):
                 part = np.ascontiguousarray(st[k0 : k0 + MAX_STATES])
@@ -655,7 +648,7 @@ class Forces:
             eng = next(iter(self._engines.values()))
         else:
             raise ValueError("born_radii(): no evaluation yet, or several contexts: pass the positions")
-        if eng._gb_set is None:
+        if eng.side_seen.get(self.implicit_solvent.side_name) is None:
             raise ValueError("born_radii(): no evaluation yet")
         out = np.empty((eng.nreplicas, self.natoms), dtype=np.float64)
         L.check(eng.lib.tmdhip_gb_born_radii(eng.ctx, out.ctypes.data_as(C.POINTER(C.c_double))), "tmdhip_gb_born_radii")
@@ -690,10 +683,7 @@ class Forces:
         neighbour list and zero force).  Used by the domain decomposition at every atom migration."""
         if self.virtual_sites is not None:
             raise ValueError("update_atoms is not available with virtual_sites")
-        if self.implicit_solvent is not None:
-            raise ValueError("update_atoms is not available with implicit_solvent")
-        if self.alchemical is not None:
-            raise ValueError("update_atoms is not available with alchemical=")
+        self._refuse_side_terms("update_atoms")
         if any(t in self.energies for t in self.bonded) or len(self._excl_csr[1]):
             raise RuntimeError("update_atoms is only available for atomic systems")
         self.par = parameters
@@ -866,11 +856,8 @@ class Forces:
         self._gb_box(self._host_box(box))
         eng = self._engine(p, exact)
         with torch.cuda.device(p.device):
-            eng.sync_restraints(self.restraints)
-            if self.metadynamics is not None:
-                self.metadynamics.sync(eng)
-            eng.sync_gb(self.implicit_solvent)
-            eng.sync_alchemical(self)
+            for t in self._active_side_terms():
+                t.sync(eng, self)
             eng.place_sites(p)  # first launch (no-op without virtual sites)
             for _ in range(4):
                 self._launch(eng, p, box, forces, want_energy, want_forces, count_pairs)
@@ -880,14 +867,9 @@ class Forces:
                 raise RuntimeError("neighbour list kept overflowing; increase `skin` capacity")
             if want_forces:
                 eng.spread_sites(forces)  # last launch
-            if self.restraints is not None and not count_pairs:
-                eng.apply_restraints(self.restraints, p, self._replica_boxes(box, p.shape[0]), forces if want_forces else None, want_energy)
-            if self.metadynamics is not None and not count_pairs:
-                eng.apply_metad(self.metadynamics, p, self._replica_boxes(box, p.shape[0]), forces if want_forces else None, want_energy)
-            if self.implicit_solvent is not None and not count_pairs:
-                eng.apply_gb(self.implicit_solvent, p, self._replica_boxes(box, p.shape[0]), forces if want_forces else None, want_energy)
-            if self.alchemical is not None and not count_pairs:
-                eng.apply_alchemical(self.alchemical, p, self._replica_boxes(box, p.shape[0]), forces if want_forces else None, want_energy)
+            if not count_pairs:
+                for t in self._active_side_terms():
+                    eng.apply_side(t, p, self._replica_boxes(box, p.shape[0]), forces if want_forces else None, want_energy)
             if eng.vsites is not None and p.data_ptr() != pos.data_ptr():
                 pos.detach().copy_(p)  # (a non-contiguous `pos` was evaluated through a copy: the sites go back)
         if target is not None:
@@ -921,11 +903,8 @@ class Forces:
         out = np.empty((R, L.NENERGY), dtype=np.float64)
         with torch.cuda.device(p.device):
             stream = C.c_void_p(torch.cuda.current_stream(p.device).cuda_stream)
-            eng.sync_restraints(self.restraints)
-            if self.metadynamics is not None:
-                self.metadynamics.sync(eng)
-            eng.sync_gb(self.implicit_solvent)
-            eng.sync_alchemical(self)
+            for t in self._active_side_terms():
+                t.sync(eng, self)
             eng.place_sites(p)  # first launch (no-op without virtual sites)
             for _ in range(4):
                 rc = L.check(
@@ -942,18 +921,12 @@ class Forces:
                 raise RuntimeError("neighbour list kept overflowing; increase `skin` capacity")
             if forces is not None:
                 eng.spread_sites(forces)  # last launch
-            if self.restraints is not None:
-                eng.apply_restraints(self.restraints, p, np.ascontiguousarray(boxes, dtype=np.float64), forces, True)
-                self._restraint_energy = eng.rbuf.cpu().numpy()
-            if self.metadynamics is not None:
-                eng.apply_metad(self.metadynamics, p, np.ascontiguousarray(boxes, dtype=np.float64), forces, True)
-                self.metadynamics.report(eng.mbuf.cpu().numpy())
-            if self.implicit_solvent is not None:
-                eng.apply_gb(self.implicit_solvent, p, np.ascontiguousarray(boxes, dtype=np.float64), forces, True)
-                self.implicit_solvent.energy = eng.gbuf.cpu().numpy()
-            if self.alchemical is not None:
-                eng.apply_alchemical(self.alchemical, p, np.ascontiguousarray(boxes, dtype=np.float64), forces, True)
-                self.alchemical.energy = eng.abuf.cpu().numpy()
+            self._side_potential = {}
+            for t in self._active_side_terms():
+                eng.apply_side(t, p, np.ascontiguousarray(boxes, dtype=np.float64), forces, True)
+                row = eng.side_row(t).cpu().numpy()
+                t.store(row)
+                self._side_potential[t.side_name] = t.potential(row)
             if eng.vsites is not None and p.data_ptr() != pos.data_ptr():
                 pos.detach().copy_(p)  # (a non-contiguous `pos` was evaluated through a copy: the sites go back)
         if target is not None:
@@ -971,14 +944,8 @@ class Forces:
         toNumpy=True,
         calculateForces=True,
     ):
-        if self.restraints is not None and _is_batched(pos):
-            raise ValueError("compute() with restraints cannot run under torch.vmap (their targets are per replica of the context)")
-        if self.metadynamics is not None and _is_batched(pos):
-            raise ValueError("compute() with metadynamics cannot run under torch.vmap (its grids are per replica of the context)")
-        if self.implicit_solvent is not None and _is_batched(pos):
-            raise ValueError("compute() with implicit_solvent cannot run under torch.vmap (its Born radii are per replica of the context)")
-        if self.alchemical is not None and _is_batched(pos):
-            raise ValueError("compute() with alchemical= cannot run under torch.vmap (its couplings are per replica of the context)")
+        if _is_batched(pos):
+            self._refuse_side_terms("vmap")
         if self.virtual_sites is not None:
             if _is_batched(pos):
                 raise ValueError("compute() with virtual_sites cannot run under torch.vmap (the sites are written into `pos` in place)")
@@ -1028,18 +995,9 @@ class Forces:
                 cols[:, k] = ehost[:, slot]
         if ext_ene is not None:
             cols[:, -1] = torch.as_tensor(ext_ene).detach().to("cpu", torch.float64).reshape(nsystems).numpy()
-        if self.restraints is not None:  # (reported, and in the total, only when the keyword was given)
-            names.append("restraints")
-            cols = np.concatenate([cols, self._restraint_energy.sum(axis=1, keepdims=True)], axis=1)
-        if self.metadynamics is not None:
-            names.append("metadynamics")
-            cols = np.concatenate([cols, self.metadynamics.energy.reshape(-1, 1)], axis=1)
-        if self.implicit_solvent is not None:
-            names.append("implicit_solvent")
-            cols = np.concatenate([cols, self.implicit_solvent.energy.sum(axis=1, keepdims=True)], axis=1)
-        if self.alchemical is not None:  # cross + intra
-            names.append("alchemical")
-            cols = np.concatenate([cols, self.alchemical.energy[:, :3].sum(axis=1, keepdims=True)], axis=1)
+        for name, e in self._side_potential.items():  # (reported, and in the total, only when the keyword was given)
+            names.append(name)
+            cols = np.concatenate([cols, e.reshape(-1, 1)], axis=1)
 
         if not returnDetails:
             tot = cols.sum(axis=1)
@@ -1085,17 +1043,11 @@ class Forces:
     # used by Integrator: no host synchronisation unless energies are requested
     def _compute_async(self, pos, box, forces, want_energy):
         ebuf = self._evaluate(pos, box, forces, want_energy, True)
-        # (the restraint energy travels with the external one: a per-replica term outside the library's eight)
-        extra = self._engine(pos.detach()).rbuf.sum(dim=1) if (want_energy and self.restraints is not None) else None
-        if want_energy and self.metadynamics is not None:
-            vb = self._engine(pos.detach()).mbuf[:, 0]
-            extra = vb if extra is None else extra + vb
-        if want_energy and self.implicit_solvent is not None:
-            gb = self._engine(pos.detach()).gbuf.sum(dim=1)
-            extra = gb if extra is None else extra + gb
-        if want_energy and self.alchemical is not None:
-            ab = self._engine(pos.detach()).abuf[:, :3].sum(dim=1)
-            extra = ab if extra is None else extra + ab
+        # (the side terms' energies travel with the external one: per-replica terms outside the library's eight)
+        extra = None
+        for t in self._active_side_terms() if want_energy else ():
+            e = t.potential(self._engine(pos.detach()).side_row(t))
+            extra = e if extra is None else extra + e
         if self.external:
             ext_ene, ext_force = self.external.calculate(pos, box)
             forces += ext_force
@@ -1118,11 +1070,8 @@ class Forces:
         eng = self._engine(pos)
         if getattr(eng, "_constraints", None) is not constraints:
             eng.set_constraints(constraints)
-        eng.sync_restraints(self.restraints)
-        if self.metadynamics is not None:
-            self.metadynamics.sync(eng)
-        eng.sync_gb(self.implicit_solvent)
-        eng.sync_alchemical(self)
+        for t in self._active_side_terms():
+            t.sync(eng, self)
         R = pos.shape[0]
         # the descriptor and the per-replica box array are kept between calls (a 20-step call is short enough for
         # the Python in front of its first launch to show)
@@ -1189,10 +1138,7 @@ class Forces:
 
         if _is_batched(pos) or _is_batched(box):
             raise ValueError("the pressure cannot be evaluated under torch.vmap (its molecule table and lists are per replica of the context)")
-        if self.implicit_solvent is not None:
-            raise ValueError("the pressure and the virial are not available with implicit_solvent (open boundaries: there is no volume)")
-        if self.alchemical is not None:
-            raise ValueError("the pressure and the virial are not available with alchemical= (the virial lacks the solute's term)")
+        self._refuse_side_terms("pressure")
         if getattr(self, "_nactive", None):
             raise ValueError("the pressure is not available for a brick of the domain decomposition (its context holds passive atoms)")
         L.require_device_tensor(pos, "pos")

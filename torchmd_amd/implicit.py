@@ -32,10 +32,22 @@ def elements_from_masses(masses):
     return [_ELEMENT_BY_MASS.get(int(round(float(x)))) for x in m]
 
 
-class GeneralizedBorn:
+class GeneralizedBorn(L.SideTerm):
     """Per-atom intrinsic radii (A) and descreening scales, the two dielectric constants, the surface tension (kcal/mol/A^2;
     0 switches the surface-area term off) and the probe radius (A).  ValueError: a radius <= 0.09 or not finite, a negative
     scale, a dielectric constant <= 0, arrays of different lengths."""
+
+    side_name, side_width = "implicit_solvent", 2  # (GB, SA)
+    side_apply, side_energy = "tmdhip_gb_apply", "tmdhip_gb_energy"
+    refusals = {
+        "vmap": "compute() with implicit_solvent cannot run under torch.vmap (its Born radii are per replica of the context)",
+        "batch": "implicit_solvent does not support atom groups (batch=): its Born radii are per replica",
+        "barostat": "implicit_solvent cannot run under barostat=: open boundaries have no volume",
+        "update_atoms": "update_atoms is not available with implicit_solvent",
+        "pressure": "the pressure and the virial are not available with implicit_solvent (open boundaries: there is no volume)",
+        "domain": "implicit_solvent cannot be domain-decomposed (the generalized-Born sums run over all pairs of atoms, "
+                  "and a brick holds passive atoms)",
+    }
 
     def __init__(self, radii, scale, solute_dielectric=1.0, solvent_dielectric=78.5, surface_tension=0.0054, probe_radius=1.4):
         self.radii = np.ascontiguousarray(np.asarray(radii, dtype=np.float64).reshape(-1))
@@ -94,3 +106,9 @@ class GeneralizedBorn:
         d.solute_dielectric, d.solvent_dielectric = self.solute_dielectric, self.solvent_dielectric
         d.surface_tension, d.probe_radius = self.surface_tension, self.probe_radius
         L.check(lib.tmdhip_set_gb(ctx, C.byref(d)), "tmdhip_set_gb")
+
+    def sync(self, eng, owner=None):
+        """Hand the model to the context of `eng` on first sight (tmdhip_set_gb)."""
+        if eng.side_seen.get(self.side_name) is not self:
+            self.upload(eng.lib, eng.ctx)
+            eng.side_seen[self.side_name] = self

@@ -26,6 +26,7 @@ import numpy as np
 import torch
 
 from . import _lib as L
+from .forces import active_side_terms
 
 TIMEFACTOR = 48.88821
 BOLTZMAN = 0.001987191
@@ -172,7 +173,7 @@ class Integrator:
         self.barostat = barostat  # barostat.MonteCarloBarostat or crescale.CRescaleBarostat
         # (a virial-driven barostat moves every time, rescales velocities too and holds one target per replica)
         self._virial_barostat = bool(getattr(barostat, "virial_driven", False))
-        self._check_restraints()
+        self._check_side_terms()
         self.replays = 0  # batches that were rewound and repeated (list validity failure / step-block time-out)
         self.thermostat = thermostat  # thermostat.VelocityRescale
         if thermostat is not None:
@@ -184,57 +185,20 @@ class Integrator:
         self.exchange = exchange  # exchange.ReplicaExchange
         if exchange is not None:
             self._init_exchange(exchange)
-        self._check_metadynamics()
-        self._check_implicit_solvent()
-        self._check_alchemical()
+        self._check_side_terms()
 
-    def _check_alchemical(self):
-        """What is refused with an alchemical solute (ValueError): atom groups and any barostat (the virial lacks the solute's
-        term; NPT is a follow-up)."""
-        if getattr(self.forces, "alchemical", None) is None:
-            return
-        if self.batch is not None:
-            raise ValueError("alchemical= does not support atom groups (batch=): its couplings are per replica")
-        if self.barostat is not None:
-            raise ValueError("alchemical= cannot run under barostat=: the virial lacks the solute's term")
-
-    def _check_implicit_solvent(self):
-        """What is refused with a generalized-Born implicit solvent (ValueError): atom groups and any barostat (the model is
-        for open boundaries: there is no volume to change)."""
-        if getattr(self.forces, "implicit_solvent", None) is None:
-            return
-        if self.batch is not None:
-            raise ValueError("implicit_solvent does not support atom groups (batch=): its Born radii are per replica")
-        if self.barostat is not None:
-            raise ValueError("implicit_solvent cannot run under barostat=: open boundaries have no volume")
-
-    def _check_metadynamics(self):
-        """What is refused with a metadynamics bias (ValueError): atom groups, a barostat (the distance grid does not scale
-        with the box) and replica exchange (the bias would have to travel with the rung)."""
+    def _check_side_terms(self):
+        """What is refused with a side term of the forces (ValueError, the term's own message: `SideTerm.refusals`): atom groups,
+        whose replicas share one row of positions; a barostat (distance restraints alone are allowed: they scale with the box);
+        for metadynamics, replica exchange and a bias made for another number of replicas.  Looked at when the integrator is
+        made and again at every `step`: entries may be added to a `Restraints` at any time."""
+        for t in active_side_terms(self.forces):
+            for what, on in (("batch", self.batch), ("barostat", self.barostat), ("exchange", getattr(self, "exchange", None))):
+                if on is not None and t.refusal(what):
+                    raise ValueError(t.refusal(what))
         md = getattr(self.forces, "metadynamics", None)
-        if md is None:
-            return
-        if self.batch is not None:
-            raise ValueError("metadynamics does not support atom groups (batch=): its grids are per replica")
-        if self.barostat is not None:
-            raise ValueError("metadynamics cannot run under barostat=")
-        if self.exchange is not None:
-            raise ValueError("metadynamics cannot run under exchange=: the bias would have to travel with the rung")
-        if md.nreplicas != self.systems.pos.shape[0]:
+        if md is not None and md.nreplicas != self.systems.pos.shape[0]:
             raise ValueError(f"the metadynamics bias was made for {md.nreplicas} replicas, the systems have {self.systems.pos.shape[0]}")
-
-    def _check_restraints(self):
-        """What is refused with restraints (ValueError): atom groups, whose replicas share one row of positions, and absolute
-        references under a barostat, which do not scale with the box (distance restraints are allowed).  Looked at when the
-        integrator is made and again at every `step`: entries may be added to a `Restraints` at any time."""
-        rs = getattr(self.forces, "restraints", None)
-        if rs is None:
-            return
-        if self.batch is not None:
-            raise ValueError("restraints do not support atom groups (batch=): their targets are per replica")
-        if self.barostat is not None and rs.npos:
-            raise ValueError("position restraints cannot run under barostat=: absolute references do not scale with the box "
-                             "(distance restraints can)")
 
     def _init_thermostat(self, th):
         """What is refused (ValueError): a second thermostat (Langevin), atom groups, a ladder of the wrong length, a ladder
@@ -321,8 +285,7 @@ class Integrator:
         lib = L.load()
         s = self.systems
         self._check_layout()
-        self._check_restraints()
-        self._check_metadynamics()
+        self._check_side_terms()
         dev = s.pos.device
         code = L.dtype_code(s.pos.dtype)
         R, N = s.pos.shape[0], s.pos.shape[1]
@@ -519,29 +482,11 @@ class Integrator:
                 raise RuntimeError(_REPLAY_FAILED + L.last_error())
             cols = self.forces.energy_columns()
             tot = obs[:, cols].sum(axis=1) if cols else np.zeros(R)
-            if self.forces.restraints is not None:  # the run's finishing launch has summed them: one small copy
-                er = np.empty((R, 2), dtype=np.float64)
-                L.check(lib.tmdhip_restraint_energy(eng.ctx, er.ctypes.data_as(C.POINTER(C.c_double)), _stream(dev)),
-                        "tmdhip_restraint_energy")
-                self.forces._restraint_energy = er
-                tot = tot + er.sum(axis=1)
-            if getattr(self.forces, "metadynamics", None) is not None:  # (V, CVs) of the finishing launch: one small copy
-                em = np.empty((R, 3), dtype=np.float64)
-                L.check(lib.tmdhip_metad_energy(eng.ctx, em.ctypes.data_as(C.POINTER(C.c_double)), _stream(dev)), "tmdhip_metad_energy")
-                self.forces.metadynamics.report(em)
-                tot = tot + em[:, 0]
-            gb = getattr(self.forces, "implicit_solvent", None)
-            if gb is not None:  # (GB, SA) of the finishing launch: one small copy
-                eg = np.empty((R, 2), dtype=np.float64)
-                L.check(lib.tmdhip_gb_energy(eng.ctx, eg.ctypes.data_as(C.POINTER(C.c_double)), _stream(dev)), "tmdhip_gb_energy")
-                gb.energy = eg
-                tot = tot + eg.sum(axis=1)
-            al = getattr(self.forces, "alchemical", None)
-            if al is not None:  # the five numbers of the finishing launch: one small copy
-                ea = np.empty((R, 5), dtype=np.float64)
-                L.check(lib.tmdhip_alchemical_energy(eng.ctx, ea.ctypes.data_as(C.POINTER(C.c_double)), _stream(dev)), "tmdhip_alchemical_energy")
-                al.energy = ea
-                tot = tot + ea[:, :3].sum(axis=1)
+            for t in active_side_terms(self.forces):  # the run's finishing launch has summed them: one small copy each
+                row = np.empty((R, t.side_width), dtype=np.float64)
+                L.check(getattr(lib, t.side_energy)(eng.ctx, row.ctypes.data_as(C.POINTER(C.c_double)), _stream(dev)), t.side_energy)
+                t.store(row)
+                tot = tot + t.potential(row)
             pot = [float(v) for v in tot]
             Ekin = obs[:, L.NENERGY].copy()
             Ekin = Ekin.astype(np.dtype("float32") if s.pos.dtype == torch.float32 else np.float64)
@@ -581,15 +526,10 @@ class Integrator:
                     self.replays += 1
                     return self._step_body(lib, s, dev, code, R, N, fast, fused, niter, replay=True)
                 raise RuntimeError((_REPLAY_FAILED + why) if (fused and replay) else (_LIST_INVALID + ": " + why))
-            if ebuf is not None and getattr(self.forces, "restraints", None) is not None:
-                # (the step-by-step loop: the restraint energies of its last evaluation, as the fused path leaves them)
-                self.forces._restraint_energy = eng.rbuf.cpu().numpy()
-            if ebuf is not None and getattr(self.forces, "metadynamics", None) is not None:
-                self.forces.metadynamics.report(eng.mbuf.cpu().numpy())
-            if ebuf is not None and getattr(self.forces, "implicit_solvent", None) is not None:
-                self.forces.implicit_solvent.energy = eng.gbuf.cpu().numpy()
-            if ebuf is not None and getattr(self.forces, "alchemical", None) is not None:
-                self.forces.alchemical.energy = eng.abuf.cpu().numpy()
+            if ebuf is not None:
+                # (the step-by-step loop: the side terms' energies of its last evaluation, as the fused path leaves them)
+                for t in active_side_terms(self.forces):
+                    t.store(eng.side_row(t).cpu().numpy())
         else:
             Ekin = ke.flatten().cpu().numpy()
         Ekin = Ekin.astype(np.dtype("float32") if s.pos.dtype == torch.float32 else np.float64)

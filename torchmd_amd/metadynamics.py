@@ -132,7 +132,19 @@ def locate(lo, h, nodes, periodic, s):
     return int(fl), int(fl) + 1, x - fl, live
 
 
-class Metadynamics:
+class Metadynamics(L.SideTerm):
+    side_name, side_width = "metadynamics", 3  # (V, s_0, s_1)
+    side_potential = slice(0, 1)
+    side_apply, side_energy = "tmdhip_metad_apply", "tmdhip_metad_energy"
+    refusals = {
+        "vmap": "compute() with metadynamics cannot run under torch.vmap (its grids are per replica of the context)",
+        "batch": "metadynamics does not support atom groups (batch=): its grids are per replica",
+        "barostat": "metadynamics cannot run under barostat=",
+        "exchange": "metadynamics cannot run under exchange=: the bias would have to travel with the rung",
+        "domain": "metadynamics cannot be domain-decomposed (a CV's atoms would straddle bricks, and atom indices change "
+                  "at every migration)",
+    }
+
     def __init__(self, cvs, sigma, height, frequency, temperature, bias_factor=None, grid_min=None, grid_max=None, grid_bins=None,
                  nreplicas=1, walkers="independent"):
         if isinstance(cvs, tuple) and len(cvs) == 2 and isinstance(cvs[0], str):
@@ -426,7 +438,7 @@ class Metadynamics:
             raise ValueError(f"Metadynamics.set_grid: the grid is {self._grid.shape}, got {grid.shape}")
         self._grid, self._dev_dirty, self._host_dirty = grid.copy(), False, True
 
-    def sync(self, eng):
+    def sync(self, eng, owner=None):
         """Make the context of `eng` hold this bias (tmdhip_set_metadynamics on first sight, the grid when the host's is newer)."""
         if self._eng is not eng:
             self._pull()
@@ -479,6 +491,15 @@ class Metadynamics:
         """Take (V, s_0, s_1) [R,3] of an evaluation: `energy` [R] and `cv` [R, ncv]."""
         out = np.asarray(out, dtype=np.float64).reshape(self.nreplicas, 3)
         self.energy, self.cv = out[:, 0].copy(), out[:, 1 : 1 + self.ncv].copy()
+
+    store = report  # (the side-term protocol's name for it)
+
+    def monitor_columns(self):
+        return ("bias",) + tuple(f"cv{c}" for c in range(self.ncv))
+
+    def monitor_row(self, k):
+        """The bias energy inside `epot` and the CVs of replica k."""
+        return {"bias": float(self.energy[k]), **{f"cv{c}": float(self.cv[k, c]) for c in range(self.ncv)}}
 
     def hills(self):
         """The hills log [n, R, ncv + 1]: (s0..., w) of every deposition."""

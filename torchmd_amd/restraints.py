@@ -50,7 +50,18 @@ def build_rows(pos_atoms, pairs):
     return np.asarray(atoms, dtype=np.int32), np.asarray(off, dtype=np.int32), np.asarray(ent, dtype=np.int32).reshape(-1, 4)
 
 
-class Restraints:
+class Restraints(L.SideTerm):
+    side_name, side_width = "restraints", 2  # (position, distance)
+    side_apply, side_energy = "tmdhip_restraint_apply", "tmdhip_restraint_energy"
+    refusals = {
+        "vmap": "compute() with restraints cannot run under torch.vmap (their targets are per replica of the context)",
+        "batch": "restraints do not support atom groups (batch=): their targets are per replica",
+        "barostat": "position restraints cannot run under barostat=: absolute references do not scale with the box "
+                    "(distance restraints can)",
+        "domain": "restraints cannot be domain-decomposed (a pair's atoms would straddle bricks, and atom indices change "
+                  "at every migration)",
+    }
+
     def __init__(self, nreplicas=1):
         if int(nreplicas) != nreplicas or nreplicas < 1:
             raise ValueError("Restraints: nreplicas must be a positive whole number")
@@ -216,6 +227,19 @@ class Restraints:
         d, keep = self.descriptor()
         L.check(lib.tmdhip_set_restraints(ctx, C.byref(d)), "tmdhip_set_restraints")
         del keep
+
+    def refusal(self, what):
+        """(Distance restraints scale with the box: only absolute references are refused under a barostat.)"""
+        return None if (what == "barostat" and not self.npos) else self.refusals.get(what)
+
+    def sync(self, eng, owner=None):
+        """Upload the tables when the copy of `eng`'s context is older (tmdhip_set_restraints)."""
+        if eng.side_seen.get(self.side_name) == (id(self), self.version):
+            return
+        if self.nreplicas != eng.nreplicas:
+            raise ValueError(f"restraints were made for {self.nreplicas} replicas, the positions have {eng.nreplicas}")
+        self.upload(eng.lib, eng.ctx)
+        eng.side_seen[self.side_name] = (id(self), self.version)
 
     @classmethod
     def from_npz(cls, path, nreplicas):

@@ -44,7 +44,7 @@ import yaml
 
 from . import io as tio
 from .forcefields import ForceField
-from .forces import Forces
+from .forces import Forces, active_side_terms
 from .integrator import Integrator, maxwell_boltzmann
 from .minimizers import minimize_bfgs, minimize_fire
 from .utils import LogWriter
@@ -320,9 +320,6 @@ def setup(args):
     return mol, system, forces
 
 
-ALCHEMICAL_COLUMNS = ("alchemical", "dudl_vdw", "dudl_elec")  # of every monitor file with an `alchemical:` mapping
-
-
 def tip4p_sites(ff, mol):
     """`virtual_sites: tip4p` — the M sites of a system of four-site waters (atom order O,H1,H2,M), with the geometry the
     force-field file states: `virtual_sites: {tip4p: {r_om: ..., r_oh: ..., theta: ...}}` (Angstrom, degrees)."""
@@ -409,16 +406,15 @@ def dynamics(args, mol, system, forces):
     columns = ("iter", "ns", "epot", "ekin", "etot", "T") + (("volume",) if barostat is not None else ())
     columns += ("pressure",) if args.pressure else ()
     columns += ("rung",) if exchange is not None else ()
-    restrained = getattr(forces, "restraints", None) is not None
-    columns += ("restraints",) if restrained else ()
-    solvent = getattr(forces, "implicit_solvent", None)
-    columns += ("implicit_solvent",) if solvent is not None else ()
+    # each side term adds its columns: what of its energy `epot` contains, as of the last evaluation (the bias and its CVs last,
+    # where the monitor files have always had them)
+    side_terms = sorted(active_side_terms(forces), key=lambda t: t.side_name == "metadynamics")
+    for term in side_terms:
+        columns += term.monitor_columns()
     alch = getattr(forces, "alchemical", None)
-    columns += ALCHEMICAL_COLUMNS if alch is not None else ()
     states = np.asarray(args.alchemical["states"], dtype=np.float64).reshape(-1, 2) if (alch is not None and args.alchemical.get("states")) else None
     foreign = []  # [frames][R, K] cross energies at `states`
     metad = getattr(forces, "metadynamics", None)
-    columns += ("bias",) + tuple(f"cv{c}" for c in range(metad.ncv)) if metad is not None else ()
     logs = [LogWriter(args.log_dir, columns, name=f"monitor_{k}.csv") for k in range(args.replicas)]
     boxes = []  # [frames][R,3] box edges, constant-pressure runs only
     if args.minimize is not None:
@@ -453,17 +449,8 @@ def dynamics(args, mol, system, forces):
                 row["pressure"] = float(pressure[k])
             if exchange is not None:
                 row["rung"] = int(exchange.rungs[k]) if exchange.rungs is not None else k
-            if restrained:  # the restraint energy inside `epot`, as of the last evaluation
-                row["restraints"] = float(forces._restraint_energy[k].sum())
-            if solvent is not None:  # the GB + SA energy inside `epot`, as of the last evaluation
-                row["implicit_solvent"] = float(solvent.energy[k].sum())
-            if alch is not None:  # the cross + intra energy inside `epot` and dU/dlambda, as of the last evaluation
-                row["alchemical"] = float(alch.energy[k, :3].sum())
-                row["dudl_vdw"], row["dudl_elec"] = float(alch.energy[k, 3]), float(alch.energy[k, 4])
-            if metad is not None:  # the bias energy inside `epot` and the CVs, as of the last evaluation
-                row["bias"] = float(metad.energy[k])
-                for c in range(metad.ncv):
-                    row[f"cv{c}"] = float(metad.cv[k, c])
+            for term in side_terms:
+                row.update(term.monitor_row(k))
             logs[k].write_row(row)
     wall = time.time() - t0
     if metad is not None:
