@@ -560,15 +560,13 @@ def test_trajectory_fp64_pme():
 
 def test_forced_replay_repeats_the_batch(monkeypatch):
     """Rewind and replay need nothing of their own: everything is enqueued again from the snapshot."""
-    from torchmd_amd import _lib as L
-
     monkeypatch.setenv("TMDHIP_VSKIN", "0")
     mol, pos, box, par, vel0 = _tip3p("f64", 1)
     rs = _tip3p_restraints(pos, box, 1)
     case = (mol, pos, box, par, vel0, 1, WATER_TERMS, dict(cutoff=9.0, rfa=True))
     tp, tv = _by_hand(case, "f64", rs, CUTS, True)
     p, v, frc, out, f, s, integ = _under_test(case, "f64", rs, CUTS, True)
-    again = integ._step_body(L.load(), s, s.pos.device, L.dtype_code(s.pos.dtype), 1, s.pos.shape[1], True, True, CUTS[-1], replay=True)
+    again = integ._step_body(CUTS[-1], replay=True)
     p2, v2 = s.pos.cpu().double().numpy(), s.vel.cpu().double().numpy()
     bar_p, bar_v = 64 * EPS64 * 10 * np.abs(tp).max(), 64 * EPS64 * 10 * np.abs(tv).max()
     assert np.abs(p2 - tp).max() <= bar_p and np.abs(v2 - tv).max() <= bar_v

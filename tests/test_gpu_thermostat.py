@@ -397,6 +397,46 @@ def test_composes_with_the_barostat():
     assert np.array_equal(ek, th.last[:, 2].cpu().numpy().astype(np.float32))
 
 
+def test_with_the_barostat_equals_the_composition_by_hand(monkeypatch):
+    """Thermostat every 10 and Monte Carlo barostat every 25 steps, calls of 20 and 30: bit for bit plain `step` over the
+    segments 10, 10 | 5, 5, 10, 10 with the application and then the attempt by hand where their multiples fall."""
+    from torchmd_amd.barostat import MonteCarloBarostat
+
+    monkeypatch.setenv("TMDHIP_LPA", "16")
+    th = _thermostat(300.0, tau=0.1, frequency=10, seed=24)
+    bar = MonteCarloBarostat(1.0, 300.0, frequency=25, seed=24)
+    mol, par, s, f, integ = _box("f32", thermostat=th, barostat=bar)
+    returned = [integ.step(n) for n in (20, 30)]
+
+    th2 = _thermostat(300.0, tau=0.1, frequency=10, seed=24)
+    bar2 = MonteCarloBarostat(1.0, 300.0, frequency=25, seed=24)
+    _, _, s2, f2, plain = _box("f32")
+    pots, recs, done = {}, [], 0
+    for n in (10, 10, 5, 5, 10, 10):
+        _, pot, _ = plain.step(n)
+        done += n
+        if done % 10 == 0:
+            th2.apply(s2, plain.masses, plain.dt, 3 * mol.numAtoms)
+        if done % 25 == 0:
+            rec = bar2.attempt(s2, f2, pot)
+            recs.append(rec)
+            pot = [float(un if ok else u) for u, un, ok in zip(rec["U"], rec["U_new"], rec["accepted"])]
+        pots[done] = pot
+    assert plain._nstep == integ._nstep == 50 and th.applications == th2.applications == 5 and len(recs) == 2
+    assert torch.equal(s.pos, s2.pos) and torch.equal(s.vel, s2.vel) and torch.equal(s.box, s2.box)
+    assert returned[0][1] == pots[20] and returned[1][1] == pots[50]
+    for ek, _, T in returned:
+        assert ek.dtype == np.float32 and np.array_equal(T, integ._temperature(ek))
+    assert np.array_equal(returned[1][0], th.last[:, 2].cpu().numpy().astype(np.float32))
+    assert torch.equal(th.last, th2.last) and np.array_equal(th.heat(), th2.heat())
+    assert bar.last.keys() == bar2.last.keys() == recs[-1].keys()
+    for k in bar.last:
+        assert np.array_equal(bar.last[k], bar2.last[k]), k
+    assert np.array_equal(bar.max_dv, bar2.max_dv) and np.array_equal(bar.accepted, bar2.accepted)
+    print(f"thermostat + barostat by hand: accepted {bar.accepted[0]} of {bar.attempts[0]}, heat {th.heat()[0]:.6f}, "
+          f"E_pot {returned[1][1][0]:.4f}, E_kin {returned[1][0][0]:.4f}")
+
+
 _CHILD = r"""
 import json, os, sys
 sys.path.insert(0, os.path.join(ROOT, "tests"))

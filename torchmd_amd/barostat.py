@@ -32,6 +32,7 @@ import numpy as np
 import torch
 
 from . import _lib as L
+from .controls import Control, box_edges, forget_continuation, positive_edges, require_layout, scaled_box
 from .integrator import BOLTZMAN
 from .wrapper import calculate_molecule_groups
 
@@ -56,10 +57,7 @@ def scale_groups(pos, scale, offsets, members, has_big, saved=None):
     """`tmdhip_scale_groups`: translate every group of `pos` [R,N,3] (device, in place) by (scale[r] - 1) * its centre;
     `scale` is a host array [R,3]; `offsets` / `members`: the groups' CSR as int32 device tensors; `saved` (like `pos`,
     or None) receives the positions as they were."""
-    L.require_device_tensor(pos, "pos")
-    if pos.dim() != 3 or pos.shape[2] != 3 or not pos.is_contiguous():
-        raise RuntimeError("pos must be a contiguous (nreplicas, natoms, 3) tensor")
-    R, N = pos.shape[0], pos.shape[1]
+    R, N = require_layout(pos, "pos")
     sc = np.ascontiguousarray(np.asarray(scale, dtype=np.float64).reshape(R, 3))
     if saved is not None and (saved.shape != pos.shape or saved.dtype != pos.dtype or saved.device != pos.device
                               or not saved.is_contiguous()):
@@ -81,25 +79,22 @@ def scale_groups(pos, scale, offsets, members, has_big, saved=None):
         )
 
 
-class MonteCarloBarostat:
+class MonteCarloBarostat(Control):
     """Isotropic Monte Carlo pressure coupling; see the module docstring.  `attempt(system, forces, epot)` is what the
     integrator calls every `frequency` steps; it returns (and keeps as `.last`) a record with, per replica, `V`, `V_new`,
     `U`, `U_new`, `u_volume`, `u_accept`, `w` and `accepted`.  `attempts` / `accepted` count per replica; `max_dv` holds
     the current dVmax per replica.  `rng` is the list of per-replica generators (anything with `.random()`)."""
+
+    rank, ladder_ok = 1, False
 
     def __init__(self, pressure_bar, temperature, frequency=25, seed=None):
         if not np.isfinite(pressure_bar):
             raise ValueError("pressure_bar must be finite")
         if not temperature or not temperature > 0:
             raise ValueError("the barostat needs a positive temperature (that of the thermostat)")
-        if int(frequency) != frequency or frequency < 1:
-            raise ValueError("frequency must be a positive number of steps")
+        super().__init__(frequency, seed)
         self.pressure_bar = float(pressure_bar)
         self.temperature = float(temperature)
-        self.frequency = int(frequency)
-        # seeded from torch's global generator so torch.manual_seed() reproduces runs (as Integrator._seed)
-        self.seed = int(seed) if seed is not None else int(torch.randint(0, 2**62, (1,), dtype=torch.int64).item())
-        self.rng = None
         self.max_dv = None
         self.attempts = self.accepted = None
         self.last = None
@@ -117,19 +112,21 @@ class MonteCarloBarostat:
                              "duck-typed force objects are not supported")
         if temperature is not None and not temperature:
             raise ValueError("the barostat needs a thermostat: set T (and gamma) on the integrator")
-        self._check_edges(torch.diagonal(system.box.detach(), dim1=-2, dim2=-1).to("cpu", torch.float64).numpy())
+        positive_edges(box_edges(system.box))
 
-    @staticmethod
-    def _check_edges(edges):
-        if not (np.asarray(edges) > 0).all():
-            raise ValueError("the barostat needs a periodic box: every box edge must be positive")
+    def attach(self, integrator):
+        it, th = integrator, integrator.thermostat
+        self.check(it.systems, it.forces, temperature=(th.temperature if th is not None else it.T) or 0)
+
+    def after_segment(self, integrator, out):
+        """The potential energy of the replicas whose move was accepted changes; velocities are never touched."""
+        rec = self.attempt(integrator.systems, integrator.forces, out[1])
+        pot = [float(un if ok else u) for u, un, ok in zip(rec["U"], rec["U_new"], rec["accepted"])]
+        return (out[0], pot, out[2])
 
     def _setup(self, system, forces):
         R, N = system.pos.shape[0], system.pos.shape[1]
-        if self.rng is None:
-            self.rng = [np.random.Generator(np.random.Philox(key=np.array([self.seed, r], dtype=np.uint64))) for r in range(R)]
-        if len(self.rng) != R:
-            raise RuntimeError(f"the barostat holds {len(self.rng)} random streams for {R} replicas")
+        self._streams(R, "barostat")
         if self.attempts is None:
             self.attempts = np.zeros(R, dtype=np.int64)
             self.accepted = np.zeros(R, dtype=np.int64)
@@ -163,9 +160,8 @@ class MonteCarloBarostat:
         _, off, mem, has_big, ngroups = self._groups
         kT = BOLTZMAN * self.temperature
         box0 = system.box.detach().clone()
-        edges = torch.diagonal(box0, dim1=-2, dim2=-1).to("cpu", torch.float64).numpy().reshape(R, 3)
-        self._check_edges(edges)
-        V = edges[:, 0] * edges[:, 1] * edges[:, 2]
+        edges = positive_edges(box_edges(box0))
+        V =edges[:, 0] * edges[:, 1] * edges[:, 2]
         if self.max_dv is None:
             self.max_dv = START_DV_FRACTION * V
         U = np.asarray(epot, dtype=np.float64).reshape(R)
@@ -174,12 +170,7 @@ class MonteCarloBarostat:
         s = ((V + dV) / V) ** (1.0 / 3.0)
         if not (np.isfinite(s).all() and (s > 0).all()):
             raise RuntimeError("barostat: the trial volume is not positive")
-        # the box the engine will see: the scaled edges rounded to the box tensor's precision; V' and the factors
-        # the molecules' centres are scaled by are taken from those, so box and positions stay consistent in fp32
-        trial = box0.clone()
-        torch.diagonal(trial, dim1=-2, dim2=-1).copy_(torch.as_tensor(s[:, None] * edges).to(trial))
-        new_edges = torch.diagonal(trial, dim1=-2, dim2=-1).to("cpu", torch.float64).numpy().reshape(R, 3)
-        V_new = new_edges[:, 0] * new_edges[:, 1] * new_edges[:, 2]
+        trial, new_edges, V_new = scaled_box(box0, edges, s)
         scale = np.where((dV == 0.0)[:, None], 1.0, new_edges / edges)
 
         scale_groups(system.pos, scale, off, mem, has_big, saved=self._saved)
@@ -200,9 +191,7 @@ class MonteCarloBarostat:
             for r in np.flatnonzero(~ok):
                 final[r].copy_(box0[r])
             system.box.copy_(final)
-        # the positions were written behind torch's back and the box is another one: the next tmdhip_md_run must not be
-        # told that it continues the previous one
-        forces._engine(system.pos)._md_key = None
+        forget_continuation(forces, system.pos)
 
         self.attempts += 1
         self.accepted += ok

@@ -38,6 +38,7 @@ import torch
 
 from . import _lib as L
 from .barostat import BAR_TO_KCAL_MOL_A3
+from .controls import Control, box_edges, forget_continuation, positive_edges, require_layout, scaled_box
 from .integrator import BOLTZMAN, PICOSEC2TIMEU
 
 _KEYS = ("V", "V_new", "P_int", "xi", "mu", "U", "U_new", "K_before", "K_after")
@@ -57,15 +58,10 @@ def rescale_molecules(pos, vel, masses, scale, offsets, members, has_big, record
     multiplied by `scale` (host array [R,3]); `masses`: device tensor [N] of the dtype of `pos`; `offsets` / `members`: the
     molecules' CSR as int32 device tensors; `record` (device float64 [R,2]) receives (K_before, K_after); `partials`: scratch
     sized by `tmdhip_rescale_molecules_workspace`."""
-    for name, t in (("pos", pos), ("vel", vel), ("masses", masses)):
-        L.require_device_tensor(t, name)
-    if pos.dim() != 3 or pos.shape[2] != 3 or not pos.is_contiguous():
-        raise RuntimeError("pos must be a contiguous (nreplicas, natoms, 3) tensor")
+    L.require_device_tensor(vel, "vel")
+    R, N = require_layout(pos, "pos", masses)
     if vel.shape != pos.shape or vel.dtype != pos.dtype or vel.device != pos.device or not vel.is_contiguous():
         raise RuntimeError("vel must be a contiguous tensor with the shape, dtype and device of pos")
-    R, N = pos.shape[0], pos.shape[1]
-    if masses.numel() != N or masses.dtype != pos.dtype or masses.device != pos.device or not masses.is_contiguous():
-        raise RuntimeError("masses must be a contiguous tensor of natoms entries with the dtype and device of pos")
     for name, t in (("offsets", offsets), ("members", members)):
         if t.dtype != torch.int32 or t.device != pos.device or not t.is_contiguous():
             raise RuntimeError(f"{name} must be a contiguous int32 tensor on the device of pos")
@@ -96,14 +92,15 @@ def _per_replica(value, name, positive):
     return a, np.ndim(value) > 0
 
 
-class CRescaleBarostat:
+class CRescaleBarostat(Control):
     """Stochastic cell rescaling; see the module docstring.  `apply(system, forces, masses, dt, epot, ekin)` is what the
     integrator calls every `frequency` steps; it returns (and keeps as `.last`) a record with, per replica, `V`, `V_new`,
     `P_int` (kcal/mol/A^3), `xi`, `mu`, `U`, `U_new`, `K_before` and `K_after` (the kinetic energy of the atoms around the
     move).  `applications` counts them; `work()` is the energy bookkeeping; `rng` is the list of per-replica generators
     (anything with `.standard_normal()`)."""
 
-    virial_driven = True  # (what the integrator dispatches on: `apply` instead of the Monte Carlo barostat's `attempt`)
+    rank = 1
+    virial_driven = True  # (moves every time, rescales velocities too and holds one target per replica; nothing dispatches on it)
 
     def __init__(self, pressure_bar, temperature, tau=1.0, compressibility=4.5e-5, frequency=10, stochastic=True, seed=None):
         self.pressures_bar, p_seq = _per_replica(pressure_bar, "pressure_bar", positive=False)
@@ -113,19 +110,13 @@ class CRescaleBarostat:
                            "compressibility": (self.compressibilities, c_seq)}
         if not np.isfinite(tau) or not tau > 0:
             raise ValueError("tau must be a positive time in ps")
-        if int(frequency) != frequency or frequency < 1:
-            raise ValueError("frequency must be a positive number of steps")
+        super().__init__(frequency, seed)
         self.tau = float(tau)
-        self.frequency = int(frequency)
         self.stochastic = bool(stochastic)
-        # seeded from torch's global generator so torch.manual_seed() reproduces runs (as Integrator._seed)
-        self.seed = int(seed) if seed is not None else int(torch.randint(0, 2**62, (1,), dtype=torch.int64).item())
-        self.rng = None
         self.last = None
         self.applications = 0
         self._work = None
         self._molecules = None
-        self._record = self._partials = None
 
     # ------------------------------------------------------------------ set-up
     def targets(self, nreplicas):
@@ -166,32 +157,28 @@ class CRescaleBarostat:
                                  "noise is that of the bath; stochastic=False (Berendsen) runs without one")
         elif not np.array_equal(BOLTZMAN * np.asarray(bath, dtype=np.float64), kT):
             raise ValueError("the barostat's temperatures must equal the thermostat's, replica by replica")
-        self._check_edges(torch.diagonal(it.systems.box.detach(), dim1=-2, dim2=-1).to("cpu", torch.float64).numpy())
+        positive_edges(box_edges(it.systems.box))
         it.forces._molecules()  # (pressure.check_molecules: every exclusion and every site's parents inside one molecule)
 
-    @staticmethod
-    def _check_edges(edges):
-        if not (np.asarray(edges) > 0).all():
-            raise ValueError("the barostat needs a periodic box: every box edge must be positive")
+    attach = check
+
+    def after_segment(self, integrator, out):
+        """Every replica is rescaled, velocities included: all three entries are those of the rescaled state."""
+        it = integrator
+        rec = self.apply(it.systems, it.forces, it.masses, it.dt, out[1], out[0])
+        Ekin, it.kinetic_source = it._run_precision(rec["K_after"]), None
+        return (Ekin, [float(u) for u in rec["U_new"]], it._temperature(Ekin))
 
     def _setup(self, system, forces):
         R, dev = system.pos.shape[0], system.pos.device
-        if self.rng is None:
-            self.rng = [np.random.Generator(np.random.Philox(key=np.array([self.seed, r], dtype=np.uint64))) for r in range(R)]
-        if len(self.rng) != R:
-            raise RuntimeError(f"the barostat holds {len(self.rng)} random streams for {R} replicas")
+        self._streams(R, "barostat")
         if self._work is None:
             self._work = np.zeros(R, dtype=np.float64)
         off, mem, _ = forces._molecules()
         if self._molecules is None or self._molecules[0] is not off or self._molecules[1].device != dev:
             self._molecules = (off, torch.as_tensor(off, device=dev), torch.as_tensor(mem, device=dev), bool(np.any(np.diff(off) > 64)))
             self._record = None
-        if self._record is None or self._record.shape[0] != R or self._record.device != dev:
-            nrec, npart = C.c_int64(), C.c_int64()
-            L.check(L.load().tmdhip_rescale_molecules_workspace(R, len(off) - 1, C.byref(nrec), C.byref(npart)),
-                    "tmdhip_rescale_molecules_workspace")
-            self._record = torch.zeros(R, nrec.value // R, dtype=torch.float64, device=dev)
-            self._partials = torch.empty(npart.value, dtype=torch.float64, device=dev)
+        self._workspace("tmdhip_rescale_molecules_workspace", R, dev, len(off) - 1)
 
     # ------------------------------------------------------------------ one application
     def apply(self, system, forces, masses, dt, epot, ekin=None):
@@ -212,8 +199,7 @@ class CRescaleBarostat:
         _, off, mem, has_big = self._molecules
         m = masses.reshape(-1)
         box0 = system.box.detach().clone()
-        edges = torch.diagonal(box0, dim1=-2, dim2=-1).to("cpu", torch.float64).numpy().reshape(R, 3)
-        self._check_edges(edges)
+        edges = positive_edges(box_edges(box0))
         terms = forces._pressure_terms(system.pos, system.box, vel=system.vel, masses=m)
         V, p_int = terms[:, 6].copy(), terms[:, 7].copy()
         U = np.asarray(epot, dtype=np.float64).reshape(R)
@@ -221,19 +207,12 @@ class CRescaleBarostat:
         mu = np.exp(delta_epsilon(p0, p_int, V, kT, beta, self.dt_over_tau(dt), xi, self.stochastic) / 3.0)
         if not (np.isfinite(mu).all() and (mu > 0).all()):
             raise RuntimeError("barostat: the box factor is not positive and finite (pressure or volume out of range)")
-        # the box the engine will see: the scaled edges rounded to the box tensor's precision; V' and the factors the
-        # molecules' centres are scaled by are taken from those, so box and positions stay consistent in fp32
-        new_box = box0.clone()
-        torch.diagonal(new_box, dim1=-2, dim2=-1).copy_(torch.as_tensor(mu[:, None] * edges).to(new_box))
-        new_edges = torch.diagonal(new_box, dim1=-2, dim2=-1).to("cpu", torch.float64).numpy().reshape(R, 3)
-        V_new = new_edges[:, 0] * new_edges[:, 1] * new_edges[:, 2]
+        new_box, new_edges, V_new = scaled_box(box0, edges, mu)
 
         rescale_molecules(system.pos, system.vel, m, new_edges / edges, off, mem, has_big, self._record, self._partials)
         system.box.copy_(new_box)  # through torch: Forces._host_box keys on the tensor's version counter
         U_new = np.asarray(forces.compute(system.pos, system.box, system.forces), dtype=np.float64).reshape(R)
-        # positions and velocities were written behind torch's back and the box is another one: the next tmdhip_md_run must
-        # not be told that it continues the previous one
-        forces._engine(system.pos)._md_key = None
+        forget_continuation(forces, system.pos)
         K = self._record[:, :2].cpu().numpy()
 
         self._work += (K[:, 1] - K[:, 0]) + (U_new - U) + p0 * (V_new - V)

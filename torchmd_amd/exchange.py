@@ -30,6 +30,7 @@ import numpy as np
 import torch
 
 from . import _lib as L
+from .controls import Control, philox_stream, require_layout, whole_frequency
 from .integrator import BOLTZMAN
 
 
@@ -74,7 +75,7 @@ def exchange_decisions(U, temperatures_of_rung, rung_of_slot, parity, u):
     return rungs, accepted, delta, pairs
 
 
-class ReplicaExchange:
+class ReplicaExchange(Control):
     """Temperature replica exchange; see the module docstring.  `attempt(system, masses, thermostat, epot)` is what the
     integrator calls every `frequency` steps.  `rungs`: host int array [R], the rung held by each slot; `attempts` /
     `accepted`: int64 [R - 1], per pair of neighbouring rungs; `record`: the last attempt's `pairs`, `U`, `delta`, `u`,
@@ -82,21 +83,39 @@ class ReplicaExchange:
     attempt, double [R, 5] = {K_before, factor, K_after, work, applications}; `work()`: the sum of K_after - K_before over all
     attempts, per slot; `rng`: the generator (anything with `.random()`)."""
 
+    rank = 2
+
     def __init__(self, frequency=500, seed=None):
-        if isinstance(frequency, bool) or not isinstance(frequency, (int, float, np.integer, np.floating)) \
-                or int(frequency) != frequency or frequency < 1:
-            raise ValueError("frequency must be a positive whole number of steps")
-        self.frequency = int(frequency)
-        # seeded from torch's global generator so torch.manual_seed() reproduces runs (as Integrator._seed)
-        self.seed = int(seed) if seed is not None else int(torch.randint(0, 2**62, (1,), dtype=torch.int64).item())
-        self.rng = np.random.Generator(np.random.Philox(key=np.array([self.seed, 0], dtype=np.uint64)))
+        if isinstance(frequency, bool) or not isinstance(frequency, (int, float, np.integer, np.floating)):
+            frequency = 0  # (refused below)
+        super().__init__(frequency, seed, "frequency must be a positive whole number of steps")
+        self.rng = philox_stream(self.seed, 0)
         self.ladder = None  # temperature of every rung, taken from the thermostat at the first attempt
         self.rungs = None
         self.attempts = self.accepted = None
         self.nattempts = 0
         self.record = None
         self.history = []
-        self._record = self._partials = None
+
+    def attach(self, integrator):
+        """What is refused (ValueError): atom groups, a barostat (which knows one temperature), and what `check` refuses."""
+        it = integrator
+        if it.batch is not None:
+            raise ValueError("exchange= does not support atom groups (batch=): a replica slot is rescaled as a whole")
+        if it.barostat is not None:
+            raise ValueError("exchange= cannot run under barostat=: the barostat holds one temperature")
+        whole_frequency(self.frequency, "the exchange frequency must be a positive whole number of steps")
+        self.check(it.thermostat, it.systems.pos.shape[0])
+
+    def after_segment(self, integrator, out):
+        """Attempted with the potential energies the segment returned: positions have not moved since."""
+        it = integrator
+        self.attempt(it.systems, it.masses, it.thermostat, out[1])
+        it.kinetic_source = self
+        return out
+
+    def kinetic(self):
+        return self.last[:, L.EXCHANGE_K_AFTER]
 
     @staticmethod
     def check(thermostat, nreplicas):
@@ -131,31 +150,17 @@ class ReplicaExchange:
         u = np.array([self.rng.random() for _ in range(ntried)], dtype=np.float64)
         return exchange_decisions(epot, self.ladder, self.rungs, parity, u) + (u,)
 
-    def _workspace(self, vel):
-        R = vel.shape[0]
-        if self._record is None or self._record.shape[0] != R or self._record.device != vel.device:
-            nrec, npart = C.c_int64(), C.c_int64()
-            L.check(L.load().tmdhip_velocity_rescale_workspace(R, C.byref(nrec), C.byref(npart)), "tmdhip_velocity_rescale_workspace")
-            self._record = torch.zeros(R, nrec.value // R, dtype=torch.float64, device=vel.device)
-            self._partials = torch.empty(npart.value, dtype=torch.float64, device=vel.device)
-
     def attempt(self, system, masses, thermostat, epot):
         """One attempt: decide on the host from `epot` [R] (the potential energies of the slots as they are), permute
         `thermostat.temperatures` in place, and enqueue the rescaling of `system.vel` [R, N, 3] on the current stream (no
         host synchronisation).  Returns (and keeps as `.record`) the record of the attempt."""
         vel = system.vel
-        L.require_device_tensor(vel, "system.vel")
-        L.require_device_tensor(masses, "masses")
-        if vel.dim() != 3 or vel.shape[2] != 3 or not vel.is_contiguous():
-            raise RuntimeError("system.vel must be a contiguous (nreplicas, natoms, 3) tensor")
-        R, N = vel.shape[0], vel.shape[1]
-        if masses.numel() != N or masses.dtype != vel.dtype or masses.device != vel.device or not masses.is_contiguous():
-            raise RuntimeError("masses must be a contiguous tensor of natoms entries with the dtype and device of system.vel")
+        R, N = require_layout(vel, "system.vel", masses)
         U = np.asarray(epot, dtype=np.float64).reshape(-1)
         if len(U) != R:
             raise ValueError(f"epot holds {len(U)} energies for {R} replicas")
         self.bind(thermostat, R)
-        self._workspace(vel)
+        self._workspace("tmdhip_velocity_rescale_workspace", R, vel.device)
         rungs, accepted, delta, pairs, u = self.decide(U)
         t_old = np.array(thermostat.temperatures, dtype=np.float64)
         t_new = self.ladder[rungs]

@@ -26,6 +26,7 @@ import numpy as np
 import torch
 
 from . import _lib as L
+from .controls import draw_seed
 from .forces import active_side_terms
 
 TIMEFACTOR = 48.88821
@@ -157,8 +158,7 @@ class Integrator:
             self.natoms = torch.bincount(batch).cpu().numpy()
         else:
             self.natoms = len(self.masses)
-        # noise stream: seeded from torch's global generator so torch.manual_seed() reproduces runs
-        self._seed = int(torch.randint(0, 2**62, (1,), dtype=torch.int64).item())
+        self._seed = draw_seed()  # (the noise stream)
         self._nstep = 0
         self._ke = None
         self.constraints = None  # constraints.ConstraintSet
@@ -170,21 +170,17 @@ class Integrator:
                              "stepped as part of its rigid water (sites on flexible molecules: Forces.compute only)")
         if constraints is not None:
             self._init_constraints(constraints)
-        self.barostat = barostat  # barostat.MonteCarloBarostat or crescale.CRescaleBarostat
-        # (a virial-driven barostat moves every time, rescales velocities too and holds one target per replica)
-        self._virial_barostat = bool(getattr(barostat, "virial_driven", False))
-        self._check_side_terms()
+        # the scheduled controls (controls.Control): thermostat.VelocityRescale; barostat.MonteCarloBarostat or
+        # crescale.CRescaleBarostat; exchange.ReplicaExchange.  `forces.metadynamics` is the fourth.
+        self.thermostat, self.barostat, self.exchange = thermostat, barostat, None
+        self._virial_barostat = bool(getattr(barostat, "virial_driven", False))  # (a plain attribute: nothing dispatches on it)
+        self.kinetic_source = None  # the control whose `kinetic()` holds the kinetic energies left (`Control.after_segment`)
+        self._check_side_terms()  # (before the exchange is known, so that the controls' own refusals come first)
         self.replays = 0  # batches that were rewound and repeated (list validity failure / step-block time-out)
-        self.thermostat = thermostat  # thermostat.VelocityRescale
-        if thermostat is not None:
-            self._init_thermostat(thermostat)
-        if barostat is not None and self._virial_barostat:
-            barostat.check(self)
-        elif barostat is not None:
-            barostat.check(systems, forces, temperature=(thermostat.temperature if thermostat is not None else T) or 0)
-        self.exchange = exchange  # exchange.ReplicaExchange
-        if exchange is not None:
-            self._init_exchange(exchange)
+        self.exchange = exchange
+        for c in (thermostat, barostat, exchange):  # (rank order)
+            if c is not None:
+                c.attach(self)
         self._check_side_terms()
 
     def _check_side_terms(self):
@@ -199,35 +195,6 @@ class Integrator:
         md = getattr(self.forces, "metadynamics", None)
         if md is not None and md.nreplicas != self.systems.pos.shape[0]:
             raise ValueError(f"the metadynamics bias was made for {md.nreplicas} replicas, the systems have {self.systems.pos.shape[0]}")
-
-    def _init_thermostat(self, th):
-        """What is refused (ValueError): a second thermostat (Langevin), atom groups, a ladder of the wrong length, a ladder
-        under a barostat (which knows one temperature).  The thermostat's N_f is this integrator's count of degrees of
-        freedom minus 3 when it removes the centre-of-mass motion; `_temperature` keeps dividing by the full count."""
-        if self.T or self.gamma is not None:
-            raise ValueError("thermostat= and a Langevin T / gamma are two thermostats: give one of them")
-        if self.batch is not None:
-            raise ValueError("thermostat= does not support atom groups (batch=): its scale factor is per replica")
-        th.targets(self.systems.pos.shape[0])
-        if self.barostat is not None and th.temperature is None and not self._virial_barostat:
-            raise ValueError("a temperature ladder cannot run under barostat=: the barostat holds one temperature")
-        if self.constraints is not None:
-            ndof = int(self._ndof)
-        else:
-            ndof = 3 * int((self.masses > 0).sum().item())
-        th.degrees_of_freedom(ndof)
-        self._thermostat_ndof = ndof
-
-    def _init_exchange(self, ex):
-        """What is refused (ValueError): exchange without a `VelocityRescale` that holds a sequence of temperatures (one per
-        replica, strictly increasing), atom groups, a barostat (which knows one temperature)."""
-        if self.batch is not None:
-            raise ValueError("exchange= does not support atom groups (batch=): a replica slot is rescaled as a whole")
-        if self.barostat is not None:
-            raise ValueError("exchange= cannot run under barostat=: the barostat holds one temperature")
-        if int(ex.frequency) != ex.frequency or ex.frequency < 1:
-            raise ValueError("the exchange frequency must be a positive whole number of steps")
-        ex.check(self.thermostat, self.systems.pos.shape[0])
 
     def _init_constraints(self, mode):
         from .constraints import find_constraints
@@ -246,6 +213,10 @@ class Integrator:
         if self.constraints is None:
             return kinetic_to_temp(Ekin, self.natoms)
         return 2.0 / (np.asarray(self._ndof, dtype=np.float64) * BOLTZMAN) * Ekin
+
+    def _run_precision(self, Ekin):
+        """A host array of kinetic energies in the precision of the run, as `step` returns it."""
+        return Ekin.astype(np.dtype("float32") if self.systems.pos.dtype == torch.float32 else np.float64)
 
     def _project_start(self):
         """OpenMM's applyConstraints at the first step: SHAKE the positions onto the constraints (the current positions as
@@ -280,27 +251,34 @@ class Integrator:
                 self.vcoeff = self.vcoeff.to(device=s.pos.device, dtype=s.pos.dtype).contiguous()
 
     def step(self, niter=1):
-        from .forces import Forces
-
-        lib = L.load()
-        s = self.systems
+        L.load()
         self._check_layout()
         self._check_side_terms()
-        dev = s.pos.device
-        code = L.dtype_code(s.pos.dtype)
-        R, N = s.pos.shape[0], s.pos.shape[1]
-        fast = isinstance(self.forces, Forces)
-        fused = fast and not self.forces.external and niter > 0
-        with torch.cuda.device(dev):
+        with torch.cuda.device(self.systems.pos.device):
             if self.constraints is not None and not self._projected:
                 self._project_start()
-            if self.thermostat is not None and niter > 0:
-                return self._step_thermostat(lib, s, dev, code, R, N, fast, niter)
-            if self.barostat is not None and niter > 0:
-                return self._step_npt(lib, s, dev, code, R, N, fast, niter)
-            if getattr(self.forces, "metadynamics", None) is not None and niter > 0:
-                return self._step_metad(lib, s, dev, code, R, N, fast, niter)
-            return self._step_body(lib, s, dev, code, R, N, fast, fused, niter, replay=False)
+            found = (self.thermostat, self.barostat, self.exchange, getattr(self.forces, "metadynamics", None))
+            return self.run_schedule(niter, [c for c in found if c is not None], self._step_body)
+
+    def run_schedule(self, niter, controls, run):
+        """`step(niter)` under scheduled controls (`controls.Control`): the call is cut into segments that end on
+        the multiples of the controls' frequencies, counted over the integrator's life; `run(n)` runs a segment as `step` runs
+        a call (rewind and replay included) and returns its (Ekin, pot, T); the controls whose multiple the segment ends on
+        then act in rank order.  The kinetic energy returned is that of the velocities as they are left: of whatever rescaled
+        them last after the last segment (`kinetic_source.kinetic()`, the only record read back).  `run` is `_step_body`; a host test
+        hands in a fake."""
+        controls = sorted(controls, key=lambda c: c.rank)
+        if not controls or niter <= 0:
+            return run(niter)
+        for n, hit in cut_schedules(self._nstep, niter, [c.frequency for c in controls]):
+            out, self.kinetic_source = run(n), None
+            for c, on in zip(controls, hit):
+                if on:
+                    out = c.after_segment(self, out)
+        if self.kinetic_source is not None:
+            Ekin = self._run_precision(self.kinetic_source.kinetic().cpu().numpy())
+            out, self.kinetic_source = (Ekin, out[1], self._temperature(Ekin)), None
+        return out
 
     def _pressure_terms(self):
         from .forces import Forces
@@ -330,97 +308,14 @@ class Integrator:
 
         return self._pressure_terms()[:, 7] / BAR_TO_KCAL_MOL_A3
 
-    def _step_npt(self, lib, s, dev, code, R, N, fast, niter):
-        """`step(niter)` at constant pressure: segments that end on multiples of the barostat's frequency (counted over the
-        integrator's life), each run as `step` runs it, and a volume move after every segment that ends on a multiple.
-        After an accepted move the returned potential energy and `systems.forces` are those of the scaled state."""
-        out = None
-        for n, attempt in cut_segments(self._nstep, niter, self.barostat.frequency):
-            fused = fast and not self.forces.external
-            out = self._step_body(lib, s, dev, code, R, N, fast, fused, n, replay=False)
-            if attempt:
-                out = self._barostat_move(s, out)
-        return out
+    def _step_body(self, niter, replay=False):
+        from .forces import Forces
 
-    def _barostat_move(self, s, out):
-        """The barostat's move after a segment that returned `out`; what `step` returns for the state it leaves.  Monte Carlo:
-        the potential energy of the replicas whose move was accepted changes.  Virial-driven (`CRescaleBarostat`): every
-        replica is rescaled, velocities included, so all three entries are those of the rescaled state."""
-        if not self._virial_barostat:
-            rec = self.barostat.attempt(s, self.forces, out[1])
-            pot = [float(un if ok else u) for u, un, ok in zip(rec["U"], rec["U_new"], rec["accepted"])]
-            return (out[0], pot, out[2])
-        rec = self.barostat.apply(s, self.forces, self.masses, self.dt, out[1], out[0])
-        Ekin = rec["K_after"].astype(np.dtype("float32") if s.pos.dtype == torch.float32 else np.float64)
-        return (Ekin, [float(u) for u in rec["U_new"]], self._temperature(Ekin))
-
-    def _step_metad(self, lib, s, dev, code, R, N, fast, niter):
-        """`step(niter)` under a metadynamics bias: segments that end on multiples of its frequency (counted over the
-        integrator's life), each run as `step` runs it (the grid is static inside a segment, so rewind and replay need nothing
-        new), and a deposition after every segment that ends on a multiple.  The potential energy returned contains V(s(x)) as
-        of before the deposition, and `systems.forces` stay as the finishing launch left them: a Gaussian is flat at its own
-        centre."""
-        md, out = self.forces.metadynamics, None
-        for n, hit in cut_segments(self._nstep, niter, md.frequency):
-            fused = fast and not self.forces.external
-            out = self._step_body(lib, s, dev, code, R, N, fast, fused, n, replay=False)
-            if hit and not md.frozen:
-                md.deposit(s)
-        return out
-
-    def _step_thermostat(self, lib, s, dev, code, R, N, fast, niter):
-        """`step(niter)` under a rescaling thermostat (and possibly a barostat, or replica exchange): segments cut at the
-        union of the schedules, each run as `step` runs it (rewind and replay included); the thermostat is applied after a
-        segment that ended on a multiple of its frequency has returned, before the volume move or the exchange attempt where
-        both fall on one step.  The kinetic energy returned is that of the velocities as they are left: `K_after` of the
-        record of whatever rescaled them last when the call ends on an application or an attempt."""
-        th, baro = self.thermostat, self.barostat
-        if self.exchange is not None:
-            return self._step_exchange(lib, s, dev, code, R, N, fast, niter)
-        md = getattr(self.forces, "metadynamics", None)  # (never with a barostat: refused)
-        freqs = (th.frequency,) + ((baro.frequency,) if baro is not None else ()) + ((md.frequency,) if md is not None else ())
-        out, rescaled = None, False
-        for n, hit in cut_schedules(self._nstep, niter, freqs):
-            fused = fast and not self.forces.external
-            out = self._step_body(lib, s, dev, code, R, N, fast, fused, n, replay=False)
-            rescaled = hit[0]
-            if hit[0]:
-                th.apply(s, self.masses, self.dt, self._thermostat_ndof)
-            if baro is not None and hit[1]:
-                out = self._barostat_move(s, out)
-                rescaled = rescaled and not self._virial_barostat  # (the kinetic energy returned is the barostat's K_after)
-            if md is not None and hit[-1] and not md.frozen:  # (after the thermostat's application where both fall on one step)
-                md.deposit(s)
-        if rescaled:
-            Ekin = th.last[:, L.THERMOSTAT_K_AFTER].cpu().numpy()
-            Ekin = Ekin.astype(np.dtype("float32") if s.pos.dtype == torch.float32 else np.float64)
-            out = (Ekin, out[1], self._temperature(Ekin))
-        return out
-
-    def _step_exchange(self, lib, s, dev, code, R, N, fast, niter):
-        """`_step_thermostat` with replica exchange as one more schedule (no barostat: refused).  Where both fall on one step
-        the thermostat is applied first, then the exchange is attempted with the potential energies the segment returned
-        (positions have not moved since).  A call that ends on an attempt returns the exchange record's `K_after`."""
-        th, ex = self.thermostat, self.exchange
-        out, last = None, None
-        for n, hit in cut_schedules(self._nstep, niter, (th.frequency, ex.frequency)):
-            fused = fast and not self.forces.external
-            out = self._step_body(lib, s, dev, code, R, N, fast, fused, n, replay=False)
-            last = None
-            if hit[0]:
-                th.apply(s, self.masses, self.dt, self._thermostat_ndof)
-                last = th.last[:, L.THERMOSTAT_K_AFTER]
-            if hit[1]:
-                ex.attempt(s, self.masses, th, out[1])
-                last = ex.last[:, L.EXCHANGE_K_AFTER]
-        if last is not None:
-            Ekin = last.cpu().numpy()
-            Ekin = Ekin.astype(np.dtype("float32") if s.pos.dtype == torch.float32 else np.float64)
-            out = (Ekin, out[1], self._temperature(Ekin))
-        return out
-
-    def _step_body(self, lib, s, dev, code, R, N, fast, fused, niter, replay):
-
+        lib, s = L.load(), self.systems
+        dev, code = s.pos.device, L.dtype_code(s.pos.dtype)
+        R, N = s.pos.shape[0], s.pos.shape[1]
+        fast = isinstance(self.forces, Forces)
+        fused = fast and not self.forces.external and niter > 0
         pot = None
         ebuf = ext = None
         if fused:
@@ -478,7 +373,7 @@ class Integrator:
                 # integrator kernel); the noise stream is counter based, so it is the same trajectory
                 if not replay:
                     self.replays += 1
-                    return self._step_body(lib, s, dev, code, R, N, fast, fused, niter, replay=True)
+                    return self._step_body(niter, replay=True)
                 raise RuntimeError(_REPLAY_FAILED + L.last_error())
             cols = self.forces.energy_columns()
             tot = obs[:, cols].sum(axis=1) if cols else np.zeros(R)
@@ -488,8 +383,7 @@ class Integrator:
                 t.store(row)
                 tot = tot + t.potential(row)
             pot = [float(v) for v in tot]
-            Ekin = obs[:, L.NENERGY].copy()
-            Ekin = Ekin.astype(np.dtype("float32") if s.pos.dtype == torch.float32 else np.float64)
+            Ekin = self._run_precision(obs[:, L.NENERGY].copy())
             return Ekin, pot, self._temperature(Ekin)
         if self.batch is None:
             if eng is not None:
@@ -524,7 +418,7 @@ class Integrator:
                 why = L.last_error()  # (tmdhip_check's verdict, set by judge_flags a moment ago)
                 if fused and not replay:  # (batch mode of the fused loop: same rewind as above)
                     self.replays += 1
-                    return self._step_body(lib, s, dev, code, R, N, fast, fused, niter, replay=True)
+                    return self._step_body(niter, replay=True)
                 raise RuntimeError((_REPLAY_FAILED + why) if (fused and replay) else (_LIST_INVALID + ": " + why))
             if ebuf is not None:
                 # (the step-by-step loop: the side terms' energies of its last evaluation, as the fused path leaves them)
@@ -532,6 +426,5 @@ class Integrator:
                     t.store(eng.side_row(t).cpu().numpy())
         else:
             Ekin = ke.flatten().cpu().numpy()
-        Ekin = Ekin.astype(np.dtype("float32") if s.pos.dtype == torch.float32 else np.float64)
-        T = self._temperature(Ekin)
-        return Ekin, pot, T
+        Ekin = self._run_precision(Ekin)
+        return Ekin, pot, self._temperature(Ekin)

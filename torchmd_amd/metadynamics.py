@@ -20,6 +20,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib as L
+from .controls import Control, whole_frequency
 
 KINDS = {"distance": 0, "dihedral": 1}
 TWO_PI = 2.0 * np.pi
@@ -132,7 +133,8 @@ def locate(lo, h, nodes, periodic, s):
     return int(fl), int(fl) + 1, x - fl, live
 
 
-class Metadynamics(L.SideTerm):
+class Metadynamics(L.SideTerm, Control):
+    rank = 3  # (the deposition, as a scheduled control: after the thermostat's application where both fall on one step)
     side_name, side_width = "metadynamics", 3  # (V, s_0, s_1)
     side_potential = slice(0, 1)
     side_apply, side_energy = "tmdhip_metad_apply", "tmdhip_metad_energy"
@@ -181,9 +183,7 @@ class Metadynamics(L.SideTerm):
         if not np.isfinite(height) or height <= 0:
             raise ValueError("Metadynamics: height must be finite and positive")
         self.height = float(height)
-        if int(frequency) != frequency or frequency < 1:
-            raise ValueError("Metadynamics: frequency must be a positive whole number of steps")
-        self.frequency = int(frequency)
+        self.frequency = whole_frequency(frequency, "Metadynamics: frequency must be a positive whole number of steps")
         if not np.isfinite(temperature) or temperature <= 0:
             raise ValueError("Metadynamics: temperature must be finite and positive")
         self.temperature = float(temperature)
@@ -486,6 +486,13 @@ class Metadynamics(L.SideTerm):
                                                  C.c_void_p(torch.cuda.current_stream(pos.device).cuda_stream)), "tmdhip_metad_deposit")
         self.nhills += 1
         self._dev_dirty = True
+
+    def after_segment(self, integrator, out):
+        """A frozen bias still cuts the call and deposits nothing.  The potential energy returned contains V(s(x)) as of
+        before the deposition, and `systems.forces` stay as they are: a Gaussian is flat at its own centre."""
+        if not self.frozen:
+            self.deposit(integrator.systems)
+        return out
 
     def report(self, out):
         """Take (V, s_0, s_1) [R,3] of an evaluation: `energy` [R] and `cv` [R, ncv]."""

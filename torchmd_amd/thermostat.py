@@ -36,6 +36,7 @@ import numpy as np
 import torch
 
 from . import _lib as L
+from .controls import Control, require_layout
 from .integrator import BOLTZMAN, PICOSEC2TIMEU
 
 _DP = C.POINTER(C.c_double)
@@ -45,7 +46,7 @@ def _dp(a):
     return a.ctypes.data_as(_DP)
 
 
-class VelocityRescale:
+class VelocityRescale(Control):
     """Stochastic velocity rescaling; see the module docstring.  `apply(system, masses, dt, ndof)` is what the integrator calls
     every `frequency` steps.  `last`: the device record of the last application, double [R, 4] = {K_before, alpha, K_after,
     |V_cm|} per replica (K of the centre-of-mass-free velocities when `remove_com` is on); `heat()`: the sum of
@@ -53,26 +54,22 @@ class VelocityRescale:
     application; `applications`: how many were made; `nf`: the N_f of the last application; `rng`: the list of per-replica
     generators (anything with `.standard_normal()` and `.standard_gamma(shape)`)."""
 
+    rank = 0
+
     def __init__(self, temperature, tau=0.1, frequency=10, remove_com=True, seed=None):
         t = np.atleast_1d(np.asarray(temperature, dtype=np.float64))
         if t.ndim != 1 or t.size == 0 or not np.isfinite(t).all() or not (t > 0).all():
             raise ValueError("temperature must be a positive number, or a sequence of positive numbers (one per replica)")
         if not np.isfinite(tau) or tau < 0:
             raise ValueError("tau must be a non-negative time in ps (0: the kinetic energy is resampled at every application)")
-        if int(frequency) != frequency or frequency < 1:
-            raise ValueError("frequency must be a positive number of steps")
+        super().__init__(frequency, seed)
         self.temperatures = t
         self.ladder = np.ndim(temperature) > 0  # a sequence (even of length 1) must match the number of replicas
         self.tau = float(tau)
-        self.frequency = int(frequency)
         self.remove_com = bool(remove_com)
-        # seeded from torch's global generator so torch.manual_seed() reproduces runs (as Integrator._seed)
-        self.seed = int(seed) if seed is not None else int(torch.randint(0, 2**62, (1,), dtype=torch.int64).item())
-        self.rng = None
         self.draws = None
         self.nf = None
         self.applications = 0
-        self._record = self._partials = None
 
     # ------------------------------------------------------------------ set-up
     @property
@@ -97,17 +94,30 @@ class VelocityRescale:
             raise ValueError(f"the thermostat needs at least 2 degrees of freedom, has {nf}")
         return nf
 
-    def _setup(self, vel):
-        R = vel.shape[0]
-        if self.rng is None:
-            self.rng = [np.random.Generator(np.random.Philox(key=np.array([self.seed, r], dtype=np.uint64))) for r in range(R)]
-        if len(self.rng) != R:
-            raise RuntimeError(f"the thermostat holds {len(self.rng)} random streams for {R} replicas")
-        if self._record is None or self._record.shape[0] != R or self._record.device != vel.device:
-            nrec, npart = C.c_int64(), C.c_int64()
-            L.check(L.load().tmdhip_thermostat_workspace(R, C.byref(nrec), C.byref(npart)), "tmdhip_thermostat_workspace")
-            self._record = torch.zeros(R, nrec.value // R, dtype=torch.float64, device=vel.device)
-            self._partials = torch.empty(npart.value, dtype=torch.float64, device=vel.device)
+    def attach(self, integrator):
+        """What is refused (ValueError): a second thermostat (Langevin), atom groups, a ladder of the wrong length, a ladder
+        under a barostat that knows one temperature.  N_f is the integrator's count of degrees of freedom minus 3 when the
+        centre-of-mass motion is removed; `Integrator._temperature` keeps dividing by the full count."""
+        it = integrator
+        if it.T or it.gamma is not None:
+            raise ValueError("thermostat= and a Langevin T / gamma are two thermostats: give one of them")
+        if it.batch is not None:
+            raise ValueError("thermostat= does not support atom groups (batch=): its scale factor is per replica")
+        self.targets(it.systems.pos.shape[0])
+        if it.barostat is not None and self.temperature is None and not it.barostat.ladder_ok:
+            raise ValueError("a temperature ladder cannot run under barostat=: the barostat holds one temperature")
+        ndof = int(it._ndof) if it.constraints is not None else 3 * int((it.masses > 0).sum().item())
+        self.degrees_of_freedom(ndof)
+        it._thermostat_ndof = ndof
+
+    def after_segment(self, integrator, out):
+        it = integrator
+        self.apply(it.systems, it.masses, it.dt, it._thermostat_ndof)
+        it.kinetic_source = self
+        return out
+
+    def kinetic(self):
+        return self.last[:, L.THERMOSTAT_K_AFTER]
 
     # ------------------------------------------------------------------ one application
     def apply(self, system, masses, dt, ndof, active=None):
@@ -118,16 +128,11 @@ class VelocityRescale:
         or `ConstraintSet.ndof()`); `active` (optional, [R]): replicas with a 0 are skipped — their velocities and
         records stay, their random numbers are drawn all the same."""
         vel = system.vel
-        L.require_device_tensor(vel, "system.vel")
-        L.require_device_tensor(masses, "masses")
-        if vel.dim() != 3 or vel.shape[2] != 3 or not vel.is_contiguous():
-            raise RuntimeError("system.vel must be a contiguous (nreplicas, natoms, 3) tensor")
-        R, N = vel.shape[0], vel.shape[1]
-        if masses.numel() != N or masses.dtype != vel.dtype or masses.device != vel.device or not masses.is_contiguous():
-            raise RuntimeError("masses must be a contiguous tensor of natoms entries with the dtype and device of system.vel")
+        R, N = require_layout(vel, "system.vel", masses)
         T = np.ascontiguousarray(self.targets(R), dtype=np.float64)
         nf = self.degrees_of_freedom(ndof)
-        self._setup(vel)
+        self._streams(R, "thermostat")
+        self._workspace("tmdhip_thermostat_workspace", R, vel.device)
         draws = np.array([[g.standard_normal(), 2.0 * g.standard_gamma(0.5 * (nf - 1))] for g in self.rng], dtype=np.float64)
         kbar = np.ascontiguousarray(0.5 * nf * BOLTZMAN * T)
         nfs = np.full(R, float(nf))
