@@ -750,7 +750,7 @@ def test_fused_launch_timeout_falls_back_to_the_integrator_kernel(monkeypatch):
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("case", ["water_langevin", "water_nve", "water_two_replicas", "lj_langevin", "water_counter_wraps",
-                                  "water_32_lanes", "water_64_lanes", "thrombin", "light_full"])
+                                  "water_two_replicas_counter_wraps", "water_32_lanes", "water_64_lanes", "thrombin", "light_full"])
 def test_step_blocks_of_the_pair_launch_are_bit_identical(case, monkeypatch):
     """Interior steps of tmdhip_md_run on the lean fp32 pair kernel are made by the pair launch itself ("step blocks"
     behind the pair blocks wait for the pair waves of their atoms: FusedStep in csrc/engine.h, pair_fast_f32.hip) instead of by an
@@ -759,7 +759,8 @@ def test_step_blocks_of_the_pair_launch_are_bit_identical(case, monkeypatch):
     the window and chain skipping active (size gate opened).  Water = 8 lanes per atom (two pair blocks per step
     block) + inline bonded records + reaction field; the LJ box = 4 lanes per atom, no bonded terms.
     `water_counter_wraps`: the launch number the force records carry starts at 2^32 - 20 and wraps during the run
-    (0 is skipped: it means "never written").  `thrombin`: a protein (4 676 atoms, all seven terms, open boundaries) —
+    (0 is skipped: it means "never written"); `water_two_replicas_counter_wraps`: the same for the two replicas' counters in
+    the batched launch.  `thrombin`: a protein (4 676 atoms, all seven terms, open boundaries) —
     a heavy topology, whose bonded force is evaluated by bonded_wave_kernel in front of the pair launch into a buffer
     that the step blocks add.  (fp64 contexts keep the separate integrator kernel: their step blocks were measured
     slower in round 4 and removed in round 5.)"""
@@ -771,9 +772,9 @@ def test_step_blocks_of_the_pair_launch_are_bit_identical(case, monkeypatch):
 
     dev, dt = _dev(), torch.float32
     monkeypatch.setenv("TMDHIP_DEBUG_CHAIN_MIN_ENTRIES", "1")
-    if case == "water_counter_wraps":
+    if case.endswith("counter_wraps"):
         monkeypatch.setenv("TMDHIP_DEBUG_FUSED_GEN0", str(2**32 - 20))
-    nrep = 2 if case == "water_two_replicas" else 1
+    nrep = 2 if case.startswith("water_two_replicas") else 1
     if case == "thrombin":
         g = load("thrombin")
         par = GoldenParameters(g, dt)
@@ -822,6 +823,8 @@ def test_step_blocks_of_the_pair_launch_are_bit_identical(case, monkeypatch):
         # every interior step: (2 - 1) + (41 - 1) + 0 + (37 - 1)
         assert st["steps_in_pair_launch"] == 77, st
         assert st["n_rebuilds"] >= 2 and st["chains_skipped"] > 20, st
+    if case == "water_two_replicas_counter_wraps":  # (it is the batched kernel's counter that wrapped)
+        assert st1[0]["batched_launches"] > 0, st1[0]
     for st, su in zip(st1, st0):
         assert su["steps_in_pair_launch"] == 0
         assert st["n_rebuilds"] == su["n_rebuilds"] and st["chains_skipped"] == su["chains_skipped"]

@@ -8,7 +8,10 @@ The rule (tmdhip_md_run and tmdhip_dd_run share it): a replica's host-mapped wor
 number in which an atom was near its displacement limit, [3 + p] the last one whose step rebuilt the list, p = seq & 1.  With a
 valid report of the previous step `seq` that this step follows, and no timeout, the rebuild chain is left out when nobody was
 near its limit in that step, or when that step rebuilt the list with its chain in place (prev_skipped false: every displacement
-is one step old).  Otherwise the chain stays.  The step's own number is seq + 1, and never 0 (0 = nothing published yet)."""
+is one step old).  Otherwise the chain stays.  The step's own number is seq + 1, and never 0 (0 = nothing published yet).
+
+The same header holds the grid geometry of a replica's share of a fused pair + step launch (fused_grid): pair blocks of four waves
+rounded up to the 8 XCDs, and behind them the step blocks, which find their atoms from these numbers alone."""
 
 import ctypes as C
 import os
@@ -35,6 +38,10 @@ def pc(tmp_path_factory):
     lib.pc_decide.restype = None
     lib.pc_next_seq.argtypes = [C.c_uint]
     lib.pc_next_seq.restype = C.c_uint
+    lib.pc_fast_threads.argtypes = []
+    lib.pc_fast_threads.restype = C.c_int
+    lib.pc_fused_grid.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int)]
+    lib.pc_fused_grid.restype = None
     return lib
 
 
@@ -98,3 +105,37 @@ def test_sequence_numbers_wrap_past_zero(pc):
     assert pc.pc_next_seq(0xFFFFFFFF) == 1  # never 0
     _, nxt = decide(pc, words(0xFFFFFFFF, True, False), 0xFFFFFFFF)
     assert nxt == 1
+
+
+K_FAST_THREADS = 256  # threads of a pair block (four waves); step blocks have as many
+
+
+def parent_fused_grid(n, apw, lpa, bonded):
+    """The formula as the two launchers each spelled it before they shared fused_grid, transcribed literally."""
+    waves = (n + apw - 1) // apw
+    wpb = K_FAST_THREADS // 64
+    npair8 = ((waves + wpb - 1) // wpb + 7) // 8 * 8
+    k, g8 = lpa * 64 // K_FAST_THREADS, npair8 // 8
+    units = (g8 + k - 1) // k
+    return npair8, units, 8 * (units if bonded == 1 else (units + 3) // 4)
+
+
+@pytest.mark.parametrize("bonded", [0, 1, 2])
+@pytest.mark.parametrize("lpa", [4, 8, 16, 32, 64])
+def test_fused_grid_shape(pc, lpa, bonded):
+    """What the step blocks rely on: whole rounds of 8 blocks (one per XCD) of either kind, and enough step blocks for the atoms
+    of all pair blocks — a step block takes 64 atoms with inline bonded records (bonded = 1), 256 otherwise."""
+    assert pc.pc_fast_threads() == K_FAST_THREADS
+    apw = 64 // lpa  # atoms per wave (ListGeom::apw)
+    per_block = K_FAST_THREADS // 64 * apw  # atoms of a pair block
+    rnd = 8 * per_block  # atoms of one round of 8 pair blocks
+    counts = {1, apw - 1, apw, apw + 1, rnd - apw, rnd - apw - 1, rnd - apw + 1, rnd - 1, rnd, rnd + 1, rnd + apw - 1, rnd + apw,
+              rnd + apw + 1, 8232, 98304}  # (8 232: the tests' water box, 98 304: the benchmark's)
+    for n in sorted(c for c in counts if c >= 1):
+        out = (C.c_int * 3)()
+        pc.pc_fused_grid(n, apw, lpa, bonded, out)
+        pair_blocks, units, step_blocks = out
+        assert pair_blocks % 8 == 0 and pair_blocks * per_block >= n > (pair_blocks - 8) * per_block, (n, lpa, pair_blocks)
+        assert step_blocks % 8 == 0 and step_blocks > 0, (n, lpa, bonded, step_blocks)
+        assert step_blocks * (64 if bonded == 1 else 256) >= pair_blocks * per_block, (n, lpa, bonded, pair_blocks, step_blocks)
+        assert (pair_blocks, units, step_blocks) == parent_fused_grid(n, apw, lpa, bonded), (n, lpa, bonded)

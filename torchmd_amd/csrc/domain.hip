@@ -539,18 +539,9 @@ int dd_fused_back(tmdhip_ctx *ctx, Replica &rp, tmdhip_comm *c, const tmdhip_dd_
       now.dd_csr_row = c->csr_row.as<int>();
       now.dd_shift = (const R *)d->send_shift_dev;
       now.dd_out = (R *)d->send_buf_dev;
-      TMD_TRY(upload_fused_static<R>(rp, now, st));
-      fl.fst = rp.fused_dev.as<FusedStaticT<R>>();
-      fl.langevin = d->vcoeff_dev != nullptr;
-      fl.step.pos_in = (const R *)d->pos_dev;  // (no bonded terms: the update reads the cell-sorted records, so it
-      fl.step.pos_out = (R *)d->pos_dev;       // can store the owned rows in place)
-      fl.step.sorted_out = rp.sorted_alt.as<R4>();
-      fl.step.noise_step = next_kick_step;
-      fl.step.bonded = 0;
-      if (rp.pub_ptr) {  // pacing on: the next iteration's sequence number
-        fl.step.seq = next_seq(rp.seq);
-        fl.step.near_host = rp.hostpub + 1 + (fl.step.seq & 1u);
-      }
+      // (no bonded terms: the update reads the cell-sorted records, so it can store the owned rows in place; paced while pacing is on)
+      TMD_TRY(fused_launch_common<R>(rp, now, d->vcoeff_dev != nullptr, (const R *)d->pos_dev, (R *)d->pos_dev, next_kick_step,
+                                     rp.pub_ptr != nullptr, fl, st));
       fused_next = true;
     }
   }
@@ -562,10 +553,7 @@ int dd_fused_back(tmdhip_ctx *ctx, Replica &rp, tmdhip_comm *c, const tmdhip_dd_
     fused_next = false;
     return rc;
   }
-  if (fused_next) {
-    std::swap(rp.sorted, rp.sorted_alt);
-    rp.steps_in_pair_launch++;
-  }
+  if (fused_next) fused_step_made(rp);
   return 0;
 }
 

@@ -413,7 +413,6 @@ constexpr int kLmViolation = 1;  // the chain of this step was left out and its 
 constexpr int kLmParity = 2;     // parity of this step
 constexpr int kLmStream = 8;     // the list does not fit the Infinity Cache: stream it with the non-temporal hint (pair_fast_f32.hip)
 constexpr int kLmPadded = 4;     // Replica::pad_rows: the dummy records exist; a wave group whose padgen word equals the rebuild count is padded
-constexpr int kFastThreads = 256;  // threads of a block of the lean fp32 pair kernel (step blocks are four waves)
 
 // ---- the step in the lean pair kernels' launch (see FusedStepT above) -------------------------------------------
 template <typename R>
@@ -846,8 +845,11 @@ int launch_pair_fast_f32(tmdhip_ctx *ctx, Replica &rp, const PairConsts<float> &
 template <bool ENERGY>
 int launch_pair_lean_f64(tmdhip_ctx *ctx, Replica &rp, const PairConsts<double> &c, double *f, int overwrite,
                          hipStream_t st, hipEvent_t e0, hipEvent_t e1, int lmode);
+// grid geometry of one replica's share of a fused launch, lone or batched (pacing.h: fused_grid)
+inline FusedGrid fused_grid_shape(const tmdhip_ctx *ctx, const Replica &rp, int bonded) {
+  return fused_grid(ctx->d.natoms, rp.lg.apw, rp.lg.lpa, bonded);
+}
 // pair_fast_f32_batch.hip: the replicas rep0 .. rep0 + bl.nrep - 1 of a cell-list context in one FUSED launch (BatchRep / BatchLaunch)
-void fused_grid_shape(const tmdhip_ctx *ctx, const Replica &rp, int bonded, int &pair_blocks, int &step_blocks);
 int launch_pair_fast_f32_batch(tmdhip_ctx *ctx, int rep0, const PairConsts<float> &c, const BatchLaunch &bl, int lpa, bool energy,
                                bool langevin, hipStream_t st);
 // pme.hip: the reciprocal-space part, excluded-pair correction, self and background terms of replica `r` — adds into
@@ -900,6 +902,22 @@ void fused_static_common(FusedStaticT<R> &now, int n, R *vel, const R *mass, con
 // device copy of a replica's FusedStatic, re-uploaded (one-thread kernel, stream-ordered) only when a field has changed
 template <typename R>
 int upload_fused_static(Replica &rp, const FusedStaticT<R> &now, hipStream_t st);
+// the per-launch part of a FUSED launch that makes a step, for tmdhip_md_run and a brick alike: `now` uploaded, where the step
+// reads and writes, its noise row and bonded mode (now.has_bonded) and — `paced` — the NEXT iteration's sequence number with its
+// report word (pace_behind_device)
+template <typename R>
+int fused_launch_common(Replica &rp, const FusedStaticT<R> &now, bool langevin, const R *pos_in, R *pos_out, uint64_t noise_step,
+                        bool paced, FusedLaunchT<R> &fl, hipStream_t st);
+// The force records of a replica's next fused launch, lone or batched: `fsort` exists (zeroed when it grows: launch number 0 =
+// never written) and `gen` is the launch's number — never 0, counted on from TMDHIP_DEBUG_FUSED_GEN0 (test knob: just below the
+// wrap-around) for a replica's first launch.  The other test knob, TMDHIP_DEBUG_STEP_TIMEOUT, stays with the lone launcher: it
+// needs FusedStepT::watch_gen, which BatchLaunch does not carry — a kernel argument of the batched launch would change.
+int begin_fused_launch(Replica &rp, int n, hipStream_t st, unsigned &gen);
+// ... and what is left to do on the host after a launch that made a step: the copy it wrote is the current one
+inline void fused_step_made(Replica &rp) {
+  std::swap(rp.sorted, rp.sorted_alt);
+  rp.steps_in_pair_launch++;
+}
 // can the pair launch of this replica integrate the next step itself?  (lean kernels, 4 .. 64 lanes per atom)
 template <typename R>
 bool fused_step_possible(const tmdhip_ctx *ctx, const Replica &rp, const PairConsts<R> &c);

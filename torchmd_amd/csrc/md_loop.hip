@@ -218,6 +218,41 @@ template void fused_static_common<float>(FusedStaticT<float> &, int, float *, co
 template void fused_static_common<double>(FusedStaticT<double> &, int, double *, const double *, const double *, double, double, uint64_t,
                                           uint64_t, const double *, const int *, const ListCheck<double> &, double);
 
+template <typename R>
+int fused_launch_common(Replica &rp, const FusedStaticT<R> &now, bool langevin, const R *pos_in, R *pos_out, uint64_t noise_step,
+                        bool paced, FusedLaunchT<R> &fl, hipStream_t st) {
+  TMD_TRY(upload_fused_static(rp, now, st));
+  fl.fst = rp.fused_dev.as<FusedStaticT<R>>();
+  fl.langevin = langevin;
+  fl.step.pos_in = pos_in;
+  fl.step.pos_out = pos_out;
+  fl.step.sorted_out = rp.sorted_alt.as<typename Vec<R>::T4>();
+  fl.step.noise_step = noise_step;
+  fl.step.bonded = now.has_bonded;
+  if (paced) {
+    fl.step.seq = next_seq(rp.seq);
+    fl.step.near_host = rp.hostpub + 1 + (fl.step.seq & 1u);
+  }
+  return 0;
+}
+template int fused_launch_common<float>(Replica &, const FusedStaticT<float> &, bool, const float *, float *, uint64_t, bool,
+                                        FusedLaunchT<float> &, hipStream_t);
+template int fused_launch_common<double>(Replica &, const FusedStaticT<double> &, bool, const double *, double *, uint64_t, bool,
+                                         FusedLaunchT<double> &, hipStream_t);
+
+int begin_fused_launch(Replica &rp, int n, hipStream_t st, unsigned &gen) {
+  if (rp.fsort.bytes < sizeof(float4) * (size_t)n) {
+    TMD_TRY(rp.fsort.ensure(sizeof(float4) * (size_t)n));
+    TMD_HIP(hipMemsetAsync(rp.fsort.p, 0, rp.fsort.bytes, st));
+    rp.fused_gen = 0;
+  }
+  if (rp.fused_gen == 0)
+    if (const char *e = std::getenv("TMDHIP_DEBUG_FUSED_GEN0")) rp.fused_gen = (unsigned)std::strtoul(e, nullptr, 0);
+  gen = rp.fused_gen = next_seq(rp.fused_gen);
+  rp.fused_launches++;
+  return 0;
+}
+
 // can the pair launch of this replica integrate the next step itself?  (lean fp32 kernel, 4 .. 64 lanes per atom: a pair
 // block's atoms fit one wave of a step block.  fp64: built in round 4, bit-identical and slower — 151 against 124.5 us
 // per step at C3, no partial last round of pair blocks for the step blocks to hide in — and removed in round 5.)
@@ -301,15 +336,14 @@ static int launch_replica_batch(tmdhip_ctx *ctx, std::vector<BatchItem> &items, 
     ctx->batch_host.assign(nrep, BatchRep{});
     for (auto &e : ctx->batch_host) std::memset(&e, 0xFF, sizeof(e));  // (matches nothing: every entry is uploaded)
   }
-  int pair_blocks = 0, step_blocks = 0;
-  fused_grid_shape(ctx, ctx->rep[0], bonded, pair_blocks, step_blocks);
+  const FusedGrid grid = fused_grid_shape(ctx, ctx->rep[0], bonded);
   for (int g0 = 0; g0 < nrep; g0 += kBatchMax) {
     const int gn = std::min(kBatchMax, nrep - g0);
     BatchLaunch bl;
     std::memset(&bl, 0, sizeof(bl));
     bl.nrep = gn;
-    bl.pair_blocks = pair_blocks;
-    bl.step_blocks = step_blocks;
+    bl.pair_blocks = grid.pair_blocks;
+    bl.step_blocks = grid.step_blocks;
     bl.bonded = bonded;
     bl.poll_limit = 1u << 22;  // ~4 s of polling
     bl.noise_step = noise_step;
@@ -318,13 +352,7 @@ static int launch_replica_batch(tmdhip_ctx *ctx, std::vector<BatchItem> &items, 
       const int r = g0 + k;
       Replica &rp = ctx->rep[r];
       BatchItem &it = items[r];
-      if (rp.fsort.bytes < sizeof(float4) * (size_t)n) {
-        TMD_TRY(rp.fsort.ensure(sizeof(float4) * (size_t)n));
-        TMD_HIP(hipMemsetAsync(rp.fsort.p, 0, rp.fsort.bytes, st));  // launch number 0 = never written
-        rp.fused_gen = 0;
-      }
-      rp.fused_gen = next_seq(rp.fused_gen);
-      rp.fused_launches++;
+      TMD_TRY(begin_fused_launch(rp, n, st, bl.gen[k]));
       const PairConsts<float> c = make_consts<float>(ctx, it.box);
       BatchRep e;
       std::memset(&e, 0, sizeof(e));
@@ -363,7 +391,6 @@ static int launch_replica_batch(tmdhip_ctx *ctx, std::vector<BatchItem> &items, 
       if (it.fl.step.near_host) bits |= kBlReports;
       if (it.pub_ptr) bits |= kBlPublish;
       bl.bits[k] = bits;
-      bl.gen[k] = rp.fused_gen;
       bl.seq[k] = it.fl.step.seq;
       bl.pub[k] = it.pub_val;
     }
@@ -765,19 +792,7 @@ struct MdRun {
     now.fbond = bm == 2 ? rp.fbond.as<R>() : nullptr;
     now.nactive = 0x7fffffff;
     TMD_TRY(rp.pos_alt.ensure(sizeof(R) * stride));
-    TMD_TRY(upload_fused_static(rp, now, st));
-    fl.fst = rp.fused_dev.as<FusedStaticT<R>>();
-    fl.langevin = langevin;
-    fl.step.pos_in = pos;
-    fl.step.pos_out = pos == s.home ? rp.pos_alt.as<R>() : s.home;
-    fl.step.sorted_out = rp.sorted_alt.as<R4>();
-    fl.step.noise_step = d->step0 + (uint64_t)it;
-    fl.step.bonded = bm;
-    if (s.pace) {  // the next iteration's sequence number (see pace_behind_device)
-      fl.step.seq = next_seq(rp.seq);
-      fl.step.near_host = rp.hostpub + 1 + (fl.step.seq & 1u);
-    }
-    return 0;
+    return fused_launch_common<R>(rp, now, langevin, pos, pos == s.home ? rp.pos_alt.as<R>() : s.home, d->step0 + (uint64_t)it, s.pace, fl, st);
   }
 
   // forces of step `it` (forces.py:122-319): nonbonded stores (list path) or accumulates into zeros
@@ -868,23 +883,9 @@ struct MdRun {
                                    st, fuse ? &fl : nullptr);
     rp.pub_ptr = nullptr;
     if (fuse && rc == 0 && en) {
-      // the call's last step: forces (pair + bonded) are in `forces`, velocities kicked, the energy rows (pair,
-      // bonded, kinetic) folded here — into the call's energy buffer and the context's kinetic-energy word
-      TMD_TRY(ctx->obs_ke.ensure(sizeof(double) * ctx->rep.size()));
-      if (nrep == 1) {  // ... and reported to the host in the same launch (tmdhip_md_observe then only waits for the word)
-        TMD_TRY(publish_final_step(ctx, rp, en, st));
-      } else {
-        hipLaunchKernelGGL(final_fold_kernel, dim3(1), dim3(kEnergySlots), 0, st, ctx->escratch.as<double>(), en,
-                           ctx->obs_ke.as<double>());
-        TMD_HIP(hipGetLastError());
-      }
-      note_final_step();
-      finalized[r] = 1;
+      TMD_TRY(took_final(true));  // (a lone launch is FINAL only in a context of one replica: fused_launch_args)
     } else if (fuse && rc == 0) {
-      cur[r] = fl.step.pos_out;
-      std::swap(rp.sorted, rp.sorted_alt);
-      stepped[r] = 1;
-      rp.steps_in_pair_launch++;
+      took_step(r, fl.step.pos_out);
     } else if (rc == kFallbackAllPairs) {
       ctx->algorithm = TMDHIP_ALGO_ALLPAIRS;
       s.list = complete = false;
@@ -897,11 +898,31 @@ struct MdRun {
     return 0;
   }
 
-  // FINAL step blocks have summed the kinetic energy of the call's last velocities (tmdhip_md_observe need not)
-  void note_final_step() {
+  // The aftermath of a fused launch, lone or batched.  It made the next step of replica r: positions and cell-sorted records of
+  // the coming iteration are the launch's output.
+  void took_step(int r, R *pos_out) {
+    cur[r] = pos_out;
+    fused_step_made(ctx->rep[r]);
+    stepped[r] = 1;
+  }
+  // It made the call's last step of every replica (FINAL step blocks): forces (pair + bonded) are in `forces`, velocities kicked;
+  // one fold block per replica adds its scratch rows (pair, bonded, kinetic) into the call's energy buffer and the context's
+  // kinetic-energy words (tmdhip_md_observe need not sum them) — `report`: one replica, and the same kernel reports them to the
+  // host (tmdhip_md_observe then only waits for the word)
+  int took_final(bool report) {
+    TMD_TRY(ctx->obs_ke.ensure(sizeof(double) * ctx->rep.size()));
+    if (report) {
+      TMD_TRY(publish_final_step(ctx, ctx->rep[0], d->energies_dev, st));
+    } else {
+      hipLaunchKernelGGL(final_fold_kernel, dim3(nrep), dim3(kEnergySlots), 0, st, ctx->escratch.as<double>(), d->energies_dev,
+                         ctx->obs_ke.as<double>());
+      TMD_HIP(hipGetLastError());
+    }
+    std::fill(finalized.begin(), finalized.end(), 1);
     ctx->ke_from_run = d->vel_dev;
     ctx->ke_from_run_mass = d->mass_dev;
     ctx->final_steps_in_pair_launch++;
+    return 0;
   }
 
   int finish_batch() {
@@ -926,24 +947,8 @@ struct MdRun {
       if (!reps.empty()) TMD_TRY(enqueue_chain_batch<float>(ctx, (int)reps.size(), reps.data(), ps.data(), par.data(), bx.data(), st));
     }
     TMD_TRY(launch_replica_batch(ctx, batch_items, batch_bonded, d->step0 + (uint64_t)it, want_e, langevin, st));
-    if (want_e) {
-      // the call's last step: forces (pair + bonded) in `forces`, velocities kicked; one fold block per replica adds its
-      // scratch rows (pair, bonded, kinetic) into the call's energy buffer and the context's kinetic-energy words
-      TMD_TRY(ctx->obs_ke.ensure(sizeof(double) * ctx->rep.size()));
-      hipLaunchKernelGGL(final_fold_kernel, dim3(nrep), dim3(kEnergySlots), 0, st, ctx->escratch.as<double>(), d->energies_dev,
-                         ctx->obs_ke.as<double>());
-      TMD_HIP(hipGetLastError());
-      for (int r = 0; r < nrep; ++r) finalized[r] = 1;
-      note_final_step();
-      return 0;
-    }
-    for (int r = 0; r < nrep; ++r) {
-      Replica &rp = ctx->rep[r];
-      cur[r] = batch_items[r].fl.step.pos_out;
-      std::swap(rp.sorted, rp.sorted_alt);
-      stepped[r] = 1;
-      rp.steps_in_pair_launch++;
-    }
+    if (want_e) return took_final(false);
+    for (int r = 0; r < nrep; ++r) took_step(r, batch_items[r].fl.step.pos_out);
     return 0;
   }
 

@@ -647,5 +647,55 @@ __global__ __launch_bounds__(kFastThreads, TMD_BATCH_WAVES) void list_pair_fast_
       S.padgen, qclass);
 }
 
+// ---- host side: from what a launch knows at run time to a kernel variant (both launchers; in the style of dispatch_lpa) ------
+// Every call below names a variant that gets compiled, and these variants are most of the library's build time: nothing here
+// may reach a combination that no launch can want.
+//
+// f(lj, el, sw, q), a std::bool_constant each, for the terms of a launch — exactly seven combinations: LJ + charges with the
+// charge products from the class table (QTAB; compiled out by TMD_CHARGE_TABLE = 0), LJ + charges, and LJ alone, each with and
+// without the LJ switching function, and charges alone, which have nothing to switch.
+template <typename F>
+inline void dispatch_pair_terms(bool lj, bool el, bool switch_on, bool qtab, F &&f) {
+  constexpr std::true_type T{};
+  constexpr std::false_type N{};
+  constexpr std::integral_constant<bool, TMD_CHARGE_TABLE != 0> Q{};
+  auto switched = [&](auto a, auto b, auto q) {
+    if (switch_on) f(a, b, T, q);
+    else f(a, b, N, q);
+  };
+  if (lj && el && qtab) switched(T, T, Q);
+  else if (lj && el) switched(T, T, N);
+  else if (lj) switched(T, N, N);
+  else f(N, T, N, N);
+}
+// f(std::integral_constant<int, FUSED>{}) for a launch with step blocks (pair_fast_body: FUSED).  Without energies: 1 an interior
+// step, 2 with the Langevin kick.  With energies: 3 / 4 the same for the last step of a call (FINAL step blocks), 5 a plain
+// evaluation, whose step blocks only add the bonded force.
+template <bool ENERGY, typename F>
+inline void dispatch_fused_mode(bool langevin, bool eval_only, F &&f) {
+  if constexpr (ENERGY) {
+    if (eval_only) f(std::integral_constant<int, 5>{});
+    else if (langevin) f(std::integral_constant<int, 4>{});
+    else f(std::integral_constant<int, 3>{});
+  } else {
+    if (langevin) f(std::integral_constant<int, 2>{});
+    else f(std::integral_constant<int, 1>{});
+  }
+}
+// f(std::integral_constant<int, LPA>{}) for the lanes per atom the lean kernel is built for; false (and no call) for any other
+template <typename F>
+inline bool dispatch_fast_lpa(int lpa, F &&f) {
+  switch (lpa) {
+    case 8: f(std::integral_constant<int, 8>{}); return true;
+#ifndef TMD_DEV_LPA8_ONLY  // (developer builds: one lanes-per-atom variant compiles in a fifth of the time)
+    case 4: f(std::integral_constant<int, 4>{}); return true;
+    case 16: f(std::integral_constant<int, 16>{}); return true;
+    case 32: f(std::integral_constant<int, 32>{}); return true;
+    case 64: f(std::integral_constant<int, 64>{}); return true;
+#endif
+    default: return false;
+  }
+}
+
 
 }  // namespace tmd
