@@ -23,6 +23,7 @@ import pytest
 import torch
 
 import _crescale as M
+import _reduce as RM
 from _golden import PREC, GoldenParameters, load
 
 pytestmark = pytest.mark.gpu
@@ -149,6 +150,41 @@ def test_kernel_against_model(prec):
     # two calls give the same bits
     again = _launch(prec, t)
     assert torch.equal(_bits(again[2]), _bits(p)) and torch.equal(_bits(again[3]), _bits(v)) and torch.equal(_bits(again[5]), _bits(rec))
+
+
+@pytest.mark.parametrize("prec", ["f32", "f64"])
+@pytest.mark.parametrize("N", RM.SHAPES)
+def test_partial_rows_and_record_bit_for_bit(N, prec):
+    """The order of the fixed-order sum (tests/_reduce.py): N molecules, three of more than 64 atoms (one wave each: the rows
+    behind those of the 256-thread blocks) and N - 3 of one atom, factors exactly 1 so that nothing is stored and K_after
+    follows the rule of K_before.  Every partial row and the record against the model, addition by addition.  The four wave
+    sums meet pairwise here."""
+    from torchmd_amd import _lib as L
+    from torchmd_amd import crescale as X
+
+    dev, dt = _dev(), PREC[prec]
+    off, natoms = RM.molecule_table(N)
+    mass, vel = RM.velocities(2, natoms, prec, 7)
+    p = torch.as_tensor(np.random.default_rng(8).uniform(-5.0, 45.0, (2, natoms, 3)), dtype=dt).to(dev).contiguous()
+    v = torch.as_tensor(vel, dtype=dt).to(dev).contiguous()
+    m = torch.as_tensor(mass, dtype=dt).to(dev)
+    nrec, npart = C.c_int64(), C.c_int64()
+    L.check(L.load().tmdhip_rescale_molecules_workspace(2, N, C.byref(nrec), C.byref(npart)), "workspace")
+    rec = torch.full((2, 2), float("nan"), dtype=torch.float64, device=dev)
+    part = torch.full((npart.value,), float("nan"), dtype=torch.float64, device=dev)
+    p0, v0 = p.clone(), v.clone()
+    X.rescale_molecules(p, v, m, np.ones((2, 3)), torch.as_tensor(off, device=dev), torch.arange(natoms, dtype=torch.int32, device=dev),
+                        True, rec, part)
+    torch.cuda.synchronize()
+    assert torch.equal(_bits(p), _bits(p0)) and torch.equal(_bits(v), _bits(v0))  # factors of 1: nothing is stored
+    nrows = (N + 255) // 256 + RM.BIG_BLOCKS
+    rows, K = part[: 2 * nrows * 2].cpu().numpy().reshape(2, nrows, 2), rec.cpu().numpy()
+    for r in range(2):
+        want = RM.crescale_rows(mass, vel[r], off, RM.PAIRWISE)
+        differ = int(((rows[r].view(np.int64) != want.view(np.int64)[:, None]).any(axis=1)).sum())
+        fold = 0.5 * RM.fold(want)
+        print(f"N = {N} {prec} replica {r}: {differ} of {nrows} partial rows differ from the model; K {K[r]!r}, model {fold!r}")
+        assert differ == 0 and K[r, 0] == fold and K[r, 1] == fold
 
 
 def test_c_refusals():

@@ -16,6 +16,7 @@ import pytest
 import torch
 
 import _exchange as M
+import _reduce as RM
 from _golden import PREC
 
 pytestmark = pytest.mark.gpu
@@ -150,6 +151,29 @@ def test_chunk_edge(prec):
     factors = np.sqrt((300.0 + 5.0 * np.arange(17)) / 340.0)
     assert factors[8] == 1.0 and len(set(factors)) == 17
     _against_model("chunk edge, R = 17, N = 300", prec, 17, 300, factors, 2, 3)
+
+
+@pytest.mark.parametrize("prec", ["f64", "f32"])
+@pytest.mark.parametrize("N", RM.SHAPES)
+def test_partial_rows_and_record_bit_for_bit(N, prec):
+    """The order of the fixed-order sum (tests/_reduce.py): every partial row exchange_reduce_kernel writes and the record's
+    K_before against the model, addition by addition.  The four wave sums meet in sequence here."""
+    mass, vel = RM.velocities(2, N, prec, 7)
+    on = mass > 0
+    factors = [1.0, np.sqrt(310.0 / 300.0)]
+    resc = _Rescaler(2)
+    resc.partials.fill_(float("nan"))
+    resc(_tensor(vel, prec), _tensor(mass, prec), factors)
+    rows = resc.partials.cpu().numpy().reshape(2, -1)
+    rec = resc.record.cpu().numpy()
+    nb = RM.nblocks_of(N)
+    for r in range(2):
+        want = RM.partial_rows(RM.mv2(mass, vel[r]), on, RM.SEQUENTIAL)
+        differ = int((rows[r, :nb].view(np.int64) != want.view(np.int64)).sum())
+        K = 0.5 * RM.fold(want)
+        print(f"N = {N} {prec} replica {r}: {differ} of {nb} partial rows differ from the model; K_before {rec[r, 0]!r}, model {K!r}")
+        assert differ == 0 and np.isnan(rows[r, nb:]).all()  # (rows past the grid are never written)
+        assert rec[r, 0] == K and rec[r, 2] == (factors[r] * factors[r]) * K
 
 
 def test_refusals_of_the_c_interface():

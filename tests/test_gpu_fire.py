@@ -10,6 +10,7 @@ import pytest
 import torch
 
 import _fire as M
+import _reduce as RM
 from _golden import GoldenParameters, PREC, load
 
 pytestmark = pytest.mark.gpu
@@ -129,6 +130,37 @@ def test_kernel_against_the_model(prec):
     assert st[0, 3] == 1 and st[0, 4] == 0  # replica 0: done at iteration 0
     assert st[1, 3] == 1 and 0 < st[1, 4] < NITER  # replica 1: converged mid-run
     assert run["worst"]["pos"] <= POS_BAR[prec], run["worst"]
+
+
+@pytest.mark.parametrize("prec", ["f64", "f32"])
+@pytest.mark.parametrize("N", RM.SHAPES)
+def test_partial_rows_and_state_bit_for_bit(N, prec):
+    """The order of the fixed-order sum (tests/_reduce.py): every partial row fire_reduce_kernel writes (the max column and the
+    three sums) against the model, addition by addition, and the state's F_max = sqrt of the folded max.  The four wave sums
+    meet in sequence here."""
+    from torchmd_amd import _lib as L
+
+    lib, dev = L.load(), _dev()
+    mass, vel = RM.velocities(2, N, prec, 7)
+    frc = RM.forces(2, N, prec, 7)
+    on = mass > 0
+    p, v, f, m = (torch.as_tensor(a, dtype=PREC[prec]).to(dev).contiguous() for a in (np.zeros_like(vel), vel, frc, mass))
+    state = torch.zeros((2, 2, L.FIRE_STATE_DOUBLES), dtype=torch.float64, device=dev)
+    partials = torch.full((2, L.FIRE_MAX_BLOCKS, 4), float("nan"), dtype=torch.float64, device=dev)
+    lp = _lib_params(M.Params(f_tol=1e-3, dt_start=0.02, dt_max=0.2, max_step=0.1))
+    L.check(lib.tmdhip_fire_init(2, state.data_ptr(), C.byref(lp), _stream()), "tmdhip_fire_init")
+    L.check(lib.tmdhip_fire_step(L.dtype_code(p.dtype), 2, N, p.data_ptr(), v.data_ptr(), f.data_ptr(), m.data_ptr(), state.data_ptr(),
+                                 partials.data_ptr(), C.byref(lp), 0, _stream()), "tmdhip_fire_step")
+    rows, new = partials.cpu().numpy(), state[:, 1].cpu().numpy()
+    nb = RM.nblocks_of(N)
+    for r in range(2):
+        cols = RM.fire_columns(vel[r], frc[r])
+        want = np.stack([RM.partial_rows(c, on, RM.SEQUENTIAL, op) for c, op in zip(cols, RM.FIRE_OPS)], axis=1)
+        differ = int((rows[r, :nb].view(np.int64) != want.view(np.int64)).any(axis=1).sum())
+        fmax = np.sqrt(RM.fold(want[:, 0], np.fmax))
+        print(f"N = {N} {prec} replica {r}: {differ} of {nb} partial rows differ from the model; F_max {new[r, 5]!r}, model {fmax!r}")
+        assert differ == 0 and np.isnan(rows[r, nb:]).all()  # (rows past the grid are never written)
+        assert new[r, 5] == fmax == np.sqrt(cols[0][on].max()) and new[r, 4] == 1
 
 
 @pytest.mark.parametrize("prec", ["f64", "f32"])

@@ -17,6 +17,7 @@ import numpy as np
 import pytest
 import torch
 
+import _reduce as RM
 import _thermostat as M
 from _golden import PREC
 
@@ -188,6 +189,28 @@ def test_stride_loop(prec):
     vel_err = float(np.abs(got[:, on] - vel[:, on]).max() / np.abs(vel[:, on]).max())
     assert not np.array_equal(got[0, on][-1], vel0[0, on][-1])  # (the last atom was reached)
     _report("stride loop, N = 70 001", prec, worst, vel_err)
+
+
+@pytest.mark.parametrize("prec", ["f64", "f32"])
+@pytest.mark.parametrize("N", RM.SHAPES)
+def test_partial_rows_and_record_bit_for_bit(N, prec):
+    """The order of the fixed-order sum (tests/_reduce.py): every partial row thermostat_reduce_kernel writes (five columns) and
+    the record's K_before against the model, addition by addition.  The four wave sums meet in sequence here.  The centre of
+    mass stays in, so that K_before is half the folded sum of m v^2 and nothing else (what csvr_kinetic of thermostat_math.h
+    subtracts for it is arithmetic behind the sum, which the compiler may contract)."""
+    mass, vel = RM.velocities(2, N, prec, 7)
+    on = mass > 0
+    th = _thermostat((300.0, 310.0), tau=0.05, frequency=10, remove_com=False, seed=12)
+    th.apply(_sys(vel, prec), _mass_t(mass, prec), 1.0 / M.TIMEFACTOR, 3 * int(on.sum()))
+    rows = th._partials.cpu().numpy().reshape(2, -1, 5)
+    rec = th._record.cpu().numpy()
+    nb = RM.nblocks_of(N)
+    for r in range(2):
+        want = np.stack([RM.partial_rows(c, on, RM.SEQUENTIAL) for c in RM.thermostat_columns(mass, vel[r])], axis=1)
+        differ = int((rows[r, :nb].view(np.int64) != want.view(np.int64)).any(axis=1).sum())
+        K = 0.5 * RM.fold(want[:, 4])
+        print(f"N = {N} {prec} replica {r}: {differ} of {nb} partial rows differ from the model; K_before {rec[r, 0]!r}, model {K!r}")
+        assert differ == 0 and rec[r, 0] == K and rec[r, 3] == 0.0
 
 
 # ----------------------------------------------------------------------------- 3. edges

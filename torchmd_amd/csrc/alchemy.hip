@@ -8,7 +8,7 @@
 //   cross   every pair (i in S, j in E) inside the engine's cutoff (min_image, norm2, r2max of pair_math.h): soft-core
 //           Lennard-Jones and lambda_elec times the engine's electrostatics, with dU/dlambda in the same pass
 //   intra   the non-excluded S-S pairs at full strength and the charge part of the solute's 1-4 pairs
-// Kernels (one wave per block, blockIdx.z or .y = replica of the launch, kChunk replicas per launch):
+// Kernels (one wave per block, blockIdx.z or .y = replica of the launch, kSideChunk replicas per launch):
 //   bounds  one wave per replica: a sphere (centre, radius) around the solute, for the early-outs
 //   env     lanes are the atoms of the system; the solute's records stream from LDS as broadcasts; a lane that stands for an
 //           environment atom sums its own force in double and is its only writer.  A wave none of whose atoms lies within
@@ -19,7 +19,7 @@
 //           are evaluated, the energy is counted by the lower index), a butterfly adds them in one fixed order, and lane 0 is
 //           the only writer of the atom.  (One thread per atom, restraint.hip's scheme, is a chain of dependent loads as long
 //           as the split count: 267 us per application on the 98 304-atom box with a 30-atom solute, against 6 us.)
-//   fold    one wave per replica folds the blocks' partial sums in one fixed order
+//   fold    one wave per replica folds the blocks' partial sums: fixed-order sum (reduce.h) of one-wave blocks
 // env and close serve whatever pointer is not null, like restraint_kernel: forces += F, vel += kick F / m (rows with m <= 0 are
 // left alone), or both.  Rows of environment atoms with no solute atom inside the cutoff are never written.  Distances and pair
 // functions are in the context's precision; every sum over partners, the energies and the derivatives are double.  There is no
@@ -42,14 +42,13 @@ using namespace tmd;
 namespace {
 
 constexpr int kTile = 64;
-constexpr int kChunk = 16;        // replicas served by one launch
 constexpr int kWantWaves = 2048;  // of the solute pass: a wave walks its chunk serially, so short chunks (measured: DESIGN §22)
 constexpr int kMaxStates = 32;    // of one tmdhip_alchemical_states call
 
 struct ChunkArgs {  // per replica of a launch: box, 1 / box (0: no image along the axis), its coupling, where its positions live
-  double box[kChunk][3], invbox[kChunk][3];
-  double lam_v[kChunk], lam_e[kChunk];
-  const void *pos[kChunk];
+  double box[kSideChunk][3], invbox[kSideChunk][3];
+  double lam_v[kSideChunk], lam_e[kSideChunk];
+  const void *pos[kSideChunk];
 };
 
 struct StateArgs {
@@ -192,24 +191,12 @@ __global__ __launch_bounds__(kTile) void alch_env_kernel(Tables<R> T, AlchConsts
     }
   }
   if (touched) {
-    const size_t at = ((size_t)blockIdx.y * T.n + i) * 3;
-    if (forces) {
-      forces[at] = (R)((double)forces[at] + fx);
-      forces[at + 1] = (R)((double)forces[at + 1] + fy);
-      forces[at + 2] = (R)((double)forces[at + 2] + fz);
-    }
-    if (vel) {
-      const double m = (double)mass[i];
-      if (m > 0.0) {
-        vel[at] = (R)((double)vel[at] + kick * fx / m);
-        vel[at + 1] = (R)((double)vel[at + 1] + kick * fy / m);
-        vel[at + 2] = (R)((double)vel[at + 2] + kick * fz / m);
-      }
-    }
+    const double f[3] = {fx, fy, fz};
+    side_store(forces, vel, ((size_t)blockIdx.y * T.n + i) * 3, mass, i, kick, f);
   }
   if (!eo) return;  // (uniform: a kernel argument)
-  const double a = wave_sum(slj), b = wave_sum(sgel), d = wave_sum(sdv);
-  if (lane == 0) eo[0] = a, eo[1] = b, eo[2] = d;
+  const double e[3] = {slj, sgel, sdv};
+  block_sums<1, Meet::Pairwise>(e, eo);
 }
 
 // Lanes are solute atoms (grid.x = ceil(ns / 64), grid.y = splits of the system, grid.z = replicas of the launch).
@@ -299,14 +286,7 @@ __global__ __launch_bounds__(kTile) void alch_close_kernel(Tables<R> T, AlchCons
   f[0] = wave_sum(f[0]), f[1] = wave_sum(f[1]), f[2] = wave_sum(f[2]);
   e_intra = wave_sum(e_intra);
   if (lane != 0) return;
-  const size_t at = ((size_t)blockIdx.y * T.n + a) * 3;
-  if (forces)
-    for (int k = 0; k < 3; ++k) forces[at + k] = (R)((double)forces[at + k] + f[k]);
-  if (vel) {
-    const double m = (double)mass[a];
-    if (m > 0.0)
-      for (int k = 0; k < 3; ++k) vel[at + k] = (R)((double)vel[at + k] + kick * f[k] / m);
-  }
+  side_store(forces, vel, ((size_t)blockIdx.y * T.n + a) * 3, mass, a, kick, f);
   if (epart) epart[(size_t)r * gridDim.x + t] = e_intra;
 }
 
@@ -315,16 +295,13 @@ __global__ __launch_bounds__(64) void alch_fold_kernel(const double *__restrict_
                                                        ChunkArgs P, int rep0, double *__restrict__ out) {
 #pragma clang fp contract(off)
   const int r = rep0 + blockIdx.x;
-  double a = 0.0, b = 0.0, d = 0.0, e = 0.0;
-  for (int k = threadIdx.x; k < nbA; k += 64) {
-    const double *p = epartA + 3 * ((size_t)r * nbA + k);
-    a += p[0], b += p[1], d += p[2];
-  }
-  for (int k = threadIdx.x; k < nbS; k += 64) e += epartC[(size_t)r * nbS + k];
-  a = wave_sum(a), b = wave_sum(b), d = wave_sum(d), e = wave_sum(e);
+  double x[3] = {0.0, 0.0, 0.0}, e[1] = {0.0};  // cross: LJ, qq g, dU/dlv; intra
+  fold_into(x, epartA + 3 * (size_t)r * nbA, nbA);
+  fold_into(e, epartC + (size_t)r * nbS, nbS);
+  x[0] = wave_sum(x[0]), x[1] = wave_sum(x[1]), x[2] = wave_sum(x[2]), e[0] = wave_sum(e[0]);
   if (threadIdx.x == 0) {
     double *o = out + 5 * (size_t)r;
-    o[0] = a, o[1] = P.lam_e[blockIdx.x] * b, o[2] = e, o[3] = d, o[4] = b;
+    o[0] = x[0], o[1] = P.lam_e[blockIdx.x] * x[1], o[2] = e[0], o[3] = x[2], o[4] = x[1];
   }
 }
 
@@ -402,15 +379,11 @@ __global__ __launch_bounds__(64) void alch_states_fold_kernel(const double *__re
                                                               double *__restrict__ sout) {
 #pragma clang fp contract(off)
   const int r = rep0 + blockIdx.x, k = blockIdx.y;
-  double g = 0.0, a = 0.0;
-  for (int b = threadIdx.x; b < nbA; b += 64) {
-    const double *p = spart + (kMaxStates + 1) * ((size_t)r * nbA + b);
-    g += p[kMaxStates];
-    a += p[k];
-  }
-  g = wave_sum(g);
-  a = wave_sum(a);
-  if (threadIdx.x == 0) sout[(size_t)r * kMaxStates + k] = a + S.lam_e[k] * g;
+  const double *rows = spart + (kMaxStates + 1) * (size_t)r * nbA;
+  double g[1] = {0.0}, a[1] = {0.0};
+  fold_into<kMaxStates + 1, Sum, Sum>(g, rows + kMaxStates, a, rows + k, nbA);
+  g[0] = wave_sum(g[0]), a[0] = wave_sum(a[0]);
+  if (threadIdx.x == 0) sout[(size_t)r * kMaxStates + k] = a[0] + S.lam_e[k] * g[0];
 }
 
 template <typename R>
@@ -438,7 +411,7 @@ template <typename R>
 ChunkArgs chunk_of(const AlchState *S, int rep_first, int nr, const void *pos, const void *const *pos_each, int c0, const double *box_host) {
   ChunkArgs P;
   const size_t stride = (size_t)S->natoms * 3;
-  for (int r = 0; r < kChunk; ++r) {
+  for (int r = 0; r < kSideChunk; ++r) {
     const bool live = r < nr;
     const double *b = box_host + 3 * (c0 + r);
     const bool allzero = !live || (b[0] == 0 && b[1] == 0 && b[2] == 0);
@@ -449,7 +422,7 @@ ChunkArgs chunk_of(const AlchState *S, int rep_first, int nr, const void *pos, c
     }
     P.lam_v[r] = live ? S->lam_v[rep_first + r] : 1.0;
     P.lam_e[r] = live ? S->lam_e[rep_first + r] : 1.0;
-    P.pos[r] = !live ? nullptr : pos_each ? pos_each[c0 + r] : (const void *)((const R *)pos + (c0 + r) * stride);
+    P.pos[r] = live ? side_pos(pos, pos_each, c0 + r, stride * sizeof(R)) : nullptr;
   }
   return P;
 }
@@ -466,8 +439,8 @@ int launch(tmdhip_ctx *ctx, AlchState *S, int rep0, int nrep, const void *pos, c
   const bool sphere = S->sphere && std::isfinite((double)c.r2max);
   const double *sph = sphere ? S->sph.as<double>() : nullptr;
   const dim3 block(kTile);
-  for (int c0 = 0; c0 < nrep; c0 += kChunk) {
-    const int nr = std::min(kChunk, nrep - c0), r0 = rep0 + c0;
+  for (int c0 = 0; c0 < nrep; c0 += kSideChunk) {
+    const int nr = std::min(kSideChunk, nrep - c0), r0 = rep0 + c0;
     const ChunkArgs P = chunk_of<R>(S, r0, nr, pos, pos_each, c0, box_host);
     R *f = forces ? (R *)forces + c0 * stride : nullptr, *v = vel ? (R *)vel + c0 * stride : nullptr;
     if (sphere) hipLaunchKernelGGL(alch_bounds_kernel<R>, dim3((unsigned)nr), block, 0, st, T, P, r0, S->sph.as<double>());
@@ -514,8 +487,8 @@ int launch_states(tmdhip_ctx *ctx, AlchState *S, const void *pos, const double *
   const Tables<R> T = tables_of<R>(ctx, S);
   const bool sphere = S->sphere && std::isfinite((double)c.r2max);
   const double *sph = sphere ? S->sph.as<double>() : nullptr;
-  for (int c0 = 0; c0 < S->nrep; c0 += kChunk) {
-    const int nr = std::min(kChunk, S->nrep - c0);
+  for (int c0 = 0; c0 < S->nrep; c0 += kSideChunk) {
+    const int nr = std::min(kSideChunk, S->nrep - c0);
     const ChunkArgs P = chunk_of<R>(S, c0, nr, pos, nullptr, c0, box_host);
     if (sphere) hipLaunchKernelGGL(alch_bounds_kernel<R>, dim3((unsigned)nr), dim3(kTile), 0, st, T, P, c0, S->sph.as<double>());
     hipLaunchKernelGGL(alch_states_kernel<R>, dim3((unsigned)S->nbA, (unsigned)nr), dim3(kTile), 0, st, T, c, P, c0, A, sph,
@@ -674,7 +647,7 @@ int tmdhip_set_alchemical(tmdhip_ctx *ctx, const tmdhip_alchemical_desc *desc) {
   S->nbS = (ns + kTile - 1) / kTile;
   const char *forced = std::getenv("TMDHIP_ALCHEMY_NSPLIT"), *sphere = std::getenv("TMDHIP_ALCHEMY_SPHERE");
   S->sphere = sphere && std::atoi(sphere) != 0;
-  const int want = forced && std::atoi(forced) > 0 ? std::atoi(forced) : kWantWaves / std::max(S->nbS * std::min(nrep, kChunk), 1);
+  const int want = forced && std::atoi(forced) > 0 ? std::atoi(forced) : kWantWaves / std::max(S->nbS * std::min(nrep, kSideChunk), 1);
   const int ns0 = std::max(1, std::min(want, S->nbA));
   S->jchunk = ((n + ns0 - 1) / ns0 + kTile - 1) / kTile * kTile;
   S->nsplit = (n + S->jchunk - 1) / S->jchunk;

@@ -48,6 +48,10 @@ struct Vec<double> {
 
 constexpr int kWave = 64;  // CDNA wavefront
 
+// replicas served by one launch of a side term (engine.h) or a scheduled control: their per-replica arguments travel as kernel
+// arguments, so there is no device parameter array and no host-to-device copy
+constexpr int kSideChunk = 16;
+
 // Coulomb constant in kcal/mol*A/e^2 — value the reference derives from scipy.constants
 // (torchmd/forces.py:375-378).
 constexpr double kElecFactor = 332.06371307417066;

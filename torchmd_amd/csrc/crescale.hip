@@ -15,9 +15,8 @@
 //   rescale_molecules_kernel  pass 1: sum m, sum m x, sum m v in double, members in index order, and sum m v^2 over the ATOMS
 //                             as they are; pass 2: x and v written back in the context's precision (one rounding), and
 //                             sum m v^2 of the velocities as stored.  Per-block partials [2] of both sums.
-//   rescale_fold_kernel       one wave per replica (the scheme of virial_fold_kernel): lane l takes the partials l, l + 64, ...,
-//                             then the butterfly; writes double [R][2] = (K_before, K_after).
-// No floating-point atomics, every sum in one fixed order: two calls on the same state give the same bits.
+//   rescale_fold_kernel       one wave per replica folds the partials; writes double [R][2] = (K_before, K_after).
+// Fixed-order sum (reduce.h), the wave sums meet pairwise: two calls on the same state give the same bits.
 //
 // Edge cases:
 //   a replica whose three factors are exactly 1   neither positions nor velocities are written; its two K entries are
@@ -41,11 +40,10 @@ using namespace tmd;
 namespace {
 
 constexpr int kThreads = 256;
-constexpr int kChunk = 16;   // replicas served by one launch (their factors travel as kernel arguments)
 constexpr int kBigMol = 64;  // more atoms than this: one wave per molecule
 
 struct ScaleArgs {
-  double s[kChunk][3];
+  double s[kSideChunk][3];
 };
 
 constexpr int kBigBlocks = 64;  // one-wave blocks per replica that share the molecules of more than kBigMol atoms
@@ -145,29 +143,22 @@ __global__ __launch_bounds__(kThreads) void rescale_molecules_kernel(int natoms,
       move_molecule<R, true>(natoms, mem, p, v, mass, s, write, off[g] + (int)threadIdx.x, off[g + 1], kb, ka);
     }
   }
-  kb = wave_sum(kb), ka = wave_sum(ka);
+  const double k[2] = {kb, ka};
   double *dst = partials + ((size_t)r * prows + (big_pass ? small_blocks_of(nmol) + blockIdx.x : blockIdx.x)) * 2;
   if (big_pass) {
-    if (threadIdx.x == 0) dst[0] = kb, dst[1] = ka;
-    return;
+    block_sums<1, Meet::Pairwise>(k, dst);
+  } else {
+    block_sums<kThreads / 64, Meet::Pairwise>(k, dst);
   }
-  __shared__ double part[kThreads / 64][2];
-  if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6][0] = kb, part[threadIdx.x >> 6][1] = ka;
-  __syncthreads();
-  if (threadIdx.x < 2) dst[threadIdx.x] = (part[0][threadIdx.x] + part[1][threadIdx.x]) + (part[2][threadIdx.x] + part[3][threadIdx.x]);
 }
 
-// one wave per replica: lane l takes the partial rows l, l + 64, ... of the `nrows` that were written, then the butterfly
+// one wave per replica folds the `nrows` partial rows that were written
 __global__ __launch_bounds__(64) void rescale_fold_kernel(const double *__restrict__ partials, int prows, int nrows, double *__restrict__ record) {
 #pragma clang fp contract(off)
   const int r = blockIdx.x;
-  double kb = 0, ka = 0;
-  for (int b = threadIdx.x; b < nrows; b += 64) {
-    kb += partials[((size_t)r * prows + b) * 2];
-    ka += partials[((size_t)r * prows + b) * 2 + 1];
-  }
-  kb = wave_sum(kb), ka = wave_sum(ka);
-  if (threadIdx.x == 0) record[2 * (size_t)r] = 0.5 * kb, record[2 * (size_t)r + 1] = 0.5 * ka;
+  double k[2];
+  fold_rows(partials + (size_t)r * prows * 2, nrows, k);
+  if (threadIdx.x == 0) record[2 * (size_t)r] = 0.5 * k[0], record[2 * (size_t)r + 1] = 0.5 * k[1];
 }
 
 // the workspace: double [R][prows][2] of partials, then int [nmol + 1]: the list of big molecules and its length
@@ -179,10 +170,10 @@ int rescale(int64_t nreplicas, int n, void *pos, void *vel, const void *mass, co
   const int small = small_blocks_of(nmol), prows = (int)partial_rows(nmol);
   int *big = (int *)(partials + (size_t)nreplicas * prows * 2);
   if (has_big) hipLaunchKernelGGL(big_list_kernel, dim3(1), dim3(64), 0, st, nmol, off, big);
-  for (int64_t r0 = 0; r0 < nreplicas; r0 += kChunk) {
-    const int nr = (int)std::min<int64_t>(kChunk, nreplicas - r0);
+  for (int64_t r0 = 0; r0 < nreplicas; r0 += kSideChunk) {
+    const int nr = (int)std::min<int64_t>(kSideChunk, nreplicas - r0);
     ScaleArgs S;
-    for (int r = 0; r < kChunk; ++r)
+    for (int r = 0; r < kSideChunk; ++r)
       for (int k = 0; k < 3; ++k) S.s[r][k] = r < nr ? scale_host[3 * (r0 + r) + k] : 1.0;
     hipLaunchKernelGGL((rescale_molecules_kernel<R>), dim3((unsigned)small, (unsigned)nr), dim3(kThreads), 0, st, n, nmol, off, mem,
                        (const int *)big, (R *)pos, (R *)vel, (const R *)mass, S, (int)r0, partials, prows, 0);

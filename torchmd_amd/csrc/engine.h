@@ -597,6 +597,41 @@ struct SideTerm {
   void (*release)(tmdhip_ctx *ctx);
 };
 
+// What a side term's kernel does with the force f on one atom (its only writer), `at` the atom's offset in the launch's rows:
+// forces += f with one rounding; vel += kick f / m with one rounding, for an atom with mass only.  Whatever pointer is not null
+// is served.  (No multiply-add in either expression: contraction cannot change them.)
+template <typename R>
+__device__ __forceinline__ void side_store(R *__restrict__ forces, R *__restrict__ vel, size_t at, const R *__restrict__ mass, int atom,
+                                           double kick, const double (&f)[3]) {
+#pragma clang fp contract(off)
+  if (forces)
+    for (int c = 0; c < 3; ++c) forces[at + c] = (R)((double)forces[at + c] + f[c]);
+  if (vel) {
+    const double m = (double)mass[atom];
+    if (m > 0.0)
+      for (int c = 0; c < 3; ++c) vel[at + c] = (R)((double)vel[at + c] + kick * f[c] / m);
+  }
+}
+
+// where replica c0 + r of a launch's chunk (kSideChunk replicas, common.h) has its positions: SideTerm::launch's pos / pos_each
+inline const void *side_pos(const void *pos, const void *const *pos_each, int r, size_t stride_bytes) {
+  return pos_each ? pos_each[r] : (const void *)((const char *)pos + r * stride_bytes);
+}
+
+// per replica of a launch: its box and where its positions live (real [N][3]); box_host: the box of the launch's first replica
+struct SideChunk {
+  double box[kSideChunk][3];
+  const void *pos[kSideChunk];
+};
+inline SideChunk side_chunk(int nr, int c0, const void *pos, const void *const *pos_each, const double *box_host, size_t stride_bytes) {
+  SideChunk B;
+  for (int r = 0; r < kSideChunk; ++r) {
+    for (int k = 0; k < 3; ++k) B.box[r][k] = r < nr ? box_host[3 * (c0 + r) + k] : 0.0;
+    B.pos[r] = r < nr ? side_pos(pos, pos_each, c0 + r, stride_bytes) : nullptr;
+  }
+  return B;
+}
+
 }  // namespace tmd
 
 struct tmdhip_ctx {

@@ -5,19 +5,17 @@
 // calls to velocities that are in memory; the factors come from the host, so nothing is read back.
 //
 // Two launches per application, blockIdx.y = replica (the shape of thermostat.hip):
-//   exchange_reduce_kernel  per block: sum m v^2 over its atoms with mass > 0 -> partials[r][block], a plain double stored by
-//                           one thread
-//   exchange_update_kernel  every thread writes v <- factor v for its atom; wave 0 of block 0 sums the partials of its replica
-//                           in one fixed order (lane l takes blocks l, l + 64, ..., then the xor butterfly) and its thread 0
-//                           writes the replica's record.  (The factor is given, not derived from the sum as the thermostat's
-//                           alpha is, so no other block needs the sum.)
-// No floating-point atomics: two runs give the same bits.  The sum and the record arithmetic in double in both precisions,
+//   exchange_reduce_kernel  per block: sum m v^2 over its atoms with mass > 0 -> partials[r][block]
+//   exchange_update_kernel  every thread writes v <- factor v for its atom; wave 0 of block 0 folds the partials of its replica
+//                           and its thread 0 writes the replica's record.  (The factor is given, not derived from the sum as
+//                           the thermostat's alpha is, so no other block needs the sum.)
+// Fixed-order sum (reduce.h), the wave sums meet in sequence.  The sum and the record arithmetic in double in both precisions,
 // contraction off; the new velocity is one IEEE product in double and one rounding on the store.
 //
 // Edge cases:
 //   factor == 1.0 exactly                 reduced and recorded (K_after = K_before), the velocities are not written at all
 //   rows with mass == 0 (virtual sites)   never read into a sum, never written: they keep their bits, NaNs included
-// The factors travel as kernel arguments, kChunk replicas per pair of launches (as tmdhip_thermostat_apply passes its
+// The factors travel as kernel arguments, kSideChunk replicas per pair of launches (as tmdhip_thermostat_apply passes its
 // parameters): no device parameter array, no host-to-device copy.
 // Streaming and HBM-bound: in fp32 the two passes read v and m twice (16 B/atom each) and write v (12 B/atom).
 #include <hip/hip_runtime.h>
@@ -35,11 +33,10 @@ namespace {
 constexpr int kThreads = 256;
 constexpr int kMaxBlocks = TMDHIP_EXCHANGE_MAX_BLOCKS;  // reduction blocks per replica = partials per replica
 constexpr int kRec = TMDHIP_EXCHANGE_RECORD_DOUBLES;
-constexpr int kChunk = 16;  // replicas served by one pair of launches
 enum { R_KBEFORE = 0, R_FACTOR, R_KAFTER, R_WORK, R_COUNT };
 
 struct ChunkArgs {
-  double factor[kChunk];
+  double factor[kSideChunk];
 };
 
 template <typename R>
@@ -55,11 +52,8 @@ __global__ __launch_bounds__(kThreads) void exchange_reduce_kernel(int natoms, c
     const double vx = v[3 * i], vy = v[3 * i + 1], vz = v[3 * i + 2];
     sum += m * (vx * vx + vy * vy + vz * vz);
   }
-  __shared__ double part[kThreads / 64];
-  const double t = wave_sum(sum);
-  if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = t;
-  __syncthreads();
-  if (threadIdx.x == 0) partials[(size_t)r * kMaxBlocks + blockIdx.x] = part[0] + part[1] + part[2] + part[3];
+  const double lane[1] = {sum};
+  block_sums<kThreads / 64, Meet::Sequential>(lane, partials + (size_t)r * kMaxBlocks + blockIdx.x);
 }
 
 template <typename R>
@@ -70,12 +64,11 @@ __global__ __launch_bounds__(kThreads) void exchange_update_kernel(int natoms, R
   const int r = replica0 + blockIdx.y;
   const double factor = A.factor[blockIdx.y];
   if (blockIdx.x == 0 && threadIdx.x < 64) {  // wave 0 of block 0: the record (no other block needs the sum)
-    double sum = 0.0;
-    for (int b = threadIdx.x; b < nblocks; b += 64) sum += partials[(size_t)r * kMaxBlocks + b];
-    sum = wave_sum(sum);
+    double sum[1];
+    fold_rows(partials + (size_t)r * kMaxBlocks, nblocks, sum);
     if (threadIdx.x == 0) {
       double *rec = record + (size_t)r * kRec;
-      const double K = 0.5 * sum;
+      const double K = 0.5 * sum[0];
       const double after = (factor * factor) * K;
       rec[R_KBEFORE] = K;
       rec[R_FACTOR] = factor;
@@ -96,10 +89,10 @@ template <typename R>
 int rescale(int64_t nreplicas, int n, void *vel, const void *mass, const double *factor, double *record, double *partials,
             hipStream_t st) {
   const int nupdate = (n + kThreads - 1) / kThreads, nreduce = std::min(nupdate, kMaxBlocks);
-  for (int64_t r0 = 0; r0 < nreplicas; r0 += kChunk) {
-    const int nr = (int)std::min<int64_t>(kChunk, nreplicas - r0);
+  for (int64_t r0 = 0; r0 < nreplicas; r0 += kSideChunk) {
+    const int nr = (int)std::min<int64_t>(kSideChunk, nreplicas - r0);
     ChunkArgs A;
-    for (int r = 0; r < kChunk; ++r) A.factor[r] = r < nr ? factor[r0 + r] : 1.0;
+    for (int r = 0; r < kSideChunk; ++r) A.factor[r] = r < nr ? factor[r0 + r] : 1.0;
     hipLaunchKernelGGL(exchange_reduce_kernel<R>, dim3((unsigned)nreduce, (unsigned)nr), dim3(kThreads), 0, st, n, (const R *)vel,
                        (const R *)mass, partials, (int)r0);
     hipLaunchKernelGGL(exchange_update_kernel<R>, dim3((unsigned)nupdate, (unsigned)nr), dim3(kThreads), 0, st, n, (R *)vel,

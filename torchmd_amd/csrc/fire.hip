@@ -4,10 +4,10 @@
 //
 // Two launches per iteration, blockIdx.y = replica:
 //   fire_reduce_kernel  per block: max |F_i|^2, sum F.v, sum v.v, sum F.F over its atoms with mass > 0 -> partials[r][block][4]
-//   fire_update_kernel  every block re-sums the partials of its replica in one fixed order (so all blocks see the same bits),
-//                       derives the new state from the state slot `iteration & 1`, moves its atoms; thread 0 of block 0 stores the
-//                       new state into the other slot.  No block can read a half-written state, and no floating-point atomics:
-//                       two runs give the same bits.
+//   fire_update_kernel  wave 0 of every block folds the partials of its replica (so all blocks see the same bits), derives the
+//                       new state from the state slot `iteration & 1`, moves its atoms; thread 0 of block 0 stores the new
+//                       state into the other slot.  No block can read a half-written state.
+// Fixed-order sum (reduce.h), the wave sums meet in sequence (the maxima pairwise: any order gives the same bits).
 // All sums and all state arithmetic in double in both precisions, contraction off, one rounding on the store of vel and pos.
 // Rows with mass == 0 (virtual sites) are neither read into a sum nor written.  A replica whose state says `done` is not
 // written at all (its state is copied to the other slot), so its positions stay bit for bit those at convergence.
@@ -39,12 +39,6 @@ __global__ void fire_init_kernel(int nreplicas, double *__restrict__ state, doub
   }
 }
 
-__device__ __forceinline__ double wave_max(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o, 64));
-  return v;
-}
-
 template <typename R>
 __global__ __launch_bounds__(kThreads) void fire_reduce_kernel(int natoms, const R *__restrict__ vel, const R *__restrict__ frc,
                                                                const R *__restrict__ mass, const double *__restrict__ state,
@@ -53,28 +47,20 @@ __global__ __launch_bounds__(kThreads) void fire_reduce_kernel(int natoms, const
   const int r = blockIdx.y;
   if (state[((size_t)r * 2 + slot) * kSlot + S_DONE] != 0.0) return;  // (the update pass does not read the partials then)
   const R *v = vel + (size_t)r * natoms * 3, *f = frc + (size_t)r * natoms * 3;
-  double f2max = 0, p = 0, vv = 0, ff = 0;
+  double f2max[1] = {0}, s[3] = {0, 0, 0};  // F.v, v.v, F.F
   for (int i = blockIdx.x * kThreads + threadIdx.x; i < natoms; i += gridDim.x * kThreads) {
     if (!(mass[i] > R(0))) continue;
     const double fx = f[3 * i], fy = f[3 * i + 1], fz = f[3 * i + 2];
     const double vx = v[3 * i], vy = v[3 * i + 1], vz = v[3 * i + 2];
     const double f2 = fx * fx + fy * fy + fz * fz;
-    f2max = fmax(f2max, f2);
-    p += fx * vx + fy * vy + fz * vz;
-    vv += vx * vx + vy * vy + vz * vz;
-    ff += f2;
+    f2max[0] = fmax(f2max[0], f2);
+    s[0] += fx * vx + fy * vy + fz * vz;
+    s[1] += vx * vx + vy * vy + vz * vz;
+    s[2] += f2;
   }
-  f2max = wave_max(f2max), p = wave_sum(p), vv = wave_sum(vv), ff = wave_sum(ff);
-  __shared__ double part[kThreads / 64][4];
-  const int w = threadIdx.x >> 6;
-  if ((threadIdx.x & 63) == 0) part[w][0] = f2max, part[w][1] = p, part[w][2] = vv, part[w][3] = ff;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    double *out = partials + ((size_t)r * kMaxBlocks + blockIdx.x) * 4;
-    out[0] = fmax(fmax(part[0][0], part[1][0]), fmax(part[2][0], part[3][0]));
-#pragma unroll
-    for (int k = 1; k < 4; ++k) out[k] = part[0][k] + part[1][k] + part[2][k] + part[3][k];
-  }
+  double *out = partials + ((size_t)r * kMaxBlocks + blockIdx.x) * 4;
+  block_sums<kThreads / 64, Meet::Pairwise, 1, Max>(f2max, out);
+  block_sums<kThreads / 64, Meet::Sequential>(s, out + 1);
 }
 
 // what every thread of a block needs from the new state
@@ -100,13 +86,11 @@ __global__ __launch_bounds__(kThreads) void fire_update_kernel(int natoms, R *__
     Move m;
     m.dt = s[S_DT], m.keep = 0, m.mix = 0, m.frozen = 1;
     if (s[S_DONE] == 0.0) {
-      double f2max = 0, p = 0, vv = 0, ff = 0;
-      for (int b = threadIdx.x; b < nblocks; b += 64) {
-        const double *q = partials + ((size_t)r * kMaxBlocks + b) * 4;
-        f2max = fmax(f2max, q[0]), p += q[1], vv += q[2], ff += q[3];
-      }
-      f2max = wave_max(f2max), p = wave_sum(p), vv = wave_sum(vv), ff = wave_sum(ff);
-      s[S_FMAX] = sqrt(f2max);
+      const double *rows = partials + (size_t)r * kMaxBlocks * 4;
+      double f2max[1] = {0}, sum[3] = {0, 0, 0};
+      fold_into<4, Max, Sum>(f2max, rows, sum, rows + 1, nblocks);
+      const double p = wave_sum(sum[0]), vv = wave_sum(sum[1]), ff = wave_sum(sum[2]);
+      s[S_FMAX] = sqrt(wave_max(f2max[0]));
       if (s[S_FMAX] < prm.f_tol) {
         s[S_DONE] = 1.0;
       } else {

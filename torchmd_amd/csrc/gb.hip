@@ -11,8 +11,8 @@
 // Every pair is visited from both sides: twice the arithmetic, but every (i, split) has one writer, the closes add the splits
 // in index order, and there is no floating-point atomic anywhere: two calls on the same state return the same bits.
 // d, r and the per-pair functions are formed in the context's precision (fp32: full-precision expf / logf / sqrtf, IEEE
-// division); every sum over j, the closes and the energies are double.  Energies: per block the wave's butterfly sum, then one
-// wave per replica folds the partials in one fixed order (lane l takes partials l, l + 64, ..., then the butterfly).
+// division); every sum over j, the closes and the energies are double.  Energies: fixed-order sum (reduce.h) of one-wave blocks,
+// then one wave per replica folds the partials.
 // nsplit: about 2048 waves per launch (two per SIMD of the 256 CUs), jchunk a multiple of the tile; TMDHIP_GB_NSPLIT (read by
 // tmdhip_set_gb) forces the split (tests).
 #include <hip/hip_runtime.h>
@@ -30,11 +30,10 @@ using namespace tmd;
 namespace {
 
 constexpr int kTile = 64;
-constexpr int kChunk = 16;  // replicas served by one launch
 constexpr int kWantWaves = 2048;
 
 struct ChunkPos {  // where the positions of each replica of a launch live (real [N][3])
-  const void *pos[kChunk];
+  const void *pos[kSideChunk];
 };
 
 struct GbState {
@@ -127,8 +126,8 @@ __global__ __launch_bounds__(kTile) void gb_energy_kernel(int n, int jchunk, Chu
     double *o = part2 + 4 * row;
     o[0] = bacc, o[1] = fx, o[2] = fy, o[3] = fz;
   }
-  const double s = wave_sum(i < n ? eacc : 0.0);
-  if (lane == 0) epart[(size_t)(rep0 + blockIdx.z) * estride + (size_t)blockIdx.y * gridDim.x + blockIdx.x] = s;
+  const double e[1] = {i < n ? eacc : 0.0};
+  block_sums<1, Meet::Pairwise>(e, epart + (size_t)(rep0 + blockIdx.z) * estride + (size_t)blockIdx.y * gridDim.x + blockIdx.x);
 }
 
 template <typename R>
@@ -190,16 +189,15 @@ __global__ __launch_bounds__(kTile) void gb_close_chain_kernel(int n, int nsplit
                                                                const double *__restrict__ born, const double *__restrict__ cfac,
                                                                R *__restrict__ b_r, double *__restrict__ epart, int estride, int eoff) {
   const int i = blockIdx.x * kTile + threadIdx.x, r = rep0 + blockIdx.y;
-  double esa = 0.0;
+  double esa[1] = {0.0};
   if (i < n) {
     double sum = 0.0;
     for (int s = 0; s < nsplit; ++s) sum += part2[4 * (((size_t)r * nsplit + s) * n + i)];
     double b;
-    esa = gb_close_chain(sum, radius[i], sa[i], born[(size_t)r * n + i], cfac[(size_t)r * n + i], b);
+    esa[0] = gb_close_chain(sum, radius[i], sa[i], born[(size_t)r * n + i], cfac[(size_t)r * n + i], b);
     b_r[(size_t)r * n + i] = (R)b;
   }
-  const double s = wave_sum(esa);
-  if (threadIdx.x == 0) epart[(size_t)r * estride + eoff + blockIdx.x] = s;
+  block_sums<1, Meet::Pairwise>(esa, epart + (size_t)r * estride + eoff + blockIdx.x);
 }
 
 // forces / vel: the rows of the launch's first replica (blockIdx.y counts from it)
@@ -218,14 +216,7 @@ __global__ __launch_bounds__(kTile) void gb_close_force_kernel(int n, int nsplit
     const double *a = part3 + 3 * (((size_t)r * nsplit + s) * n + i);
     for (int c = 0; c < 3; ++c) f[c] += a[c];
   }
-  const size_t at = ((size_t)blockIdx.y * n + i) * 3;
-  if (forces)
-    for (int c = 0; c < 3; ++c) forces[at + c] = (R)((double)forces[at + c] + f[c]);
-  if (vel) {
-    const double m = (double)mass[i];
-    if (m > 0.0)
-      for (int c = 0; c < 3; ++c) vel[at + c] = (R)((double)vel[at + c] + kick * f[c] / m);
-  }
+  side_store(forces, vel, ((size_t)blockIdx.y * n + i) * 3, mass, i, kick, f);
 }
 
 // one wave per replica (blockIdx.x counts from rep0): out[r] = ((1/2) sum of the pair partials, sum of the SA partials)
@@ -234,14 +225,13 @@ __global__ __launch_bounds__(64) void gb_fold_kernel(const double *__restrict__ 
 #pragma clang fp contract(off)
   const int r = rep0 + blockIdx.x;
   const double *e = epart + (size_t)r * estride;
-  double sg = 0.0, ss = 0.0;
-  for (int b = threadIdx.x; b < npair; b += 64) sg += e[b];
-  for (int b = npair + threadIdx.x; b < estride; b += 64) ss += e[b];
-  sg = wave_sum(sg);
-  ss = wave_sum(ss);
+  double sg[1] = {0.0}, ss[1] = {0.0};
+  fold_into(sg, e, npair);
+  fold_into(ss, e + npair, estride - npair);
+  sg[0] = wave_sum(sg[0]), ss[0] = wave_sum(ss[0]);
   if (threadIdx.x == 0) {
-    out[2 * (size_t)r] = 0.5 * sg;
-    out[2 * (size_t)r + 1] = ss;
+    out[2 * (size_t)r] = 0.5 * sg[0];
+    out[2 * (size_t)r + 1] = ss[0];
   }
 }
 
@@ -253,11 +243,10 @@ int launch(tmdhip_ctx *ctx, GbState *S, int rep0, int nrep, const void *pos, con
   const int n = S->natoms, nb = S->nb, ns = S->nsplit, estride = ns * nb + nb;
   const size_t stride = (size_t)n * 3;
   const R *qs = ctx->qs.as<R>(), *rho = S->rho.as<R>(), *sig = S->sig.as<R>();
-  for (int c0 = 0; c0 < nrep; c0 += kChunk) {
-    const int nr = std::min(kChunk, nrep - c0), r0 = rep0 + c0;
+  for (int c0 = 0; c0 < nrep; c0 += kSideChunk) {
+    const int nr = std::min(kSideChunk, nrep - c0), r0 = rep0 + c0;
     ChunkPos P;
-    for (int r = 0; r < kChunk; ++r)
-      P.pos[r] = r >= nr ? nullptr : pos_each ? pos_each[c0 + r] : (const void *)((const R *)pos + (c0 + r) * stride);
+    for (int r = 0; r < kSideChunk; ++r) P.pos[r] = r < nr ? side_pos(pos, pos_each, c0 + r, stride * sizeof(R)) : nullptr;
     const dim3 pair((unsigned)nb, (unsigned)ns, (unsigned)nr), atom((unsigned)nb, (unsigned)nr), block(kTile);
     hipLaunchKernelGGL(gb_born_kernel<R>, pair, block, 0, st, n, S->jchunk, P, r0, rho, sig, S->part1.as<double>());
     hipLaunchKernelGGL(gb_close_born_kernel<R>, atom, block, 0, st, n, ns, r0, S->part1.as<double>(), S->radius.as<double>(),

@@ -90,13 +90,10 @@ __global__ __launch_bounds__(256) void kinetic_kernel(int64_t natoms, const R *_
     const R vx = v[3 * i], vy = v[3 * i + 1], vz = v[3 * i + 2];
     acc += 0.5 * (double)mass[i] * ((double)vx * vx + (double)vy * vy + (double)vz * vz);
   }
-  acc = wave_sum(acc);
-  __shared__ double part[4];
-  if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = acc;
-  __syncthreads();
+  const double sum = block_sum<Meet::Sequential>(acc);  // fixed-order sum (reduce.h); only the atomic's order is not fixed
   if (threadIdx.x == 0) {
-    if (DIRECT) ke[r] = part[0] + part[1] + part[2] + part[3];
-    else unsafeAtomicAdd(&ke[r], part[0] + part[1] + part[2] + part[3]);
+    if (DIRECT) ke[r] = sum;
+    else unsafeAtomicAdd(&ke[r], sum);
   }
 }
 

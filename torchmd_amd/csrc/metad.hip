@@ -9,7 +9,7 @@
 //   finish    vel, forces, out   ... and f = R((double)f + F_b), (V, s)     after the last step of a call
 //   evaluate  forces and / or out                                           tmdhip_metad_apply
 // Arithmetic in double from positions of either dtype, one rounding on each store; rows of other atoms are never read or
-// written.  The boxes, and where each replica's positions live, travel as kernel arguments, kChunk replicas per launch.
+// written.  The boxes, and where each replica's positions live, travel as kernel arguments, kSideChunk replicas per launch.
 // Latency-bound: positions -> 4 or 16 nodes of 16 or 32 bytes -> one store per component.
 //
 // The deposit chain, two launches and no host synchronisation: (a) one wave per replica evaluates s0 and V(s0) on the grid AS
@@ -30,14 +30,8 @@ using namespace tmd;
 
 namespace {
 
-constexpr int kChunk = 16;          // replicas served by one launch
 constexpr int kNodeThreads = 256;   // the node kernel's block
 constexpr int kOut = 1 + kMetadMaxCv;  // doubles per replica of the bias kernel's report: V, s_0, s_1
-
-struct ChunkArgs {  // per replica of a launch: its box and where its positions live (real [N][3])
-  double box[kChunk][3];
-  const void *pos[kChunk];
-};
 
 struct MetadState {
   int nrep = 0, natoms = 0, shared = 0;
@@ -65,7 +59,7 @@ __device__ __forceinline__ void load_cv_atoms(const MetadDef &D, const R *p, dou
 template <typename R>
 __global__ __launch_bounds__(64) void metad_bias_kernel(MetadDef D, const double *__restrict__ grid, size_t grid_stride, int natoms,
                                                         R *__restrict__ forces, R *__restrict__ vel, const R *__restrict__ mass,
-                                                        double kick, double *__restrict__ out, ChunkArgs B, int rep0) {
+                                                        double kick, double *__restrict__ out, SideChunk B, int rep0) {
 #pragma clang fp contract(off)
   const int t = threadIdx.x;
   if (t >= D.nrows) return;
@@ -78,17 +72,7 @@ __global__ __launch_bounds__(64) void metad_bias_kernel(MetadDef D, const double
   const double V = metad_interp(D, grid + (size_t)r * grid_stride, s, dV);
   metad_row_force(D, t, dV, g, f);
   const int a = D.row_atom[t];
-  if (forces) {
-    R *fo = forces + base + 3 * (size_t)a;
-    for (int c = 0; c < 3; ++c) fo[c] = (R)((double)fo[c] + f[c]);
-  }
-  if (vel) {
-    const double m = (double)mass[a];
-    if (m > 0.0) {
-      R *vo = vel + base + 3 * (size_t)a;
-      for (int c = 0; c < 3; ++c) vo[c] = (R)((double)vo[c] + kick * f[c] / m);
-    }
-  }
+  side_store(forces, vel, base + 3 * (size_t)a, mass, a, kick, f);
   if (out && t == 0) {
     out[(size_t)r * kOut] = V;
     for (int c = 0; c < kMetadMaxCv; ++c) out[(size_t)r * kOut + 1 + c] = s[c];
@@ -98,7 +82,7 @@ __global__ __launch_bounds__(64) void metad_bias_kernel(MetadDef D, const double
 // (a) of the deposit chain: one wave per replica (lane 0 works), row[r] = (s0..., w) with V(s0) read from the grid as it is
 template <typename R>
 __global__ __launch_bounds__(64) void metad_height_kernel(MetadDef D, const double *__restrict__ grid, size_t grid_stride,
-                                                          double height, double kdt, int plain, double *__restrict__ row, ChunkArgs B,
+                                                          double height, double kdt, int plain, double *__restrict__ row, SideChunk B,
                                                           int rep0) {
 #pragma clang fp contract(off)
   if (threadIdx.x != 0) return;
@@ -142,13 +126,6 @@ __global__ __launch_bounds__(kNodeThreads) void metad_node_kernel(MetadDef D, do
   *cell = v;
 }
 
-void fill_chunk(ChunkArgs &B, int nr, int c0, const void *pos, const void *const *pos_each, const double *box_host, size_t stride_bytes) {
-  for (int r = 0; r < kChunk; ++r) {
-    for (int k = 0; k < 3; ++k) B.box[r][k] = r < nr ? box_host[3 * (c0 + r) + k] : 0.0;
-    B.pos[r] = r >= nr ? nullptr : pos_each ? pos_each[c0 + r] : (const void *)((const char *)pos + (c0 + r) * stride_bytes);
-  }
-}
-
 // replicas rep0 .. rep0 + nrep - 1; forces / vel point at the rows of replica rep0, box_host at its box; the positions are
 // [nrep][N][3] at `pos`, or, with `pos_each`, one array per replica; `out` (double [R][kOut], indexed by the replica's number)
 template <typename R>
@@ -156,10 +133,9 @@ int launch(MetadState *S, int rep0, int nrep, const void *pos, const void *const
            void *vel, const void *mass, double kick, double *out, hipStream_t st) {
   const size_t stride = (size_t)S->natoms * 3;
   const size_t gstride = S->shared ? 0 : (size_t)S->nodes * metad_width(S->def);
-  for (int c0 = 0; c0 < nrep; c0 += kChunk) {
-    const int nr = std::min(kChunk, nrep - c0);
-    ChunkArgs B;
-    fill_chunk(B, nr, c0, pos, pos_each, box_host, stride * sizeof(R));
+  for (int c0 = 0; c0 < nrep; c0 += kSideChunk) {
+    const int nr = std::min(kSideChunk, nrep - c0);
+    const SideChunk B = side_chunk(nr, c0, pos, pos_each, box_host, stride * sizeof(R));
     hipLaunchKernelGGL(metad_bias_kernel<R>, dim3((unsigned)nr), dim3(64), 0, st, S->def, S->grid.as<double>(), gstride, S->natoms,
                        forces ? (R *)forces + c0 * stride : nullptr, vel ? (R *)vel + c0 * stride : nullptr, (const R *)mass, kick, out,
                        B, rep0 + c0);
@@ -183,10 +159,9 @@ int launch_deposit(MetadState *S, const void *pos, const double *box_host, doubl
                    hipStream_t st) {
   const size_t stride = (size_t)S->natoms * 3;
   const size_t gstride = S->shared ? 0 : (size_t)S->nodes * metad_width(S->def);
-  for (int c0 = 0; c0 < S->nrep; c0 += kChunk) {
-    const int nr = std::min(kChunk, S->nrep - c0);
-    ChunkArgs B;
-    fill_chunk(B, nr, c0, pos, nullptr, box_host, stride * sizeof(R));
+  for (int c0 = 0; c0 < S->nrep; c0 += kSideChunk) {
+    const int nr = std::min(kSideChunk, S->nrep - c0);
+    const SideChunk B = side_chunk(nr, c0, pos, nullptr, box_host, stride * sizeof(R));
     hipLaunchKernelGGL(metad_height_kernel<R>, dim3((unsigned)nr), dim3(64), 0, st, S->def, S->grid.as<double>(), gstride, height, kdt,
                        plain, row, B, c0);
   }

@@ -20,6 +20,7 @@
 #pragma once
 
 #include "common.h"
+#include "reduce.h"
 
 namespace tmd {
 
@@ -128,14 +129,6 @@ __device__ __forceinline__ R pair_terms(const PairConsts<R> &c, R r2, R qq, R A,
     if (ENERGY) e[3] += er;
   }
   return dEdr * rinv;
-}
-
-// wave-wide sum (64 lanes), result valid in every lane
-template <typename T>
-__device__ __forceinline__ T wave_sum(T v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
 }
 
 // Energy accumulation.  Thousands of waves adding into the same 8 doubles serialise on one L2 atomic

@@ -208,31 +208,7 @@ __global__ __launch_bounds__(kPmeThreads) void pme_influence_kernel(PmeBox<R> bx
   infl[c] = (R)G;
 }
 
-template <typename T>
-__device__ __forceinline__ double block_sum(double v, double *lds) {
-  v = wave_sum(v);
-  if ((threadIdx.x & 63) == 0) lds[threadIdx.x >> 6] = v;
-  __syncthreads();
-  double s = 0.0;
-  if (threadIdx.x == 0)
-    for (int w = 0; w < kPmeThreads / 64; ++w) s += lds[w];
-  return s;
-}
-
-// block-wide meeting of three per-lane doubles: dst[0..2] = the block's sums, the wave partials added in sequence
-__device__ __forceinline__ void block_store3(const double (&w)[3], double *dst) {
-  __shared__ double lds[3][kPmeThreads / 64];
-  for (int a = 0; a < 3; ++a) {
-    const double s = wave_sum(w[a]);
-    if ((threadIdx.x & 63) == 0) lds[a][threadIdx.x >> 6] = s;
-  }
-  __syncthreads();
-  if (threadIdx.x < 3) {
-    double s = 0.0;
-    for (int k = 0; k < kPmeThreads / 64; ++k) s += lds[threadIdx.x][k];
-    dst[threadIdx.x] = s;
-  }
-}
+static_assert(kPmeThreads == 4 * kWave, "the blocks' sums (reduce.h) meet four waves");
 
 // mode c of the half-complex grid: S(m) *= G(m) in place; its indices, the weight of the mode (2 where the grid leaves the
 // conjugate out), G and |S|^2 before the multiplication
@@ -260,15 +236,13 @@ __device__ __forceinline__ PmeMode conv_mode(int c, int Ky, int Kz, const R *__r
 template <typename R, typename C>
 __global__ __launch_bounds__(kPmeThreads) void pme_conv_kernel(int Kx, int Ky, int Kz, const R *__restrict__ infl, C *__restrict__ cg,
                                                               double *__restrict__ epart) {
-  __shared__ double lds[kPmeThreads / 64];
   const int c = blockIdx.x * blockDim.x + threadIdx.x;
-  double e = 0.0;
+  double e[1] = {0.0};
   if (c < Kx * Ky * (Kz / 2 + 1)) {
     const PmeMode m = conv_mode<R, C>(c, Ky, Kz, infl, cg);
-    e = m.wz * m.G * m.s2;
+    e[0] = m.wz * m.G * m.s2;
   }
-  const double s = block_sum<R>(e, lds);
-  if (threadIdx.x == 0) epart[blockIdx.x] = s;
+  block_sums<4, Meet::Sequential>(e, epart + blockIdx.x);
 }
 
 // F_i = -q_i sum_k grad Q_i(k) phi(k), added to the atom's own row
@@ -335,9 +309,8 @@ template <typename R>
 __global__ __launch_bounds__(kPmeThreads) void pme_excl_kernel(int n, const R *__restrict__ pos, const R *__restrict__ qs,
                                                               const int *__restrict__ excl_off, const int *__restrict__ excl_idx,
                                                               PmeBox<R> bx, R beta, R *__restrict__ forces, double *__restrict__ epart) {
-  __shared__ double lds[kPmeThreads / 64];
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  double e = 0.0;
+  double e[1] = {0.0};
   if (i < n) {
     const R qi = qs[i];
     const R xi = pos[3 * (size_t)i], yi = pos[3 * (size_t)i + 1], zi = pos[3 * (size_t)i + 2];
@@ -358,7 +331,7 @@ __global__ __launch_bounds__(kPmeThreads) void pme_excl_kernel(int n, const R *_
       fx += s * dx;
       fy += s * dy;
       fz += s * dz;
-      if (j > i) e -= (double)(qq * beta * f0);
+      if (j > i) e[0] -= (double)(qq * beta * f0);
     }
     if (forces) {
       forces[3 * (size_t)i + 0] += fx;
@@ -366,18 +339,17 @@ __global__ __launch_bounds__(kPmeThreads) void pme_excl_kernel(int n, const R *_
       forces[3 * (size_t)i + 2] += fz;
     }
   }
-  const double s = block_sum<R>(e, lds);
-  if (threadIdx.x == 0) epart[blockIdx.x] = s;
+  block_sums<4, Meet::Sequential>(e, epart + blockIdx.x);
 }
 
-// energies[ELECTROSTATICS] += 1/2 sum(conv partials) + sum(exclusion partials) + constant, in a fixed order
+// energies[ELECTROSTATICS] += 1/2 sum(conv partials) + sum(exclusion partials) + constant, in a fixed order (the partials taken
+// 256 apart by the block's threads, not by reduce.h's fold)
 __global__ __launch_bounds__(kPmeThreads) void pme_energy_kernel(const double *__restrict__ conv, int nconv, const double *__restrict__ excl,
                                                                 int nexcl, double konst, double *__restrict__ energies) {
-  __shared__ double lds[kPmeThreads / 64];
   double a = 0.0, b = 0.0;
   for (int k = threadIdx.x; k < nconv; k += kPmeThreads) a += conv[k];
   for (int k = threadIdx.x; k < nexcl; k += kPmeThreads) b += excl[k];
-  const double s = block_sum<double>(0.5 * a + b, lds);
+  const double s = block_sum<Meet::Sequential>(0.5 * a + b);
   if (threadIdx.x == 0) energies[TMDHIP_E_ELECTROSTATICS] += s + konst;
 }
 
@@ -516,7 +488,7 @@ __global__ __launch_bounds__(kPmeThreads) void pme_conv_virial_kernel(PmeBox<R> 
     if (m2 > 0.0)
       for (int a = 0; a < 3; ++a) w[a] = e * virial_mode_factor(m2, f[a] * f[a], beta);
   }
-  block_store3(w, vpart + 3 * (size_t)blockIdx.x);
+  block_sums<4, Meet::Sequential>(w, vpart + 3 * (size_t)blockIdx.x);
 }
 
 // one thread per atom: -delta_i,a F^rec_i,a, per-block partials; block 0 also stores the background's share (E ~ 1 / V: its
@@ -532,7 +504,7 @@ __global__ __launch_bounds__(kPmeThreads) void pme_virial_atoms_kernel(int n, co
     const double *c = centre + 3 * (size_t)mol_of[i];
     for (int a = 0; a < 3; ++a) w[a] = -(((double)pos[3 * (size_t)i + a] - c[a]) * (double)frec[3 * (size_t)i + a]);
   }
-  block_store3(w, vpart + 3 * (size_t)blockIdx.x);
+  block_sums<4, Meet::Sequential>(w, vpart + 3 * (size_t)blockIdx.x);
   if (blockIdx.x == 0 && threadIdx.x < 3) vpart[3 * (size_t)gridDim.x + threadIdx.x] = background;
 }
 

@@ -11,10 +11,9 @@
 //   finish    vel, forces, E     ... and f = R((double)f + F_r), energies   after the last step of a call
 //   evaluate  forces and / or E                                             tmdhip_restraint_apply
 // Arithmetic in double from positions of either dtype, one rounding on each store.  Rows of atoms in no restraint are never
-// read or written.  Energies: per block the four waves' butterfly sums meet in LDS and one thread stores the block's two
-// partials; a second launch of one wave per replica folds them in one fixed order (lane l takes blocks l, l + 64, ..., then the
-// xor butterfly).  The boxes, and where each replica's positions live (inside tmdhip_md_run: either of two buffers), travel as
-// kernel arguments, kChunk replicas per launch.
+// read or written.  Energies: fixed-order sum (reduce.h), the wave sums meet pairwise; a second launch of one wave per replica
+// folds the blocks' two partials.  The boxes, and where each replica's positions live (inside tmdhip_md_run: either of two
+// buffers), travel as kernel arguments, kSideChunk replicas per launch.
 // Latency-bound: a handful of atoms, three loads deep (row -> entry -> partner position).
 #include <hip/hip_runtime.h>
 
@@ -30,12 +29,6 @@ using namespace tmd;
 namespace {
 
 constexpr int kThreads = 256;
-constexpr int kChunk = 16;  // replicas served by one launch
-
-struct ChunkArgs {  // per replica of a launch: its box and where its positions live (real [N][3])
-  double box[kChunk][3];
-  const void *pos[kChunk];
-};
 
 struct RestraintTables {
   int natoms, nrows, npos, ndist;
@@ -64,12 +57,12 @@ struct RestraintState {
 template <typename R>
 __global__ __launch_bounds__(kThreads) void restraint_kernel(RestraintTables T, R *__restrict__ forces, R *__restrict__ vel,
                                                              const R *__restrict__ mass, double kick, double *__restrict__ partials,
-                                                             int nblocks, ChunkArgs B, int rep0) {
+                                                             int nblocks, SideChunk B, int rep0) {
 #pragma clang fp contract(off)
   const int r = rep0 + blockIdx.y;
   const size_t base = (size_t)blockIdx.y * T.natoms * 3;
   const int t = blockIdx.x * kThreads + threadIdx.x;
-  double e_pos = 0.0, e_dist = 0.0;
+  double energy[2] = {0.0, 0.0};  // position, distance
   if (t < T.nrows) {
     const double box[3] = {B.box[blockIdx.y][0], B.box[blockIdx.y][1], B.box[blockIdx.y][2]};
     const int a = T.atom[t];
@@ -83,7 +76,7 @@ __global__ __launch_bounds__(kThreads) void restraint_kernel(RestraintTables T, 
         const size_t q = (size_t)r * T.npos + en.index;
         const double k = T.pos_k[q];
         if (!(k > 0.0)) continue;
-        e_pos += restraint_position(x, T.pos_ref + 3 * q, box, k, g);
+        energy[0] += restraint_position(x, T.pos_ref + 3 * q, box, k, g);
         for (int c = 0; c < 3; ++c) f[c] += g[c];
       } else {
         const size_t q = (size_t)r * T.ndist + en.index;
@@ -92,50 +85,25 @@ __global__ __launch_bounds__(kThreads) void restraint_kernel(RestraintTables T, 
         const int b = en.partner;
         const double y[3] = {(double)p[3 * b], (double)p[3 * b + 1], (double)p[3 * b + 2]};
         const double ed = en.sign > 0 ? restraint_distance(x, y, box, k, T.dist_r0[q], g) : restraint_distance(y, x, box, k, T.dist_r0[q], g);
-        if (a < b) e_dist += ed;
+        if (a < b) energy[1] += ed;
         for (int c = 0; c < 3; ++c) f[c] += en.sign > 0 ? g[c] : -g[c];
       }
     }
-    if (forces) {
-      R *fo = forces + base + 3 * (size_t)a;
-      for (int c = 0; c < 3; ++c) fo[c] = (R)((double)fo[c] + f[c]);
-    }
-    if (vel) {
-      const double m = (double)mass[a];
-      if (m > 0.0) {
-        R *vo = vel + base + 3 * (size_t)a;
-        for (int c = 0; c < 3; ++c) vo[c] = (R)((double)vo[c] + kick * f[c] / m);
-      }
-    }
+    side_store(forces, vel, base + 3 * (size_t)a, mass, a, kick, f);
   }
   if (!partials) return;  // (uniform: a kernel argument)
-  __shared__ double part[kThreads / 64][2];
-  const double sp = wave_sum(e_pos), sd = wave_sum(e_dist);
-  if ((threadIdx.x & 63) == 0) {
-    part[threadIdx.x >> 6][0] = sp;
-    part[threadIdx.x >> 6][1] = sd;
-  }
-  __syncthreads();
-  if (threadIdx.x < 2)
-    partials[((size_t)r * nblocks + blockIdx.x) * 2 + threadIdx.x] =
-        (part[0][threadIdx.x] + part[1][threadIdx.x]) + (part[2][threadIdx.x] + part[3][threadIdx.x]);
+  block_sums<kThreads / 64, Meet::Pairwise>(energy, partials + ((size_t)r * nblocks + blockIdx.x) * 2);
 }
 
-// one wave per replica (blockIdx.x counts from rep0): out[r][2] = the sums of the replica's partials, in one fixed order
+// one wave per replica (blockIdx.x counts from rep0): out[r][2] = the fold of the replica's partials
 __global__ __launch_bounds__(64) void restraint_fold_kernel(const double *__restrict__ partials, int nblocks, double *__restrict__ out,
                                                             int rep0) {
-#pragma clang fp contract(off)
   const int r = rep0 + blockIdx.x;
-  double sp = 0.0, sd = 0.0;
-  for (int b = threadIdx.x; b < nblocks; b += 64) {
-    sp += partials[((size_t)r * nblocks + b) * 2];
-    sd += partials[((size_t)r * nblocks + b) * 2 + 1];
-  }
-  sp = wave_sum(sp);
-  sd = wave_sum(sd);
+  double sum[2];
+  fold_rows(partials + (size_t)r * nblocks * 2, nblocks, sum);
   if (threadIdx.x == 0) {
-    out[2 * (size_t)r] = sp;
-    out[2 * (size_t)r + 1] = sd;
+    out[2 * (size_t)r] = sum[0];
+    out[2 * (size_t)r + 1] = sum[1];
   }
 }
 
@@ -147,13 +115,9 @@ int launch(RestraintState *S, int rep0, int nrep, const void *pos, const void *c
            void *vel, const void *mass, double kick, double *out, hipStream_t st) {
   const RestraintTables T = S->tables();
   const size_t stride = (size_t)S->natoms * 3;
-  for (int c0 = 0; c0 < nrep; c0 += kChunk) {
-    const int nr = std::min(kChunk, nrep - c0);
-    ChunkArgs B;
-    for (int r = 0; r < kChunk; ++r) {
-      for (int k = 0; k < 3; ++k) B.box[r][k] = r < nr ? box_host[3 * (c0 + r) + k] : 0.0;
-      B.pos[r] = r >= nr ? nullptr : pos_each ? pos_each[c0 + r] : (const void *)((const R *)pos + (c0 + r) * stride);
-    }
+  for (int c0 = 0; c0 < nrep; c0 += kSideChunk) {
+    const int nr = std::min(kSideChunk, nrep - c0);
+    const SideChunk B = side_chunk(nr, c0, pos, pos_each, box_host, stride * sizeof(R));
     hipLaunchKernelGGL(restraint_kernel<R>, dim3((unsigned)S->nblocks, (unsigned)nr), dim3(kThreads), 0, st, T,
                        forces ? (R *)forces + c0 * stride : nullptr, vel ? (R *)vel + c0 * stride : nullptr,
                        (const R *)mass, kick, out ? S->partials.as<double>() : nullptr, S->nblocks, B, rep0 + c0);

@@ -5,12 +5,11 @@
 //
 // Two launches per application, blockIdx.y = replica:
 //   thermostat_reduce_kernel  per block: sum m, sum m vx, sum m vy, sum m vz, sum m v^2 over its atoms with mass > 0
-//                             -> partials[r][block][5], stored as plain doubles by one thread
-//   thermostat_update_kernel  wave 0 of every block re-sums the partials of its replica in one fixed order (lane l takes blocks
-//                             l, l + 64, ..., then the xor butterfly: all blocks see the same bits), derives V_cm, K and alpha
-//                             (thermostat_math.h) and hands them to the block through LDS; every thread writes
-//                             v <- alpha (v - V_cm) for its atom; thread 0 of block 0 writes the replica's record.
-// No floating-point atomics: two runs give the same bits.  All sums and all state arithmetic in double in both precisions,
+//                             -> partials[r][block][5]
+//   thermostat_update_kernel  wave 0 of every block folds the partials of its replica (all blocks see the same bits), derives
+//                             V_cm, K and alpha (thermostat_math.h) and hands them to the block through LDS; every thread
+//                             writes v <- alpha (v - V_cm) for its atom; thread 0 of block 0 writes the replica's record.
+// Fixed-order sum (reduce.h), the wave sums meet in sequence.  All sums and all state arithmetic in double in both precisions,
 // contraction off, one rounding on the store of v.
 //
 // Edge cases:
@@ -19,7 +18,7 @@
 //                                                (its record is)
 //   rows with mass == 0 (virtual sites)          never read into a sum, never written: they keep their bits, NaNs included
 //   active[r] == 0                               replica r is skipped: neither its velocities nor its record are touched
-// The per-replica parameters travel as kernel arguments, kChunk replicas per pair of launches (as tmdhip_scale_groups passes its
+// The per-replica parameters travel as kernel arguments, kSideChunk replicas per pair of launches (as tmdhip_scale_groups passes its
 // scale factors): no device parameter array, no host-to-device copy.
 // Streaming and HBM-bound: in fp32 the two passes read v and m twice (16 B/atom each) and write v (12 B/atom).
 #include <hip/hip_runtime.h>
@@ -39,12 +38,11 @@ constexpr int kThreads = 256;
 constexpr int kMaxBlocks = TMDHIP_THERMOSTAT_MAX_BLOCKS;  // reduction blocks per replica = rows of partials per replica
 constexpr int kRec = TMDHIP_THERMOSTAT_RECORD_DOUBLES;
 constexpr int kSums = 5;
-constexpr int kChunk = 16;  // replicas served by one pair of launches
 enum { R_KBEFORE = 0, R_ALPHA, R_KAFTER, R_VCM, R_HEAT, R_COUNT };
 
 struct ChunkArgs {
-  double kbar[kChunk], nf[kChunk], c[kChunk], r1[kChunk], s[kChunk];
-  int active[kChunk];
+  double kbar[kSideChunk], nf[kSideChunk], c[kSideChunk], r1[kSideChunk], s[kSideChunk];
+  int active[kSideChunk];
 };
 
 template <typename R>
@@ -65,19 +63,7 @@ __global__ __launch_bounds__(kThreads) void thermostat_reduce_kernel(int natoms,
     sum[3] += m * vz;
     sum[4] += m * (vx * vx + vy * vy + vz * vz);
   }
-  __shared__ double part[kThreads / 64][kSums];
-  const int w = threadIdx.x >> 6;
-#pragma unroll
-  for (int k = 0; k < kSums; ++k) {
-    const double t = wave_sum(sum[k]);
-    if ((threadIdx.x & 63) == 0) part[w][k] = t;
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    double *out = partials + ((size_t)r * kMaxBlocks + blockIdx.x) * kSums;
-#pragma unroll
-    for (int k = 0; k < kSums; ++k) out[k] = part[0][k] + part[1][k] + part[2][k] + part[3][k];
-  }
+  block_sums<kThreads / 64, Meet::Sequential>(sum, partials + ((size_t)r * kMaxBlocks + blockIdx.x) * kSums);
 }
 
 // what every thread of a block needs
@@ -97,14 +83,8 @@ __global__ __launch_bounds__(kThreads) void thermostat_update_kernel(int natoms,
   const int r = replica0 + rl;
   __shared__ Scale sc;
   if (threadIdx.x < 64) {  // wave 0: the same order of additions in every block
-    double sum[kSums] = {0, 0, 0, 0, 0};
-    for (int b = threadIdx.x; b < nblocks; b += 64) {
-      const double *q = partials + ((size_t)r * kMaxBlocks + b) * kSums;
-#pragma unroll
-      for (int k = 0; k < kSums; ++k) sum[k] += q[k];
-    }
-#pragma unroll
-    for (int k = 0; k < kSums; ++k) sum[k] = wave_sum(sum[k]);
+    double sum[kSums];
+    fold_rows(partials + (size_t)r * kMaxBlocks * kSums, nblocks, sum);
     if (threadIdx.x == 0) {
       Scale s;
       const double K = csvr_kinetic(sum[0], sum[1], sum[2], sum[3], sum[4], remove_com, s.vcm);
@@ -137,11 +117,11 @@ template <typename R>
 int apply(int64_t nreplicas, int n, void *vel, const void *mass, const double *kbar, const double *nf, const double *c,
           const double *r1, const double *s, const int32_t *active, int remove_com, double *record, double *partials, hipStream_t st) {
   const int nupdate = (n + kThreads - 1) / kThreads, nreduce = std::min(nupdate, kMaxBlocks);
-  for (int64_t r0 = 0; r0 < nreplicas; r0 += kChunk) {
-    const int nr = (int)std::min<int64_t>(kChunk, nreplicas - r0);
+  for (int64_t r0 = 0; r0 < nreplicas; r0 += kSideChunk) {
+    const int nr = (int)std::min<int64_t>(kSideChunk, nreplicas - r0);
     ChunkArgs A;
     bool any = false;
-    for (int r = 0; r < kChunk; ++r) {
+    for (int r = 0; r < kSideChunk; ++r) {
       const bool in = r < nr;
       A.kbar[r] = in ? kbar[r0 + r] : 0.0, A.nf[r] = in ? nf[r0 + r] : 1.0, A.c[r] = in ? c[r0 + r] : 1.0;
       A.r1[r] = in ? r1[r0 + r] : 0.0, A.s[r] = in ? s[r0 + r] : 0.0;

@@ -11,15 +11,14 @@
 //   mol_centre_kernel      one thread per molecule of <= 64 atoms (one wave per larger one: a second launch, only when such
 //                          molecules exist), blockIdx.y = replica: R_I in double, per-block partials of sum M_I V_I,a^2
 //   virial_list_kernel     walk_list_rows, as list_pair_kernel<R, false, LPA, 0>: every lane adds f_a (d_a / 2 - delta_i,a)
-//                          pair by pair in double; wave butterfly, the four waves meet in LDS, one thread stores the block's
-//                          three partials
+//                          pair by pair in double; the block's three partials
 //   virial_allpairs_kernel walk_allpairs_tiles, as allpairs_kernel: all-pairs contexts and cell-list contexts that fell back
 //   pme.hip: pme_virial    PME contexts: the chain of pme_apply (pme_forward / pme_inverse) with the modes' W^rec from
 //                          pme_conv_virial_kernel, -delta_i . F^rec_i from the force kernel into a scratch array, and the
 //                          neutralising background, as partials of their own
-//   virial_fold_kernel     one wave per replica: lane l sums the partials l, l + 64, ..., then the butterfly; writes
+//   virial_fold_kernel     one wave per replica folds the partials; writes
 //                          double [R][8] = (sum M V^2 x, y, z; W x, y, z; V; P)
-// No floating-point atomics anywhere, every sum in one fixed order: two calls on the same state give the same bits.
+// Fixed-order sum (reduce.h), the wave sums meet pairwise: two calls on the same state give the same bits.
 // The pair kernels are bound like the generic list kernel (gather latency + pair_terms); everything else is a few
 // microseconds of launch.
 #include "pair_walk.h"
@@ -47,25 +46,6 @@ struct VirialState {
     for (DevBuf *b : {&off, &mem, &mol_of, &big, &centre, &kpart, &wpart, &xpart, &boxes, &out}) b->release();
   }
 };
-
-// block-wide meeting of three per-lane doubles: dst[0..2] = the block's sums, in one fixed order
-template <int WAVES>
-__device__ __forceinline__ void block_store3(double a, double b, double c, double *dst) {
-#pragma clang fp contract(off)
-  __shared__ double part[WAVES][3];
-  a = wave_sum(a), b = wave_sum(b), c = wave_sum(c);
-  if ((threadIdx.x & 63) == 0) {
-    part[threadIdx.x >> 6][0] = a;
-    part[threadIdx.x >> 6][1] = b;
-    part[threadIdx.x >> 6][2] = c;
-  }
-  __syncthreads();
-  if (threadIdx.x < 3) {
-    double s = part[0][threadIdx.x];
-    if (WAVES == 4) s = (s + part[1][threadIdx.x]) + (part[2][threadIdx.x] + part[3][threadIdx.x]);
-    dst[threadIdx.x] = s;
-  }
-}
 
 // big_pass = 0: thread = molecule (those of more than kBigMol atoms are left out), grid.x = ceil(nmol / 256);
 // big_pass = 1: block of one wave = big[blockIdx.x].  blockIdx.y = replica.  vel may be null (no kinetic term).
@@ -108,18 +88,18 @@ __global__ __launch_bounds__(kThreads) void mol_centre_kernel(int natoms, int nm
     px = wave_sum(px), py = wave_sum(py), pz = wave_sum(pz);
     work = threadIdx.x == 0;
   }
-  double kx = 0, ky = 0, kz = 0;
+  double k[3] = {0, 0, 0};
   if (work) {
     double *c = centre + ((size_t)r * nmol + g) * 3;
     c[0] = sx / sm, c[1] = sy / sm, c[2] = sz / sm;
     // M V_a^2 = (sum m v_a)^2 / M
-    kx = px * px / sm, ky = py * py / sm, kz = pz * pz / sm;
+    k[0] = px * px / sm, k[1] = py * py / sm, k[2] = pz * pz / sm;
   }
   double *dst = kpart + ((size_t)r * kblocks + (big_pass ? small_blocks + blockIdx.x : blockIdx.x)) * 3;
-  if (big_pass) {
-    if (threadIdx.x == 0) dst[0] = kx, dst[1] = ky, dst[2] = kz;
+  if (big_pass) {  // (lane 0 alone holds the molecule's term)
+    if (threadIdx.x == 0) dst[0] = k[0], dst[1] = k[1], dst[2] = k[2];
   } else {
-    block_store3<kThreads / 64>(kx, ky, kz, dst);
+    block_sums<kThreads / 64, Meet::Pairwise>(k, dst);
   }
 }
 
@@ -150,7 +130,7 @@ __global__ __launch_bounds__(256) void virial_list_kernel(int n, const typename 
         fs = hit ? fs : R(0);
         virial_pair<R>(dx, dy, dz, fs, delta, w);
       });
-  block_store3<4>(w[0], w[1], w[2], wpart + 3 * (size_t)blockIdx.x);
+  block_sums<4, Meet::Pairwise>(w, wpart + 3 * (size_t)blockIdx.x);
 }
 
 // allpairs_kernel<R, false>'s walk (pair_walk.h) with the virial's accumulation.  grid = (nb, nsplit, replicas) of allpairs_split,
@@ -180,22 +160,19 @@ __global__ __launch_bounds__(64) void virial_allpairs_kernel(int n, const R *__r
                            virial_pair<R>(dx, dy, dz, fs, delta, w);
                          });
   const size_t slot = ((size_t)rep * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
-  block_store3<1>(w[0], w[1], w[2], wpart + 3 * slot);
+  block_sums<1, Meet::Pairwise>(w, wpart + 3 * slot);
 }
 
-// one wave per replica: lane l takes the partials l, l + 64, ..., then the butterfly
+// one wave per replica; the pair rows and the PME rows share one accumulator (the PME rows behind the pair rows, lane by lane)
 __global__ __launch_bounds__(64) void virial_fold_kernel(const double *__restrict__ kpart, int kblocks, const double *__restrict__ wpart,
                                                          int wstride, const double *__restrict__ xpart, int xstride,
                                                          const double *__restrict__ boxes, double *__restrict__ out) {
 #pragma clang fp contract(off)
   const int r = blockIdx.x;
   double k[3] = {0.0, 0.0, 0.0}, w[3] = {0.0, 0.0, 0.0};
-  for (int b = threadIdx.x; b < kblocks; b += 64)
-    for (int a = 0; a < 3; ++a) k[a] += kpart[((size_t)r * kblocks + b) * 3 + a];
-  for (int b = threadIdx.x; b < wstride; b += 64)
-    for (int a = 0; a < 3; ++a) w[a] += wpart[((size_t)r * wstride + b) * 3 + a];
-  for (int b = threadIdx.x; b < xstride; b += 64)
-    for (int a = 0; a < 3; ++a) w[a] += xpart[((size_t)r * xstride + b) * 3 + a];
+  fold_into(k, kpart + (size_t)r * kblocks * 3, kblocks);
+  fold_into(w, wpart + (size_t)r * wstride * 3, wstride);
+  fold_into(w, xpart + (size_t)r * xstride * 3, xstride);
   for (int a = 0; a < 3; ++a) k[a] = wave_sum(k[a]), w[a] = wave_sum(w[a]);
   if (threadIdx.x == 0) virial_finish(k, w, boxes + 3 * (size_t)r, out + 8 * (size_t)r);
 }
