@@ -102,6 +102,10 @@ __global__ void snapshot3_kernel(size_t n4, const uint4 *__restrict__ a, const u
   out[n4 + i] = b[i];
   out[2 * n4 + i] = c[i];
 }
+// can a kernel (this one, or the first integrator kernel of the call) take the snapshot?  16-byte words throughout
+inline bool snapshot_by_kernel(const tmdhip_md_desc *d, size_t bytes) {
+  return ((uintptr_t)d->pos_dev | (uintptr_t)d->vel_dev | (uintptr_t)d->forces_dev) % 16 == 0 && bytes % 16 == 0;
+}
 
 template <typename R, bool SECOND, bool LANGEVIN, bool FIRST>
 void launch_md_step(const MdStepArgs<R> &a, const PairConsts<R> &c, bool check, hipStream_t st, int nrep = 1) {
@@ -517,6 +521,7 @@ struct MdRun {
 
   int run() {
     if (any_side) TMD_TRY(check_side_terms());
+    fall_back_before_the_walk();
     TMD_TRY(snapshot_unless_first_kernel_takes_it());
     for (it = 0; it <= d->niter; ++it) {
       first = it < d->niter;
@@ -573,12 +578,40 @@ struct MdRun {
     return 0;
   }
 
+  // An AUTO context falls back to all pairs, for good and for every replica, when a box is too small for cells.  With several
+  // replicas that must not happen in the middle of the walk over them: a replica in front of the one with the small box has by
+  // then made its next step inside its pair launch (took_step), and step_all_replicas_together, which takes over from the next
+  // iteration, would make that step again.  The boxes of a call are fixed, so the same host arithmetic the re-plan runs
+  // (grid_plan.h; open boundaries always get a grid, whatever the atoms' bounds) decides it here, before the first kernel.
+  void fall_back_before_the_walk() {
+    if (nrep < 2 || !list_context() || ctx->d.algorithm != TMDHIP_ALGO_AUTO) return;
+    const double none[3] = {0, 0, 0};
+    for (int r = 0; r < nrep; ++r) {
+      const double *box = d->box_host + 3 * r;
+      if (list_matches_box(ctx->rep[r], box)) continue;
+      GridPlan p{};
+      if (!plan_grid_host(n, ctx->rlist, box, none, none, read_stencil_knob(), p)) {
+        ctx->algorithm = TMDHIP_ALGO_ALLPAIRS;
+        return;
+      }
+    }
+  }
+
   int snapshot_unless_first_kernel_takes_it() {
     if (!ctx->snap_pending) return 0;
+    const size_t bytes = sizeof(R) * stride * nrep, n4 = bytes / 16;
+    if (!snapshot_by_kernel(d, bytes)) {  // (buffers that the 16-byte kernels cannot read: three copies)
+      const size_t padded = (bytes + 15) / 16 * 16;
+      char *sn = ctx->snap.as<char>();
+      TMD_HIP(hipMemcpyAsync(sn, d->pos_dev, bytes, hipMemcpyDeviceToDevice, st));
+      TMD_HIP(hipMemcpyAsync(sn + padded, d->vel_dev, bytes, hipMemcpyDeviceToDevice, st));
+      TMD_HIP(hipMemcpyAsync(sn + 2 * padded, d->forces_dev, bytes, hipMemcpyDeviceToDevice, st));
+      ctx->snap_pending = false;
+      return 0;
+    }
     // the first kernel of the call takes the snapshot only when it is the plain first half step of a list replica with a valid
     // list (the common case); otherwise the copy kernel runs after all
     if (nrep == 1 && list_context() && list_matches_box(ctx->rep[0], d->box_host)) return 0;
-    const size_t bytes = sizeof(R) * stride * nrep, n4 = bytes / 16;
     hipLaunchKernelGGL(snapshot3_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, st, n4, (const uint4 *)d->pos_dev,
                        (const uint4 *)d->vel_dev, (const uint4 *)d->forces_dev, ctx->snap.as<uint4>(), ctx->snap_zero, ctx->snap_nzero);
     TMD_HIP(hipGetLastError());
@@ -985,39 +1018,38 @@ int tmdhip_md_run(tmdhip_ctx *ctx, const tmdhip_md_desc *desc, void *stream) {
   if (!desc->pos_dev || !desc->vel_dev || !desc->forces_dev || !desc->mass_dev || !desc->box_host)
     return fail("tmdhip_md_run: null buffer");
   if (desc->niter == 0) return 0;
+  // tmdhip_md_restore answers for THIS call from here on: a call that is refused before its snapshot is enqueued (the checks
+  // below, a side term's run_check) or that takes none (an all-pairs context) must not leave an earlier call's entry state on offer
+  ctx->snap_bytes = 0;
   if (ctx->vsites && !cons_has_sites(ctx))
     return fail("tmdhip_md_run: a context with virtual sites steps them with their rigid waters: set the constraints "
                 "(tmdhip_set_constraints after tmdhip_set_vsites)");
   hipStream_t st = (hipStream_t)stream;
   const int nzero = (int)(TMDHIP_NENERGY * ctx->rep.size());
   bool zeroed = desc->energies_dev == nullptr;
+  size_t snap_wanted = 0;  // bytes of the snapshot md_run's first kernel is to take (snap_pending)
   if (ctx->algorithm == TMDHIP_ALGO_CELLLIST) {
     // state at entry, for tmdhip_md_restore (a truncated list is only detected after the batch)
     const size_t bytes = (size_t)ctx->real_size * 3 * ctx->d.natoms * ctx->rep.size();
     const size_t padded = (bytes + 15) / 16 * 16;
     TMD_TRY(ctx->snap.ensure(3 * padded));
-    char *sn = ctx->snap.as<char>();
-    const bool aligned = ((uintptr_t)desc->pos_dev | (uintptr_t)desc->vel_dev | (uintptr_t)desc->forces_dev) % 16 == 0 &&
-                         bytes % 16 == 0;
-    if (aligned) {
-      const size_t n4 = bytes / 16;
-      const bool fits = (size_t)nzero <= n4;
-      // (md_run's first kernel saves the state itself where it can — one launch less per call —, else runs snapshot3_kernel)
-      ctx->snap_pending = true;
-      ctx->snap_zero = fits ? desc->energies_dev : nullptr;
-      ctx->snap_nzero = nzero;
-      zeroed = zeroed || fits;
-    } else {
-      TMD_HIP(hipMemcpyAsync(sn, desc->pos_dev, bytes, hipMemcpyDeviceToDevice, st));
-      TMD_HIP(hipMemcpyAsync(sn + padded, desc->vel_dev, bytes, hipMemcpyDeviceToDevice, st));
-      TMD_HIP(hipMemcpyAsync(sn + 2 * padded, desc->forces_dev, bytes, hipMemcpyDeviceToDevice, st));
-    }
-    ctx->snap_bytes = bytes;
+    // md_run takes the snapshot once it has accepted the call (snapshot_unless_first_kernel_takes_it): its first kernel saves
+    // the state itself where it can — one launch less per call —, else snapshot3_kernel, or three copies where the buffers
+    // are not 16-byte aligned
+    const bool fits = snapshot_by_kernel(desc, bytes) && (size_t)nzero <= bytes / 16;
+    ctx->snap_pending = true;
+    ctx->snap_zero = fits ? desc->energies_dev : nullptr;
+    ctx->snap_nzero = nzero;
+    zeroed = zeroed || fits;
+    snap_wanted = bytes;
   }
   if (!zeroed) TMD_HIP(hipMemsetAsync(desc->energies_dev, 0, sizeof(double) * nzero, st));
   for (auto &rp : ctx->rep) rp.spec_valid = false;  // (a plain evaluation's report says nothing about positions this call moves)
   const int rc = ctx->d.dtype == TMDHIP_F32 ? md_run<float>(ctx, desc, st) : md_run<double>(ctx, desc, st);
   for (auto &rp : ctx->rep) rp.skin_vel = nullptr;  // rebuilds outside an MD run know no velocities: static skins
+  // a kernel of md_run has taken the snapshot (it clears snap_pending where it enqueues it): only then is there a saved state.
+  // A run that failed before that point leaves snap_bytes = 0, and tmdhip_md_restore refuses.
+  if (snap_wanted && !ctx->snap_pending) ctx->snap_bytes = snap_wanted;
   if (rc == 0 && ctx->vsites) {
     // the forces of the last step leave the call spread (zero site rows), as a plain evaluation leaves them; the final kick has
     // folded the same shares in registers
