@@ -484,6 +484,13 @@ int tmdhip_restraint_apply(tmdhip_ctx *ctx, const void *pos_dev, const double *b
 /* The restraint energies of the last step of the last tmdhip_md_run: out_host double [R][2] = (position, distance).  One small
  * copy and a synchronisation of the stream; zeros without restraints. */
 int tmdhip_restraint_energy(tmdhip_ctx *ctx, double *out_host, void *stream);
+/* Cross energies for an exchange of windows between replicas: out_host double [R][R][2], entry [i][k] = the (position, distance)
+ * energies of replica i's configuration (pos_dev real [R][N][3], box_host [R][3]: row i of each) under row k of the tables the
+ * context holds.  tmdhip_restraint_apply's walk with the table row taken from a grid axis of its own: energies only, nothing but
+ * a workspace of its own is written (the row tmdhip_restraint_energy reads is left alone), [i][i] has the bits
+ * tmdhip_restraint_apply gives for the same state, and two calls give the same bits.  Synchronises the stream.  A context without
+ * restraints: nothing is launched, the output is zeroed.  Null arguments are refused before any launch. */
+int tmdhip_restraint_states(tmdhip_ctx *ctx, const void *pos_dev, const double *box_host, double *out_host, void *stream);
 /* Generalized-Born implicit solvent, OBC2 (Onufriev, Bashford, Case 2004) with the ACE-type surface-area term, for contexts with
  * open boundaries (added to ABI 11: new symbols only).  Per atom: intrinsic radius r_i (A), descreening scale s_i, and the
  * context's charges.  rho_i = r_i - 0.09, sigma_j = s_j rho_j; every ordered pair i != j counts (bonded pairs too): no minimum

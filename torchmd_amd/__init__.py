@@ -10,7 +10,8 @@ rescaling, one target temperature per replica) and `torchmd_amd.ReplicaExchange`
 restraints with one target per replica) and `torchmd_amd.Metadynamics` (well-tempered metadynamics on distance and
 dihedral collective variables) and `torchmd_amd.GeneralizedBorn` (OBC2 generalized-Born / surface-area implicit solvent for
 systems with open boundaries) and `torchmd_amd.Alchemical` (alchemical decoupling of a solute: soft-core pairs with one coupling
-per replica, dU/dlambda and foreign energies); all imported on first use only,
+per replica, dU/dlambda and foreign energies) and `torchmd_amd.HamiltonianExchange` (replicas trade those couplings and the
+restraints' windows); all imported on first use only,
 backed by hand-written HIP kernels in `torchmd_amd/lib/libtmdhip.so` (C ABI: include/tmdhip.h).
 """
 
@@ -39,6 +40,10 @@ def __getattr__(name):
         from . import exchange
 
         return getattr(exchange, name)
+    if name == "HamiltonianExchange":
+        from .hrex import HamiltonianExchange
+
+        return HamiltonianExchange
     if name == "Restraints":
         from .restraints import Restraints
 
@@ -63,6 +68,7 @@ __all__ = [
     "CRescaleBarostat",
     "Forces",
     "GeneralizedBorn",
+    "HamiltonianExchange",
     "Integrator",
     "Metadynamics",
     "MonteCarloBarostat",

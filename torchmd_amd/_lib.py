@@ -451,6 +451,7 @@ SIGNATURES = {
         [C.c_void_p, C.c_void_p, C.POINTER(C.c_double), C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p],
     ),
     "tmdhip_restraint_energy": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.c_void_p]),
+    "tmdhip_restraint_states": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_void_p]),
     "tmdhip_set_gb": (C.c_int, [C.c_void_p, C.POINTER(GbDesc)]),
     "tmdhip_gb_apply": (
         C.c_int,
@@ -613,6 +614,21 @@ class SideTerm:
     def store(self, row):
         """Take the host copy of an evaluation's energy row."""
         self.energy = row
+
+    # What an exchange of per-replica parameters between replicas asks of a term (hrex.HamiltonianExchange, DESIGN §24).  The
+    # defaults mean "nothing per replica to trade": such a term is the same in every state.
+    def exchange_parameters(self, nreplicas):
+        """An opaque snapshot of the per-replica parameters, row a of which defines state a; None: nothing to trade."""
+        return None
+
+    def cross_energies(self, owner, pos, box, snapshot):
+        """float64 [R, R]: column a is the term's potential for the configuration of slot r (row r) under state a of
+        `snapshot`; a constant per row may be left out.  `owner`: the `Forces`."""
+        raise NotImplementedError
+
+    def assign_states(self, snapshot, state_of_slot):
+        """Give slot r the parameters of state `state_of_slot[r]` of `snapshot` (one version bump)."""
+        raise NotImplementedError
 
     def monitor_columns(self):
         return (self.side_name,)

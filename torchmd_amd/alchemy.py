@@ -123,6 +123,21 @@ class Alchemical(L.SideTerm):
         return (np.ascontiguousarray(np.broadcast_to(self.lambda_vdw, (nreplicas,)).astype(np.float64)),
                 np.ascontiguousarray(np.broadcast_to(self.lambda_elec, (nreplicas,)).astype(np.float64)))
 
+    # ------------------------------------------------------------------ exchange of couplings between replicas (DESIGN §24)
+    def exchange_parameters(self, nreplicas):
+        """[R, 2] = (lambda_vdw, lambda_elec) per replica; None for one coupling shared by all replicas."""
+        if len(self.lambda_vdw) == 1 and nreplicas != 1:
+            return None
+        return np.stack(self.lambdas(nreplicas), axis=1)
+
+    def cross_energies(self, owner, pos, box, snapshot):
+        """The cross energy at every state (the intra part is the same in all of them: a constant per row)."""
+        return owner.alchemical_energies(pos, box, snapshot)
+
+    def assign_states(self, snapshot, state_of_slot):
+        s = np.asarray(snapshot)[np.asarray(state_of_slot, dtype=np.int64)]
+        self.set_lambdas(s[:, 0], s[:, 1])
+
     def topology(self, parameters, energies):
         """The index tuples of the bonded terms that are on: {name: [M, width]}."""
         out = {}

@@ -1,5 +1,5 @@
 // Harmonic position and distance restraints with one target per replica, for gfx950 (tmdhip_set_restraints,
-// tmdhip_restraint_apply, tmdhip_restraint_energy; the per-entry arithmetic: restraint_math.h).
+// tmdhip_restraint_apply, tmdhip_restraint_energy, tmdhip_restraint_states; the per-entry arithmetic: restraint_math.h).
 //
 // One kernel, blockIdx.y = replica, 256 threads, ONE THREAD PER RESTRAINED ATOM: the thread walks its atom's row of a CSR built
 // on the host at set-up (the position entry first, then the distance entries by restraint index), sums the row's forces in
@@ -15,6 +15,12 @@
 // folds the blocks' two partials.  The boxes, and where each replica's positions live (inside tmdhip_md_run: either of two
 // buffers), travel as kernel arguments, kSideChunk replicas per launch.
 // Latency-bound: a handful of atoms, three loads deep (row -> entry -> partner position).
+//
+// Cross energies (tmdhip_restraint_states, for an exchange of windows between replicas): the same walk with the table
+// row taken from blockIdx.z instead of the replica's own number, energies only: entry [i][k] is configuration i in box i under
+// row k.  The energy lines of the two kernels are the same expressions in the same order, and both sums go through block_sums
+// and fold_rows, so [i][i] has the bits restraint_kernel gives.  The partials and the result live in a workspace of their own
+// (allocated at the first call): the partials and the energy row of a run are never touched.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -42,10 +48,11 @@ struct RestraintState {
   DevBuf atom, off, ent, pos_ref, pos_k, dist_r0, dist_k;
   DevBuf partials;  // double [R][nblocks][2]
   DevBuf energy;    // double [R][2]: (position, distance) of the last tmdhip_md_run
+  DevBuf cross_partials, cross;  // tmdhip_restraint_states: double [R][R][nblocks][2] and [R][R][2], allocated at the first call
   std::vector<int32_t> atom_h;
   const void *mass_checked = nullptr;  // the mass array whose restrained rows are known to be positive
   void release() {
-    for (DevBuf *b : {&atom, &off, &ent, &pos_ref, &pos_k, &dist_r0, &dist_k, &partials, &energy}) b->release();
+    for (DevBuf *b : {&atom, &off, &ent, &pos_ref, &pos_k, &dist_r0, &dist_k, &partials, &energy, &cross_partials, &cross}) b->release();
   }
   RestraintTables tables() const {
     return {natoms, nrows, npos, ndist, atom.as<int32_t>(), off.as<int32_t>(), ent.as<RestraintEntry>(),
@@ -105,6 +112,69 @@ __global__ __launch_bounds__(64) void restraint_fold_kernel(const double *__rest
     out[2 * (size_t)r] = sum[0];
     out[2 * (size_t)r + 1] = sum[1];
   }
+}
+
+// restraint_kernel's walk without the forces: blockIdx.y = configuration of the launch (rep0 counts it in), blockIdx.z = row k of
+// the tables; partials [R][R][nblocks][2], (configuration, row) outermost
+template <typename R>
+__global__ __launch_bounds__(kThreads) void restraint_states_kernel(RestraintTables T, double *__restrict__ partials, int nblocks,
+                                                                    int nrep, SideChunk B, int rep0) {
+#pragma clang fp contract(off)
+  const int i = rep0 + blockIdx.y, r = blockIdx.z;
+  const int t = blockIdx.x * kThreads + threadIdx.x;
+  double energy[2] = {0.0, 0.0};  // position, distance
+  if (t < T.nrows) {
+    const double box[3] = {B.box[blockIdx.y][0], B.box[blockIdx.y][1], B.box[blockIdx.y][2]};
+    const int a = T.atom[t];
+    const R *p = (const R *)B.pos[blockIdx.y];
+    const double x[3] = {(double)p[3 * a], (double)p[3 * a + 1], (double)p[3 * a + 2]};
+    for (int e = T.off[t]; e < T.off[t + 1]; ++e) {
+      const RestraintEntry en = T.ent[e];
+      double g[3];
+      if (en.kind == 0) {
+        const size_t q = (size_t)r * T.npos + en.index;
+        const double k = T.pos_k[q];
+        if (!(k > 0.0)) continue;
+        energy[0] += restraint_position(x, T.pos_ref + 3 * q, box, k, g);
+      } else {
+        const int b = en.partner;
+        if (!(a < b)) continue;  // (counted by the lower atom)
+        const size_t q = (size_t)r * T.ndist + en.index;
+        const double k = T.dist_k[q];
+        if (!(k > 0.0)) continue;
+        const double y[3] = {(double)p[3 * b], (double)p[3 * b + 1], (double)p[3 * b + 2]};
+        energy[1] += en.sign > 0 ? restraint_distance(x, y, box, k, T.dist_r0[q], g) : restraint_distance(y, x, box, k, T.dist_r0[q], g);
+      }
+    }
+  }
+  block_sums<kThreads / 64, Meet::Pairwise>(energy, partials + (((size_t)i * nrep + r) * nblocks + blockIdx.x) * 2);
+}
+
+// one wave per (configuration, row): out[i][k][2] = the fold of its partials
+__global__ __launch_bounds__(64) void restraint_states_fold_kernel(const double *__restrict__ partials, int nblocks, double *__restrict__ out) {
+  const size_t ik = blockIdx.x;
+  double sum[2];
+  fold_rows(partials + ik * nblocks * 2, nblocks, sum);
+  if (threadIdx.x == 0) {
+    out[2 * ik] = sum[0];
+    out[2 * ik + 1] = sum[1];
+  }
+}
+
+template <typename R>
+int launch_states(RestraintState *S, const void *pos, const double *box_host, hipStream_t st) {
+  const RestraintTables T = S->tables();
+  const size_t stride = (size_t)S->natoms * 3;
+  for (int c0 = 0; c0 < S->nrep; c0 += kSideChunk) {
+    const int nr = std::min(kSideChunk, S->nrep - c0);
+    const SideChunk B = side_chunk(nr, c0, pos, nullptr, box_host, stride * sizeof(R));
+    hipLaunchKernelGGL(restraint_states_kernel<R>, dim3((unsigned)S->nblocks, (unsigned)nr, (unsigned)S->nrep), dim3(kThreads), 0, st, T,
+                       S->cross_partials.as<double>(), S->nblocks, S->nrep, B, c0);
+  }
+  hipLaunchKernelGGL(restraint_states_fold_kernel, dim3((unsigned)(S->nrep * S->nrep)), dim3(64), 0, st, S->cross_partials.as<double>(),
+                     S->nblocks, S->cross.as<double>());
+  TMD_HIP(hipGetLastError());
+  return 0;
 }
 
 // replicas rep0 .. rep0 + nrep - 1; forces / vel point at the rows of replica rep0, box_host at its box; the positions are
@@ -237,6 +307,25 @@ int tmdhip_restraint_apply(tmdhip_ctx *ctx, const void *pos_dev, const double *b
 
 int tmdhip_restraint_energy(tmdhip_ctx *ctx, double *out_host, void *stream) {
   return side_energy(ctx, kSideRestraints, "tmdhip_restraint_energy", out_host, stream);
+}
+
+int tmdhip_restraint_states(tmdhip_ctx *ctx, const void *pos_dev, const double *box_host, double *out_host, void *stream) {
+  if (!ctx || !pos_dev || !box_host || !out_host) return fail("tmdhip_restraint_states: null argument");
+  RestraintState *S = state_of(ctx);
+  const size_t nrep = ctx->rep.size(), count = 2 * nrep * nrep;
+  if (!S) {
+    std::fill(out_host, out_host + count, 0.0);
+    return 0;
+  }
+  if (nrep > 65535) return fail("tmdhip_restraint_states: at most 65535 replicas (the table row is a grid axis)");
+  hipStream_t st = (hipStream_t)stream;
+  // (a buffer that grows is freed: nothing of an earlier call is in flight, every call ends with a synchronisation)
+  TMD_TRY(S->cross_partials.ensure(sizeof(double) * count * S->nblocks));
+  TMD_TRY(S->cross.ensure(sizeof(double) * count));
+  TMD_TRY(ctx->d.dtype == TMDHIP_F32 ? launch_states<float>(S, pos_dev, box_host, st) : launch_states<double>(S, pos_dev, box_host, st));
+  TMD_HIP(hipMemcpyAsync(out_host, S->cross.p, sizeof(double) * count, hipMemcpyDeviceToHost, st));
+  TMD_HIP(hipStreamSynchronize(st));
+  return 0;
 }
 
 }  // extern "C"

@@ -632,6 +632,31 @@ class Forces:
                 out[:, k0 : k0 + len(part)] = got
         return out
 
+    def restraint_energies(self, pos, box):
+        """The (position, distance) restraint energies of every replica's configuration, in its own box, under every replica's
+        row of the tables: [R, R, 2] float64 (numpy), entry [i, k] = configuration i under row k (tmdhip_restraint_states).  The
+        diagonal holds the bits an evaluation reports for the same state."""
+        if self.restraints is None:
+            raise ValueError("restraint_energies() needs restraints=")
+        if _is_batched(pos):
+            raise ValueError("restraint_energies() cannot run under torch.vmap")
+        L.require_device_tensor(pos, "pos")
+        p = pos.detach()
+        if not p.is_contiguous():
+            p = p.contiguous()
+        if p.dim() != 3 or p.shape[1] != self.natoms:
+            raise RuntimeError(f"pos must have shape (nreplicas, {self.natoms}, 3), got {tuple(p.shape)}")
+        eng = self._engine(p)
+        R = p.shape[0]
+        boxes = self._replica_boxes(box, R)
+        out = np.empty((R, R, 2), dtype=np.float64)
+        with torch.cuda.device(p.device):
+            self.restraints.sync(eng, self)
+            L.check(eng.lib.tmdhip_restraint_states(eng.ctx, C.c_void_p(p.data_ptr()), boxes.ctypes.data_as(C.POINTER(C.c_double)),
+                                                    out.ctypes.data_as(C.POINTER(C.c_double)),
+                                                    C.c_void_p(torch.cuda.current_stream(p.device).cuda_stream)), "tmdhip_restraint_states")
+        return out
+
     def _gb_box(self, hbox):
         """The generalized-Born model is for open boundaries: every box edge must be zero."""
         if self.implicit_solvent is not None and np.any(np.asarray(hbox) != 0):

@@ -8,7 +8,8 @@ Mirror of the reference module (`torchmd/integrator.py`): same constants, helper
 §20) and an opt-in `thermostat` keyword (a
 `thermostat.VelocityRescale`: stochastic velocity rescaling between batches of steps, one target temperature per replica,
 DESIGN §14) and an opt-in `exchange` keyword (an `exchange.ReplicaExchange`: temperature replica exchange on the thermostat's
-ladder) that this package adds.  Each iteration is
+ladder, DESIGN §16, or an `hrex.HamiltonianExchange`: replicas trade alchemical couplings and restraint windows)
+that this package adds.  Each iteration is
 
     tmdhip_first_vv  ->  forces.compute  ->  tmdhip_langevin_second_vv | tmdhip_second_vv
 
@@ -171,7 +172,7 @@ class Integrator:
         if constraints is not None:
             self._init_constraints(constraints)
         # the scheduled controls (controls.Control): thermostat.VelocityRescale; barostat.MonteCarloBarostat or
-        # crescale.CRescaleBarostat; exchange.ReplicaExchange.  `forces.metadynamics` is the fourth.
+        # crescale.CRescaleBarostat; exchange.ReplicaExchange or hrex.HamiltonianExchange.  `forces.metadynamics` is the fourth.
         self.thermostat, self.barostat, self.exchange = thermostat, barostat, None
         self._virial_barostat = bool(getattr(barostat, "virial_driven", False))  # (a plain attribute: nothing dispatches on it)
         self.kinetic_source = None  # the control whose `kinetic()` holds the kinetic energies left (`Control.after_segment`)

@@ -151,6 +151,34 @@ class Restraints(L.SideTerm):
             self.dist_k = self._per_entry(distance_k, self.ndist, "distance_k")
         self.version += 1
 
+    # ------------------------------------------------------------------ exchange of windows between replicas
+    def exchange_parameters(self, nreplicas):
+        """The four tables as they are, row a = state a, and `state_of_slot` (which `assign_states` keeps: the device tables
+        are indexed by slot, `cross_energies` answers by state); None without entries."""
+        if not (self.npos or self.ndist):
+            return None
+        if self.nreplicas != nreplicas:
+            raise ValueError(f"restraints were made for {self.nreplicas} replicas, the exchange has {nreplicas}")
+        return {"pos_ref": self.pos_ref.copy(), "pos_k": self.pos_k.copy(), "dist_r0": self.dist_r0.copy(),
+                "dist_k": self.dist_k.copy(), "state_of_slot": np.arange(self.nreplicas, dtype=np.int64)}
+
+    def cross_energies(self, owner, pos, box, snapshot):
+        """Position plus distance energy of slot r's configuration under state a: tmdhip_restraint_states gives it under the
+        row of every slot, and column a is the column of the slot that holds state a."""
+        slot_of_state = np.argsort(snapshot["state_of_slot"])
+        return owner.restraint_energies(pos, box).sum(axis=2)[:, slot_of_state]
+
+    def assign_states(self, snapshot, state_of_slot):
+        s = np.array(state_of_slot, dtype=np.int64)
+        version = self.version
+        if self.ndist:
+            self.set_distance_targets(snapshot["dist_r0"][s])
+        if self.npos:
+            self.set_position_reference(snapshot["pos_ref"][s])
+        self.set_strengths(snapshot["pos_k"][s] if self.npos else None, snapshot["dist_k"][s] if self.ndist else None)
+        self.version = version + 1  # (one bump, one upload at the next evaluation)
+        snapshot["state_of_slot"] = s
+
     def atoms(self):
         """Every restrained atom, ascending."""
         return np.unique(np.concatenate([self.pos_atom, self.dist_pair.reshape(-1)])).astype(np.int64)

@@ -28,6 +28,11 @@ DESIGN §22) every monitor file gains the columns `alchemical` (the cross + intr
 with `states` the cross energy of every saved frame at those couplings is written to `{output}_states_{k}.npy` `[frames, K]`.
 With `pressure: true` every monitor file gains a `pressure` column (bar): the instantaneous pressure of the force field from the
 molecular virial, evaluated when a monitor row is written, with or without `barostat_pressure`.
+With a `hamiltonian_exchange:` mapping (frequency, seed, temperature, keep_matrices; not together with
+`exchange_frequency`) the replicas trade their alchemical couplings and restraint tables: every monitor file gains a `state`
+column — the state the replica slot holds at that row — the acceptance counts are written to `hamiltonian_exchange.json`, and
+with `keep_matrices` the reduced cross energies of every attempt to `hrex_u.npy` `[nattempts, R, R]` (slot, state) and the
+assignment after it to `hrex_states.npy` `[nattempts, R]`.
 """
 
 from __future__ import annotations
@@ -45,7 +50,7 @@ import yaml
 from . import io as tio
 from .forcefields import ForceField
 from .forces import Forces, active_side_terms
-from .integrator import Integrator, maxwell_boltzmann
+from .integrator import BOLTZMAN, Integrator, maxwell_boltzmann
 from .minimizers import minimize_bfgs, minimize_fire
 from .utils import LogWriter
 from .parameters import Parameters
@@ -75,6 +80,7 @@ DEFAULTS = dict(
     remove_com=True,  # the thermostat also takes out the centre-of-mass motion
     exchange_frequency=None,  # steps between two replica-exchange attempts; None: none.  Needs thermostat: csvr with a list: DESIGN §16
     exchange_seed=None,  # seed of the exchange's random stream; None: drawn from torch's generator (so `seed` reproduces it)
+    hamiltonian_exchange=None,  # None or a mapping {frequency, seed, temperature, keep_matrices}: replicas trade couplings / windows: DESIGN §24
     restraints=None,  # None or an .npz file: harmonic position / distance restraints (pos_atom, pos_ref, pos_k, dist_pair, dist_r0, dist_k): DESIGN §17
     metadynamics=None,  # None or a mapping with the arguments of metadynamics.Metadynamics (cvs: [[kind, [atoms]], ...]): DESIGN §18
     pressure=False,  # True: every monitor file gains a `pressure` column (bar): the instantaneous pressure from the molecular virial: DESIGN §19
@@ -97,7 +103,7 @@ def get_args(arguments=None):
             ap.add_argument(opt, dest=key, action="store_true", default=None)
         elif key in ("forceterms", "structure"):
             ap.add_argument(opt, dest=key, nargs="+", default=None)
-        elif key in ("external", "exclusions", "pme_grid", "metadynamics"):
+        elif key in ("external", "exclusions", "pme_grid", "metadynamics", "hamiltonian_exchange"):
             continue
         else:
             ap.add_argument(opt, dest=key, default=None, type=type(val) if val is not None else str)
@@ -164,6 +170,17 @@ def get_args(arguments=None):
             raise ValueError(f"exchange_frequency must be a positive number of steps, got {args.exchange_frequency}")
         if args.thermostat != "csvr" or not isinstance(args.thermostat_temperature, list):
             raise ValueError("exchange_frequency needs thermostat: csvr with a list as thermostat_temperature (the ladder)")
+    if isinstance(args.hamiltonian_exchange, str) and args.hamiltonian_exchange.lower() in ("none", "null", ""):
+        args.hamiltonian_exchange = None
+    if args.hamiltonian_exchange is not None:
+        hx = args.hamiltonian_exchange
+        if not isinstance(hx, dict):
+            raise ValueError("hamiltonian_exchange must be a mapping (frequency, seed, temperature, keep_matrices)")
+        unknown = set(hx) - {"frequency", "seed", "temperature", "keep_matrices"}
+        if unknown:
+            raise ValueError(f"hamiltonian_exchange: unknown keys {sorted(unknown)}")
+        if args.exchange_frequency is not None:
+            raise ValueError("hamiltonian_exchange and exchange_frequency are two exchanges: give one of them")
     if isinstance(args.restraints, str) and args.restraints.lower() in ("none", "null", ""):
         args.restraints = None
     if isinstance(args.metadynamics, str) and args.metadynamics.lower() in ("none", "null", ""):
@@ -395,6 +412,13 @@ def dynamics(args, mol, system, forces):
         from .exchange import ReplicaExchange
 
         exchange = extra["exchange"] = ReplicaExchange(args.exchange_frequency, seed=args.exchange_seed)
+    hrex = None
+    if args.hamiltonian_exchange is not None:
+        from .hrex import HamiltonianExchange
+
+        hx = args.hamiltonian_exchange
+        hrex = extra["exchange"] = HamiltonianExchange(hx.get("frequency", 500), temperature=hx.get("temperature"), seed=hx.get("seed"),
+                                                       keep_matrices=bool(hx.get("keep_matrices", False)))
     if thermostat is not None:
         integrator = Integrator(system, forces, args.timestep, device, constraints=args.constraints, thermostat=thermostat, **extra)
     else:
@@ -406,6 +430,7 @@ def dynamics(args, mol, system, forces):
     columns = ("iter", "ns", "epot", "ekin", "etot", "T") + (("volume",) if barostat is not None else ())
     columns += ("pressure",) if args.pressure else ()
     columns += ("rung",) if exchange is not None else ()
+    columns += ("state",) if hrex is not None else ()
     # each side term adds its columns: what of its energy `epot` contains, as of the last evaluation (the bias and its CVs last,
     # where the monitor files have always had them)
     side_terms = sorted(active_side_terms(forces), key=lambda t: t.side_name == "metadynamics")
@@ -449,6 +474,8 @@ def dynamics(args, mol, system, forces):
                 row["pressure"] = float(pressure[k])
             if exchange is not None:
                 row["rung"] = int(exchange.rungs[k]) if exchange.rungs is not None else k
+            if hrex is not None:
+                row["state"] = int(hrex.states[k])
             for term in side_terms:
                 row.update(term.monitor_row(k))
             logs[k].write_row(row)
@@ -462,6 +489,14 @@ def dynamics(args, mol, system, forces):
             json.dump({"frequency": exchange.frequency, "seed": exchange.seed, "temperatures": [float(t) for t in thermostat_ladder],
                        "attempts": [] if none else exchange.attempts.tolist(), "accepted": [] if none else exchange.accepted.tolist(),
                        "rungs": list(range(args.replicas)) if none else exchange.rungs.tolist()}, fh)
+    if hrex is not None:
+        with open(os.path.join(args.log_dir, "hamiltonian_exchange.json"), "w") as fh:
+            json.dump({"frequency": hrex.frequency, "seed": hrex.seed, "temperature": 1.0 / (BOLTZMAN * hrex.beta),
+                       "attempts": hrex.attempts.tolist(), "accepted": hrex.accepted.tolist(), "states": hrex.states.tolist()}, fh)
+        if hrex.keep_matrices:
+            R = args.replicas
+            np.save(os.path.join(args.log_dir, "hrex_u.npy"), np.asarray(hrex.matrices, dtype=np.float64).reshape(-1, R, R))
+            np.save(os.path.join(args.log_dir, "hrex_states.npy"), np.asarray(hrex.history, dtype=np.int64).reshape(-1, R))
     print(f"{args.steps} steps in {wall:.2f} s = {args.steps * args.timestep * FS2NS / wall * 86400:.1f} ns/day per replica")
     return stager
 
