@@ -491,6 +491,50 @@ int tmdhip_restraint_energy(tmdhip_ctx *ctx, double *out_host, void *stream);
  * tmdhip_restraint_apply gives for the same state, and two calls give the same bits.  Synchronises the stream.  A context without
  * restraints: nothing is launched, the output is zeroed.  Null arguments are refused before any launch. */
 int tmdhip_restraint_states(tmdhip_ctx *ctx, const void *pos_dev, const double *box_host, double *out_host, void *stream);
+/* Harmonic, optionally flat-bottomed restraints on the distance, angle and dihedral between centres of groups of atoms, with
+ * targets, strengths and widths per replica (added to ABI 11: new symbols only).  All in double:
+ *   centre    X_g = x_a0 + sum_a w_a mi(x_a - x_a0), a0 the group's first atom, w_a = W_a / sum W (normalised here, the sum in
+ *             member order), mi the minimum image d - box rint(d / box) (no image along an edge of zero).  PRECONDITION: every
+ *             atom of a group lies within half a box edge of a0 along every periodic axis.
+ *   distance  s = |mi(X_a - X_b)|          angle  s = acos(clamp(u.v / |u||v|, -1, 1)), u = mi(X_a - X_b), v = mi(X_c - X_b)
+ *   dihedral  s = the torsion of four centres in the convention of the metadynamics CV; delta wrapped into [-pi, pi]
+ *   energy    delta = s - s0, u = sign(delta) max(|delta| - flat, 0), E = k u^2 / 2; k = 0 switches an entry off for a replica
+ * Singular geometries (r = 0, sin theta = 0, collinear centres of a dihedral) give no force and the energy of the formula.
+ * The force on atom a of group g is w_a G_g, G_g the sum of -dE/dX_g over the restraints that name g; an atom in several
+ * groups is written by one thread, which adds its memberships by ascending group and, within a group, the restraints by
+ * ascending index.  No floating-point atomics: two runs give the same bits.  Rows of atoms in no group are never written.
+ * tmdhip_set_group_restraints validates, builds the rows, copies the tables and synchronises; calling it again replaces the
+ * tables; enable = 0 or nrestraints = 0 releases everything.  Refused: a wrong struct size or nreplicas, an empty group, an
+ * atom twice in one group, an index out of range, a weight that is not finite or not > 0, a restraint that names a group twice
+ * or has the wrong number of groups for its kind (kind 0 = distance: 2, 1 = angle: 3, 2 = dihedral: 4; the rest of the row is
+ * -1), a negative or non-finite k or flat, a non-finite target, an angle target outside [0, pi], a group atom that is a
+ * virtual site of the context, a context with passive atoms and, where masses are seen, a group atom without mass (one
+ * read-back per mass array, as for tmdhip_set_restraints).  tmdhip_md_run integrates under the total force as it does with
+ * restraints: the impulse dt a(x) / (1 - gamma dt) between launches (two launches: centres, forces) and a finishing launch. */
+typedef struct tmdhip_group_restraint_desc {
+  int32_t struct_size; /* = sizeof(tmdhip_group_restraint_desc) */
+  int32_t enable;
+  int32_t nreplicas; /* = the context's */
+  int32_t ngroups, nrestraints;
+  int32_t reserved;
+  const int32_t *group_off_host;    /* [ngroups + 1] */
+  const int32_t *member_atom_host;  /* [group_off[ngroups]] */
+  const double *member_weight_host; /* raw weights > 0, same length */
+  const int32_t *kind_host;         /* [M] */
+  const int32_t *groups_host;       /* [M][4], -1 padded */
+  const double *target_host;        /* [R][M] */
+  const double *k_host;             /* [R][M] */
+  const double *flat_host;          /* [R][M] */
+} tmdhip_group_restraint_desc;
+int tmdhip_set_group_restraints(tmdhip_ctx *ctx, const tmdhip_group_restraint_desc *desc);
+/* tmdhip_restraint_apply's contract; energies_dev (double [R][3]) = (distance, angle, dihedral) energies, overwritten. */
+int tmdhip_group_restraint_apply(tmdhip_ctx *ctx, const void *pos_dev, const double *box_host, void *forces_dev, void *vel_dev,
+                                 const void *mass_dev, double kick, double *energies_dev, void *stream);
+/* The energies of the last step of the last tmdhip_md_run: out_host double [R][3]; zeros without the term. */
+int tmdhip_group_restraint_energy(tmdhip_ctx *ctx, double *out_host, void *stream);
+/* Cross energies, tmdhip_restraint_states' contract: out_host double [R][R][3], entry [i][k] = configuration i in box i under
+ * row k of the tables; [i][i] has the bits tmdhip_group_restraint_apply gives; the run's energy row is left alone. */
+int tmdhip_group_restraint_states(tmdhip_ctx *ctx, const void *pos_dev, const double *box_host, double *out_host, void *stream);
 /* Generalized-Born implicit solvent, OBC2 (Onufriev, Bashford, Case 2004) with the ACE-type surface-area term, for contexts with
  * open boundaries (added to ABI 11: new symbols only).  Per atom: intrinsic radius r_i (A), descreening scale s_i, and the
  * context's charges.  rho_i = r_i - 0.09, sigma_j = s_j rho_j; every ordered pair i != j counts (bonded pairs too): no minimum

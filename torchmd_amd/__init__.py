@@ -11,7 +11,8 @@ restraints with one target per replica) and `torchmd_amd.Metadynamics` (well-tem
 dihedral collective variables) and `torchmd_amd.GeneralizedBorn` (OBC2 generalized-Born / surface-area implicit solvent for
 systems with open boundaries) and `torchmd_amd.Alchemical` (alchemical decoupling of a solute: soft-core pairs with one coupling
 per replica, dU/dlambda and foreign energies) and `torchmd_amd.HamiltonianExchange` (replicas trade those couplings and the
-restraints' windows); all imported on first use only,
+restraints' windows) and `torchmd_amd.GroupRestraints` (restraints on the distance, angle and dihedral between centres of groups
+of atoms, the Boresch set among them); all imported on first use only,
 backed by hand-written HIP kernels in `torchmd_amd/lib/libtmdhip.so` (C ABI: include/tmdhip.h).
 """
 
@@ -48,6 +49,10 @@ def __getattr__(name):
         from .restraints import Restraints
 
         return Restraints
+    if name == "GroupRestraints":
+        from .group_restraints import GroupRestraints
+
+        return GroupRestraints
     if name == "Metadynamics":
         from .metadynamics import Metadynamics
 
@@ -68,6 +73,7 @@ __all__ = [
     "CRescaleBarostat",
     "Forces",
     "GeneralizedBorn",
+    "GroupRestraints",
     "HamiltonianExchange",
     "Integrator",
     "Metadynamics",

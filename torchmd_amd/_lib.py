@@ -264,6 +264,25 @@ class RestraintDesc(C.Structure):
     ]
 
 
+class GroupRestraintDesc(C.Structure):
+    _fields_ = [
+        ("struct_size", C.c_int32),
+        ("enable", C.c_int32),
+        ("nreplicas", C.c_int32),
+        ("ngroups", C.c_int32),
+        ("nrestraints", C.c_int32),
+        ("reserved", C.c_int32),
+        ("group_off_host", C.c_void_p),
+        ("member_atom_host", C.c_void_p),
+        ("member_weight_host", C.c_void_p),
+        ("kind_host", C.c_void_p),
+        ("groups_host", C.c_void_p),
+        ("target_host", C.c_void_p),
+        ("k_host", C.c_void_p),
+        ("flat_host", C.c_void_p),
+    ]
+
+
 class GbDesc(C.Structure):
     _fields_ = [
         ("struct_size", C.c_int32),
@@ -452,6 +471,13 @@ SIGNATURES = {
     ),
     "tmdhip_restraint_energy": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.c_void_p]),
     "tmdhip_restraint_states": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_void_p]),
+    "tmdhip_set_group_restraints": (C.c_int, [C.c_void_p, C.POINTER(GroupRestraintDesc)]),
+    "tmdhip_group_restraint_apply": (
+        C.c_int,
+        [C.c_void_p, C.c_void_p, C.POINTER(C.c_double), C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p],
+    ),
+    "tmdhip_group_restraint_energy": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.c_void_p]),
+    "tmdhip_group_restraint_states": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_void_p]),
     "tmdhip_set_gb": (C.c_int, [C.c_void_p, C.POINTER(GbDesc)]),
     "tmdhip_gb_apply": (
         C.c_int,
@@ -591,7 +617,7 @@ def require_device_tensor(t, name):
 
 
 class SideTerm:
-    """What `Restraints`, `Metadynamics`, `GeneralizedBorn` and `Alchemical` have in common: a force term outside the pair /
+    """What `Restraints`, `Metadynamics`, `GeneralizedBorn`, `Alchemical` and `GroupRestraints` have in common: a force term outside the pair /
     bonded engine ("Adding a side term").  `Forces`, `Integrator`, run.py and the domain decomposition loop over
     `forces.SIDE_TERMS` and ask only for what stands here.  A term also provides `sync(eng, owner)`: make the context of the
     engine `eng` hold this object's tables (`owner`: the `Forces`)."""

@@ -580,9 +580,9 @@ struct Replica {
 // half-step velocities between two launches; a finishing launch adds dt/2 a, adds the force to the caller's array and writes
 // the energy row ("Adding a side term").  The order of the slots is the launch order and part of the contract:
 // velocity increments are floating-point adds, so another order changes bits.
-enum { kSideRestraints, kSideMetad, kSideGb, kSideAlchemy, kSideTerms };
+enum { kSideRestraints, kSideMetad, kSideGb, kSideAlchemy, kSideGroups, kSideTerms };
 // doubles per replica of a term's energy row (known while the term is off: tmdhip_*_apply / _energy zero the row then)
-constexpr int kSideWidth[kSideTerms] = {2, 3, 2, 5};
+constexpr int kSideWidth[kSideTerms] = {2, 3, 2, 5, 3};
 struct SideTerm {
   void *state = nullptr;  // null: off (no launch, nothing allocated); the term's tmdhip_set_* fills the slot, its release clears it
   const char *needs = nullptr;  // for messages: "restraints need", "metadynamics needs", ...

@@ -51,10 +51,10 @@ def build_exclusion_csr(natoms, pairs):
 
 _LIVE_ENGINES = weakref.WeakSet()
 
-# The attributes of a `Forces` that hold its side terms (`_lib.SideTerm`: Restraints, Metadynamics, GeneralizedBorn, Alchemical),
+# The attributes of a `Forces` that hold its side terms (`_lib.SideTerm`: Restraints, Metadynamics, GeneralizedBorn, Alchemical, GroupRestraints),
 # in the order of the library's table (engine.h).  The order is fixed: it is the launch order, and the order in which the energies
 # are added to the potential; both are floating-point sums, so another order changes bits.
-SIDE_TERMS = ("restraints", "metadynamics", "implicit_solvent", "alchemical")
+SIDE_TERMS = ("restraints", "metadynamics", "implicit_solvent", "alchemical", "group_restraints")
 
 
 def active_side_terms(forces):
@@ -404,6 +404,12 @@ class Forces:
                           and dU/dlambda, `alchemical_energies()` the cross energy at other couplings.  Not under
                           `torch.vmap`, with `batch=`, `virtual_sites=`, `pme=True`, `implicit_solvent=`, `barostat=`,
                           `pressure()` / `virial()`, the repulsion terms or the domain decomposition.
+    group_restraints      a `group_restraints.GroupRestraints`: harmonic, optionally flat-bottomed restraints on the distance,
+                          angle and dihedral between centres of groups of atoms, per replica.  Groups without
+                          explicit weights are weighted by the masses of `parameters`.  Its force is added last,
+                          `compute(returnDetails=True)` reports a "group_restraints" entry and the total includes it, and
+                          `Integrator.step` integrates under the total force.  Not under `torch.vmap`, with `batch=`,
+                          `barostat=`, `pressure()` / `virial()`, `update_atoms` or the domain decomposition.
     """
 
     bonded = ["bonds", "angles", "dihedrals", "impropers", "1-4"]
@@ -433,6 +439,7 @@ class Forces:
         metadynamics=None,
         implicit_solvent=None,
         alchemical=None,
+        group_restraints=None,
         restraints=None,
     ):
         self.par = parameters
@@ -558,6 +565,13 @@ class Forces:
                 tables = (torch.as_tensor(A).detach().cpu().double().numpy(), torch.as_tensor(B).detach().cpu().double().numpy(),
                           parameters.mapped_atom_types.detach().cpu().numpy())
             alchemical.check(self.natoms, parameters, self.energies, self._excl_csr, tables)
+        self.group_restraints = group_restraints
+        if group_restraints is not None:
+            from .group_restraints import GroupRestraints
+
+            if not isinstance(group_restraints, GroupRestraints):
+                raise ValueError("group_restraints must be a group_restraints.GroupRestraints")
+            group_restraints.check(self.natoms, torch.as_tensor(parameters.masses).detach().cpu().double().reshape(-1).numpy(), virtual_sites)
         self._side_potential = {}  # {side_name: [R]} of the last synchronous evaluation, host
         self._engines = {}
         self._box_cache = None
@@ -655,6 +669,32 @@ class Forces:
             L.check(eng.lib.tmdhip_restraint_states(eng.ctx, C.c_void_p(p.data_ptr()), boxes.ctypes.data_as(C.POINTER(C.c_double)),
                                                     out.ctypes.data_as(C.POINTER(C.c_double)),
                                                     C.c_void_p(torch.cuda.current_stream(p.device).cuda_stream)), "tmdhip_restraint_states")
+        return out
+
+    def group_restraint_energies(self, pos, box):
+        """The (distance, angle, dihedral) group-restraint energies of every replica's configuration, in its own box, under every
+        replica's row of the tables: [R, R, 3] float64 (numpy), entry [i, k] = configuration i under row k
+        (tmdhip_group_restraint_states).  The diagonal holds the bits an evaluation reports for the same state."""
+        if self.group_restraints is None:
+            raise ValueError("group_restraint_energies() needs group_restraints=")
+        if _is_batched(pos):
+            raise ValueError("group_restraint_energies() cannot run under torch.vmap")
+        L.require_device_tensor(pos, "pos")
+        p = pos.detach()
+        if not p.is_contiguous():
+            p = p.contiguous()
+        if p.dim() != 3 or p.shape[1] != self.natoms:
+            raise RuntimeError(f"pos must have shape (nreplicas, {self.natoms}, 3), got {tuple(p.shape)}")
+        eng = self._engine(p)
+        R = p.shape[0]
+        boxes = self._replica_boxes(box, R)
+        out = np.empty((R, R, 3), dtype=np.float64)
+        with torch.cuda.device(p.device):
+            self.group_restraints.sync(eng, self)
+            L.check(eng.lib.tmdhip_group_restraint_states(eng.ctx, C.c_void_p(p.data_ptr()), boxes.ctypes.data_as(C.POINTER(C.c_double)),
+                                                          out.ctypes.data_as(C.POINTER(C.c_double)),
+                                                          C.c_void_p(torch.cuda.current_stream(p.device).cuda_stream)),
+                    "tmdhip_group_restraint_states")
         return out
 
     def _gb_box(self, hbox):

@@ -16,7 +16,10 @@ replica exchange on the ladder of `thermostat: csvr`) every monitor
 ladder the replica slot holds at that row — and the acceptance counts are written to `exchange.json` at the end.  With
 `restraints: file.npz` (harmonic position and distance restraints; arrays named as the fields of
 tmdhip_restraint_desc without `_host`, per-replica leading axes optional) every monitor file gains a `restraints` column: the
-restraint energy that `epot` contains.  With a `metadynamics:` mapping (the arguments of `metadynamics.Metadynamics`: cvs, sigma,
+restraint energy that `epot` contains.  With `group_restraints: file.npz` (restraints on the distance, angle and dihedral
+between centres of groups of atoms; arrays group_off, member_atom, optionally member_weight, kind, groups, target, k,
+optionally flat) every monitor file gains a `group_restraints` column likewise, and the start configuration is checked for groups
+that are not whole.  With a `metadynamics:` mapping (the arguments of `metadynamics.Metadynamics`: cvs, sigma,
 height, frequency, temperature, bias_factor, grid_min, grid_max, grid_bins, walkers) every monitor file gains a `bias`
 column (V(s(x)), inside `epot`) and one column per CV (`cv0`, `cv1`), and the hills log and the grid are written to
 `{output}_hills.npy` `[n,R,ncv+1]` and `{output}_bias_grid.npz` at the end.
@@ -82,6 +85,7 @@ DEFAULTS = dict(
     exchange_seed=None,  # seed of the exchange's random stream; None: drawn from torch's generator (so `seed` reproduces it)
     hamiltonian_exchange=None,  # None or a mapping {frequency, seed, temperature, keep_matrices}: replicas trade couplings / windows: DESIGN §24
     restraints=None,  # None or an .npz file: harmonic position / distance restraints (pos_atom, pos_ref, pos_k, dist_pair, dist_r0, dist_k): DESIGN §17
+    group_restraints=None,  # None or an .npz file: restraints between centres of groups of atoms (group_off, member_atom, kind, groups, target, k, flat): DESIGN §25
     metadynamics=None,  # None or a mapping with the arguments of metadynamics.Metadynamics (cvs: [[kind, [atoms]], ...]): DESIGN §18
     pressure=False,  # True: every monitor file gains a `pressure` column (bar): the instantaneous pressure from the molecular virial: DESIGN §19
     alchemical=None,  # None or a mapping with the arguments of alchemy.Alchemical (atoms, lambda_vdw, lambda_elec, alpha) and `states`: DESIGN §22
@@ -183,6 +187,8 @@ def get_args(arguments=None):
             raise ValueError("hamiltonian_exchange and exchange_frequency are two exchanges: give one of them")
     if isinstance(args.restraints, str) and args.restraints.lower() in ("none", "null", ""):
         args.restraints = None
+    if isinstance(args.group_restraints, str) and args.group_restraints.lower() in ("none", "null", ""):
+        args.group_restraints = None
     if isinstance(args.metadynamics, str) and args.metadynamics.lower() in ("none", "null", ""):
         args.metadynamics = None
     if args.metadynamics is not None and not isinstance(args.metadynamics, dict):
@@ -331,9 +337,17 @@ def setup(args):
         from .alchemy import Alchemical
 
         extra["alchemical"] = Alchemical.from_config(args.alchemical)
+    if args.group_restraints is not None:
+        from .group_restraints import GroupRestraints
+
+        extra["group_restraints"] = GroupRestraints.from_npz(args.group_restraints, args.replicas)
     forces = Forces(parameters, terms=terms, external=external, cutoff=args.cutoff, rfa=args.rfa,
                     switch_dist=args.switch_dist, exclusions=tuple(args.exclusions), pme=args.pme,
                     ewald_tolerance=args.ewald_tolerance, pme_order=args.pme_order, pme_grid=args.pme_grid, **extra)
+    if forces.group_restraints is not None and not forces.group_restraints.check_extent(
+            system.pos.detach().cpu().numpy(), torch.diagonal(system.box, dim1=-2, dim2=-1).detach().cpu().numpy()):
+        raise ValueError("group_restraints: an atom of a group lies half a box edge or more from the group's first atom "
+                         "(make the groups whole before the run)")
     return mol, system, forces
 
 
