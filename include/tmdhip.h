@@ -671,6 +671,50 @@ int tmdhip_metad_energy(tmdhip_ctx *ctx, double *out_host, void *stream);
 /* Host copies of the grid(s), for restart and inspection: `count` doubles = grids x nodes x (2 or 4); they synchronise. */
 int tmdhip_metad_get_grid(tmdhip_ctx *ctx, double *out_host, int64_t count);
 int tmdhip_metad_set_grid(tmdhip_ctx *ctx, const double *in_host, int64_t count);
+/* Metadynamics on CVs of groups of atoms (added to ABI 11: new symbols only).  The same grid, interpolant, hills and slot as
+ * above (a context holds ONE metadynamics bias, of either flavour; tmdhip_metad_apply / _deposit / _energy / _get_grid /
+ * _set_grid and tmdhip_set_metadynamics(enable = 0) serve both), with CVs of any number of atoms (csrc/cv_math.h):
+ *   groups    group g = members group_off[g] .. group_off[g + 1] of member_atom / member_weight (distinct atoms, weights finite
+ *             and > 0, normalised in member order).  Centre X_g = x_a0 + sum_a w_a mi(x_a - x_a0), a0 the first member, mi the
+ *             minimum image: every member must lie within half a box edge of a0 along every periodic axis.
+ *   kind 2    group distance   s = |mi(X_A - X_B)|, groups[c][0..1]; not periodic
+ *   kind 3    group angle      the angle at X_B of groups[c][0..2] in [0, pi]; not periodic; no force where sin = 0 or an arm is 0
+ *   kind 4    group dihedral   the torsion of four centres (the dihedral CV's formula); periodic on [-pi, pi)
+ *   kind 5    coordination     s = sum_{i in A} sum_{j in B, j != i} f(r_ij), A, B = groups[c][0..1] (weights not read), r the
+ *             minimum-image distance, x = (r - d0) / r0, phi = 1 for x <= 0 and 1 / (1 + x^n) otherwise (x^n by repeated
+ *             multiplication); f = phi, or with coord_dmax > 0: (phi - phi_max) / (1 - phi_max) for r < dmax and 0 from dmax on,
+ *             phi_max = phi((dmax - d0) / r0).  An atom of both sets is skipped against itself.  Not periodic.
+ * A distance or dihedral of single atoms is a kind 2 or 4 of one-atom groups of weight 1.  Refused before any allocation or
+ * launch: a bad struct size, a wrong nreplicas, ncv outside 1..2, an unknown kind, null or non-monotonic tables, an empty group,
+ * an index out of range or repeated inside a group, a weight that is not finite and > 0, a group index out of range or named
+ * twice within one CV, r0 <= 0, n outside 2..24, d0 < 0, dmax <= d0, |A| |B| >= 2^31, sigma / bins / range / spacing as above,
+ * a virtual site among the atoms, a context with passive atoms.  Refused where a run or an evaluation starts: a CV atom
+ * without mass (where masses are seen), and, with any non-zero box edge, a coordination CV without dmax or with dmax beyond
+ * half the shortest non-zero edge.  Two dependent launches per application (centres and pair sums; CVs, bias and the atoms'
+ * stores), three per deposition; double arithmetic, one rounding per store, no floating-point atomics, rows of atoms in no CV
+ * are never read or written. */
+#define TMDHIP_METAD_GROUP_DISTANCE 2
+#define TMDHIP_METAD_GROUP_ANGLE 3
+#define TMDHIP_METAD_GROUP_DIHEDRAL 4
+#define TMDHIP_METAD_COORDINATION 5
+typedef struct tmdhip_metad_group_desc {
+  int32_t struct_size; /* = sizeof(tmdhip_metad_group_desc) */
+  int32_t enable;
+  int32_t nreplicas;   /* = the context's */
+  int32_t ncv;         /* 1 or 2 */
+  int32_t shared;      /* as tmdhip_metad_desc */
+  int32_t ngroups;
+  int32_t kind[2];
+  int32_t groups[2][4]; /* group indices in the CV's order, -1 beyond the kind's number */
+  int32_t bins[2];
+  int32_t coord_n[2];
+  double grid_min[2], grid_max[2], sigma[2];
+  double coord_r0[2], coord_d0[2], coord_dmax[2]; /* coord_dmax <= 0: no dmax */
+  const int32_t *group_off_host;                  /* [ngroups + 1] */
+  const int32_t *member_atom_host;
+  const double *member_weight_host;
+} tmdhip_metad_group_desc;
+int tmdhip_set_metadynamics_groups(tmdhip_ctx *ctx, const tmdhip_metad_group_desc *desc);
 /* Instantaneous pressure: the molecular virial (added to ABI 11: new symbols only; the suite pins the number).  For orthorhombic periodic boxes, per replica and axis a:
  *   P_aa V = sum_I M_I V_I,a^2 + W_aa,   P = (P_xx + P_yy + P_zz) / 3
  *   W_aa   = 1/2 sum_i sum_{j in list(i)} d_ij,a f_ij,a - sum_i delta_i,a F_i,a

@@ -22,8 +22,8 @@ LIBDIR = os.path.join(PKG, "lib")
 OBJDIR = os.path.join(LIBDIR, "obj")
 LIBPATH = os.path.join(LIBDIR, "libtmdhip.so")
 SOURCES = ["context.hip", "list_build.hip", "pair_generic.hip", "pair_fast_f32.hip", "pair_fast_f32_batch.hip", "pair_lean_f64.hip", "md_loop.hip",
-           "md_cons.hip", "md_observe.hip", "bonded.hip", "integrator.hip", "domain.hip", "dd_migrate.hip", "pme.hip", "barostat.hip", "vsite.hip", "fire.hip", "thermostat.hip", "exchange.hip", "restraint.hip", "metad.hip", "virial.hip", "crescale.hip", "gb.hip", "alchemy.hip", "group_restraint.hip"]
-HEADERS = ["common.h", "reduce.h", "pair_math.h", "rng.h", "bonded_math.h", "engine.h", "md_step.h", "pair_fast_kernel.h", "dd_comm.h", "cons_math.h", "vsite_math.h", "pacing.h", "chain_plan.h", "grid_plan.h", "thermostat_math.h", "restraint_math.h", "metad_math.h", "virial_math.h", "crescale_math.h", "pair_walk.h", "allpairs_split.h", "charge_class.h", "gb_math.h", "alchemy_math.h", "group_math.h",
+           "md_cons.hip", "md_observe.hip", "bonded.hip", "integrator.hip", "domain.hip", "dd_migrate.hip", "pme.hip", "barostat.hip", "vsite.hip", "fire.hip", "thermostat.hip", "exchange.hip", "restraint.hip", "metad.hip", "virial.hip", "crescale.hip", "gb.hip", "alchemy.hip", "group_restraint.hip", "metad_group.hip"]
+HEADERS = ["common.h", "reduce.h", "pair_math.h", "rng.h", "bonded_math.h", "engine.h", "md_step.h", "pair_fast_kernel.h", "dd_comm.h", "cons_math.h", "vsite_math.h", "pacing.h", "chain_plan.h", "grid_plan.h", "thermostat_math.h", "restraint_math.h", "metad_math.h", "virial_math.h", "crescale_math.h", "pair_walk.h", "allpairs_split.h", "charge_class.h", "gb_math.h", "alchemy_math.h", "group_math.h", "cv_math.h", "metad_state.h",
            os.path.join("..", "..", "include", "tmdhip.h")]
 ARCH = "gfx950"
 FLAGS = ["-fno-slp-vectorize"]  # the SLP vectoriser packs the pair kernel into v_pk_* ops + v_mov transposes: measured slower

@@ -337,6 +337,30 @@ class MetadDesc(C.Structure):
     ]
 
 
+class MetadGroupDesc(C.Structure):
+    _fields_ = [
+        ("struct_size", C.c_int32),
+        ("enable", C.c_int32),
+        ("nreplicas", C.c_int32),
+        ("ncv", C.c_int32),
+        ("shared", C.c_int32),
+        ("ngroups", C.c_int32),
+        ("kind", C.c_int32 * 2),
+        ("groups", (C.c_int32 * 4) * 2),
+        ("bins", C.c_int32 * 2),
+        ("coord_n", C.c_int32 * 2),
+        ("grid_min", C.c_double * 2),
+        ("grid_max", C.c_double * 2),
+        ("sigma", C.c_double * 2),
+        ("coord_r0", C.c_double * 2),
+        ("coord_d0", C.c_double * 2),
+        ("coord_dmax", C.c_double * 2),
+        ("group_off_host", C.c_void_p),
+        ("member_atom_host", C.c_void_p),
+        ("member_weight_host", C.c_void_p),
+    ]
+
+
 class MoleculeDesc(C.Structure):
     _fields_ = [
         ("struct_size", C.c_int32),
@@ -496,6 +520,7 @@ SIGNATURES = {
         [C.c_void_p, C.c_void_p, C.POINTER(C.c_double), C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_void_p],
     ),
     "tmdhip_set_metadynamics": (C.c_int, [C.c_void_p, C.POINTER(MetadDesc)]),
+    "tmdhip_set_metadynamics_groups": (C.c_int, [C.c_void_p, C.POINTER(MetadGroupDesc)]),
     "tmdhip_metad_apply": (
         C.c_int,
         [C.c_void_p, C.c_void_p, C.POINTER(C.c_double), C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p],

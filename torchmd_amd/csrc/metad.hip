@@ -17,6 +17,10 @@
 // the hills of its grid (one, or with shared walkers all R in replica order) and does one read-modify-write of its node: one
 // writer per node, no floating-point atomics.  (b) is exp-bound (R exponentials per node behind a 16 / 32 byte load and
 // store, both one vector access per lane; consecutive lanes take consecutive nodes).
+//
+// A bias on CVs of groups of atoms (tmdhip_set_metadynamics_groups, metad_group.hip) lives in the same slot and the same
+// MetadState (metad_state.h): the grid, (b), the energy row, get / set and release here serve it unchanged; in the place of
+// (a) it runs its own gather and heights (MetadState::group_heights), which leave the same log rows.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -25,25 +29,14 @@
 
 #include "engine.h"
 #include "metad_math.h"
+#include "metad_state.h"
 
 using namespace tmd;
 
 namespace {
 
 constexpr int kNodeThreads = 256;   // the node kernel's block
-constexpr int kOut = 1 + kMetadMaxCv;  // doubles per replica of the bias kernel's report: V, s_0, s_1
-
-struct MetadState {
-  int nrep = 0, natoms = 0, shared = 0;
-  MetadDef def{};
-  int64_t nodes = 0;    // per grid
-  int ngrids = 0;
-  DevBuf grid;          // double [ngrids][nodes][width]
-  DevBuf last;          // double [R][kOut]: (V, s) of the last step of the last tmdhip_md_run
-  const void *mass_checked = nullptr;
-  size_t grid_doubles() const { return (size_t)ngrids * nodes * metad_width(def); }
-  const double *grid_of(int r) const { return grid.as<double>() + (shared ? 0 : (size_t)r * nodes * metad_width(def)); }
-};
+constexpr int kOut = kMetadOut;  // doubles per replica of the bias kernel's report: V, s_0, s_1
 
 // the positions of the CVs' atoms, in each CV's order, as doubles
 template <typename R>
@@ -145,7 +138,7 @@ int launch(MetadState *S, int rep0, int nrep, const void *pos, const void *const
 }
 
 static_assert(kSideWidth[kSideMetad] == kOut, "the bias kernel reports kOut doubles per replica");
-MetadState *state_of(tmdhip_ctx *ctx) { return (MetadState *)ctx->side[kSideMetad].state; }
+MetadState *state_of(tmdhip_ctx *ctx) { return metad_state_of(ctx); }
 
 int launch_any(tmdhip_ctx *ctx, int rep0, int nrep, const void *pos, const void *const *pos_each, const double *box_host, void *forces,
                void *vel, const void *mass, double kick, double *out, hipStream_t st) {
@@ -154,12 +147,13 @@ int launch_any(tmdhip_ctx *ctx, int rep0, int nrep, const void *pos, const void 
                                     : launch<double>(S, rep0, nrep, pos, pos_each, box_host, forces, vel, mass, kick, out, st);
 }
 
+// (the group flavour, metad_group.hip, has produced the log rows already: `heights` = false)
 template <typename R>
 int launch_deposit(MetadState *S, const void *pos, const double *box_host, double height, double kdt, int plain, double *row,
-                   hipStream_t st) {
+                   hipStream_t st, bool heights = true) {
   const size_t stride = (size_t)S->natoms * 3;
   const size_t gstride = S->shared ? 0 : (size_t)S->nodes * metad_width(S->def);
-  for (int c0 = 0; c0 < S->nrep; c0 += kSideChunk) {
+  for (int c0 = 0; heights && c0 < S->nrep; c0 += kSideChunk) {
     const int nr = std::min(kSideChunk, S->nrep - c0);
     const SideChunk B = side_chunk(nr, c0, pos, nullptr, box_host, stride * sizeof(R));
     hipLaunchKernelGGL(metad_height_kernel<R>, dim3((unsigned)nr), dim3(64), 0, st, S->def, S->grid.as<double>(), gstride, height, kdt,
@@ -190,16 +184,7 @@ int check_masses(tmdhip_ctx *ctx, const char *, const double *, const void *mass
   return 0;
 }
 
-double *run_energy(tmdhip_ctx *ctx) { return state_of(ctx)->last.as<double>(); }
-
-void release(tmdhip_ctx *ctx) {
-  MetadState *S = state_of(ctx);
-  if (!S) return;
-  S->grid.release();
-  S->last.release();
-  delete S;
-  ctx->side[kSideMetad] = SideTerm{};
-}
+void release(tmdhip_ctx *ctx) { metad_release(ctx); }
 
 }  // namespace
 
@@ -228,7 +213,7 @@ int tmdhip_set_metadynamics(tmdhip_ctx *ctx, const tmdhip_metad_desc *desc) {
   TMD_HIP(hipDeviceSynchronize());  // (a launch that reads the old grid may still be in flight)
   release(ctx);
   MetadState *S = new MetadState;
-  ctx->side[kSideMetad] = SideTerm{S, "metadynamics needs", launch_any, check_masses, run_energy, release};
+  ctx->side[kSideMetad] = SideTerm{S, "metadynamics needs", launch_any, check_masses, metad_run_energy, metad_release};
   S->nrep = nrep;
   S->natoms = n;
   S->shared = desc->shared ? 1 : 0;
@@ -261,6 +246,10 @@ int tmdhip_metad_deposit(tmdhip_ctx *ctx, const void *pos_dev, const double *box
   if (!(height > 0.0) || !std::isfinite(height)) return fail("tmdhip_metad_deposit: the height must be finite and positive");
   if (!plain && (!(kdt > 0.0) || !std::isfinite(kdt))) return fail("tmdhip_metad_deposit: k_B dT must be finite and positive (or plain = 1)");
   hipStream_t st = (hipStream_t)stream;
+  if (S->group_heights) {
+    TMD_TRY(S->group_heights(ctx, pos_dev, box_host, height, kdt, plain, log_row_dev, st));
+    return launch_deposit<double>(S, pos_dev, box_host, height, kdt, plain, log_row_dev, st, false);
+  }
   return ctx->d.dtype == TMDHIP_F32 ? launch_deposit<float>(S, pos_dev, box_host, height, kdt, plain, log_row_dev, st)
                                     : launch_deposit<double>(S, pos_dev, box_host, height, kdt, plain, log_row_dev, st);
 }

@@ -11,11 +11,25 @@ derivatives; the bias IS the cubic / bicubic Hermite interpolant of those nodes,
 `walkers="independent"` keeps one grid per replica, `"shared"` one grid that every replica deposits into (multiple walkers).
 The grid lives on the device of the `Forces` that holds the object; `grid` reads it back.  `energy_forces` and `deposit_model`
 are the numpy models of the bias kernel and of the deposit chain (the tests' reference); the module-level functions are the
-expressions of csrc/metad_math.h."""
+expressions of csrc/metad_math.h.
+
+CVs of groups of atoms (csrc/cv_math.h and metad_group.hip):
+
+    ("group_distance", (A, B))   ("group_angle", (A, B, C))   ("group_dihedral", (A, B, C, D))
+    ("coordination", (A, B), {"r0": 3.5, "n": 6, "d0": 0.0, "d_max": 9.0})
+
+A group is a sequence of atom indices or `{"atoms": [...], "weights": [...]}`; weights default to the masses the `Forces` hands
+over.  The first three act on the centres X_g = x_a0 + sum_a w_a mi(x_a - x_a0) (every member within half a box edge of the
+first: `check_extent`), the angle in [0, pi] and not periodic, the dihedral periodic.  The coordination number is
+s = sum_{i in A} sum_{j in B, j != i} f(r_ij) with x = (r - d0) / r0, phi = 1 for x <= 0 and 1 / (1 + x^n) otherwise, and, with
+`d_max`, f = (phi - phi_max) / (1 - phi_max) below d_max and 0 from there on; in a periodic box `d_max` is required and at most
+half the shortest edge (`check_box`).  A "distance" or "dihedral" beside a new kind is served as single-atom groups of weight 1;
+a bias of the two old kinds alone is untouched by all this (`grouped` is False)."""
 
 from __future__ import annotations
 
 import ctypes as C
+import math
 
 import numpy as np
 
@@ -23,6 +37,11 @@ from . import _lib as L
 from .controls import Control, whole_frequency
 
 KINDS = {"distance": 0, "dihedral": 1}
+# CVs of groups of atoms (csrc/cv_math.h, tmdhip_set_metadynamics_groups); a bias that names one of them is "grouped", and a
+# distance / dihedral beside it is served as single-atom groups of weight 1
+GROUP_KINDS = {"group_distance": 2, "group_angle": 3, "group_dihedral": 4, "coordination": 5}
+GROUP_ARITY = {2: 2, 3: 3, 4: 4, 5: 2}
+PERIODIC_KINDS = ("dihedral", "group_dihedral")
 TWO_PI = 2.0 * np.pi
 
 
@@ -133,6 +152,75 @@ def locate(lo, h, nodes, periodic, s):
     return int(fl), int(fl) + 1, x - fl, live
 
 
+def coord_phi(x, n):
+    """(phi, d phi / dx) of cv_math.h for an array x: 1 and 0 for x <= 0, else q = x^(n-1) by repeated multiplication,
+    1 / (1 + q x) and -(n q) / (1 + q x)^2."""
+    x = np.asarray(x, dtype=np.float64)
+    on = x > 0.0
+    xs = np.where(on, x, 1.0)
+    with np.errstate(over="ignore", invalid="ignore"):  # (an infinite distance: phi = 0, the slope is not a number)
+        q = np.ones_like(xs)
+        for _ in range(1, int(n)):
+            q = q * xs
+        den = 1.0 + q * xs
+        return np.where(on, 1.0 / den, 1.0), np.where(on, -(float(n) * q) / (den * den), 0.0)
+
+
+def coord_switch(r, r0, n, d0=0.0, d_max=None):
+    """(f, df/dr) of the coordination switch for an array of distances (cv_math.h's coord_switch)."""
+    r = np.asarray(r, dtype=np.float64)
+    phi, dphi = coord_phi((r - d0) / r0, n)
+    if d_max is None:
+        return phi, dphi / r0
+    phimax = coord_phi((d_max - d0) / r0, n)[0]
+    scale = 1.0 / (1.0 - phimax)
+    inside = r < d_max
+    return np.where(inside, (phi - phimax) * scale, 0.0), np.where(inside, (dphi / r0) * scale, 0.0)
+
+
+def coordination_pairs(pos, box, A, B, r0, n, d0=0.0, d_max=None):
+    """Every pair of a coordination CV seen from the atoms of A: (f [nA,nB], gd [nA,nB,3]) with gd = (df/dr / r) mi(x_i - x_j);
+    an atom of both sets has zeros against itself.  s = f.sum(), ds/dx_i += gd.sum(1) for i in A, ds/dx_j -= gd.sum(0) for j in B."""
+    A, B = np.asarray(A), np.asarray(B)
+    d = min_image(pos[A][:, None, :] - pos[B][None, :, :], box)
+    r = np.sqrt((d[..., 0] * d[..., 0] + d[..., 1] * d[..., 1]) + d[..., 2] * d[..., 2])
+    f, df = coord_switch(r, r0, n, d0, d_max)
+    other = A[:, None] != B[None, :]
+    f = np.where(other, f, 0.0)
+    on = other & (df != 0.0)
+    g = np.where(on, df / np.where(on, r, 1.0), 0.0)
+    return f, g[..., None] * d
+
+
+def cv_of_centres(kind, X, box):
+    """A CV of centres X [arity,3] (cv_math.h's cv_of_centres, operation by operation): (s, ds/dX [4,3])."""
+    g = np.zeros((4, 3))
+    if kind == GROUP_KINDS["group_distance"]:
+        d = min_image(X[0] - X[1], box)
+        r = np.sqrt((d[0] * d[0] + d[1] * d[1]) + d[2] * d[2])
+        if r > 0.0:
+            g[0] = d / r
+            g[1] = -g[0]
+        return r, g
+    if kind == GROUP_KINDS["group_angle"]:
+        u, v = min_image(X[0] - X[1], box), min_image(X[2] - X[1], box)
+        nu, nv = np.sqrt(_dot(u, u)), np.sqrt(_dot(v, v))
+        co = 1.0
+        if nu > 0.0 and nv > 0.0:
+            co = _dot(u, v) / (nu * nv)
+        co = 1.0 if co > 1.0 else (-1.0 if co < -1.0 else co)
+        theta = float(np.arccos(co))
+        si = np.sqrt(1.0 - co * co)
+        if nu > 0.0 and nv > 0.0 and si > 0.0:
+            fa, fc = 1.0 / (nu * si), 1.0 / (nv * si)
+            uh, vh = u / nu, v / nv
+            g[0] = -(fa * (vh - co * uh))
+            g[2] = -(fc * (uh - co * vh))
+            g[1] = -g[0] - g[2]
+        return theta, g
+    return cv_dihedral(X, box)
+
+
 class Metadynamics(L.SideTerm, Control):
     rank = 3  # (the deposition, as a scheduled control: after the thermostat's application where both fall on one step)
     side_name, side_width = "metadynamics", 3  # (V, s_0, s_1)
@@ -149,14 +237,21 @@ class Metadynamics(L.SideTerm, Control):
 
     def __init__(self, cvs, sigma, height, frequency, temperature, bias_factor=None, grid_min=None, grid_max=None, grid_bins=None,
                  nreplicas=1, walkers="independent"):
-        if isinstance(cvs, tuple) and len(cvs) == 2 and isinstance(cvs[0], str):
+        if isinstance(cvs, tuple) and len(cvs) in (2, 3) and isinstance(cvs[0], str):
             cvs = [cvs]
         cvs = list(cvs)
         if not 1 <= len(cvs) <= 2:
             raise ValueError("Metadynamics: one or two CVs (more than 2 CVs are not supported)")
         self.ncv = len(cvs)
         self.kinds, self.atoms = [], np.full((2, 4), -1, dtype=np.int32)
+        self.grouped = any(isinstance(cv, (tuple, list)) and len(cv) >= 1 and cv[0] in GROUP_KINDS for cv in cvs)
+        self.group_atoms, self.group_weights = [], []  # per group: int32 [n] in the order given; float64 [n] > 0 or None = the masses
+        self.cv_kind, self.cv_groups, self.coord = [], [], [None, None]  # the library's kind, the CV's groups, the switch
+        self.masses = None  # what a Forces hands over (check): the default weights
         for c, cv in enumerate(cvs):
+            if self.grouped:
+                self._add_group_cv(c, cv)
+                continue
             try:
                 kind, at = cv
             except (TypeError, ValueError):
@@ -201,12 +296,12 @@ class Metadynamics(L.SideTerm, Control):
             raise ValueError("Metadynamics: grid_bins must be a whole number or one per CV")
         self.bins = np.ones(2, dtype=np.int32)
         for c, kind in enumerate(self.kinds):
-            if kind == "dihedral":
+            if kind in PERIODIC_KINDS:
                 a, b = -np.pi, np.pi
             else:
                 a, b = lo[c], hi[c]
                 if not (np.isfinite(a) and np.isfinite(b)) or not a < b:
-                    raise ValueError(f"Metadynamics: CV {c} (distance) needs finite grid_min < grid_max")
+                    raise ValueError(f"Metadynamics: CV {c} ({kind}) needs finite grid_min < grid_max")
             nb = bins_in[c]
             if nb is None:
                 nb = int(np.ceil((b - a) / (0.5 * self.sigma[c])))
@@ -218,7 +313,7 @@ class Metadynamics(L.SideTerm, Control):
                                  "(the Hermite interpolant's force error is not small enough to integrate under beyond that)")
             self.bins[c], self.lo[c], self.h[c] = int(nb), a, h
             self.grid_min[c], self.grid_max[c] = a, b
-            self.periodic[c] = kind == "dihedral"
+            self.periodic[c] = kind in PERIODIC_KINDS
             self.nodes[c] = int(nb) if self.periodic[c] else int(nb) + 1
         self.ngrids = 1 if walkers == "shared" else self.nreplicas
         self.width = 2 if self.ncv == 1 else 4
@@ -234,6 +329,10 @@ class Metadynamics(L.SideTerm, Control):
         self.frozen = False
         self.cv = None      # [R, ncv] of the last evaluation
         self.energy = None  # [R] V(s(x)) of the last evaluation
+        if self.grouped:
+            self.row_atom = np.unique(np.concatenate(self.group_atoms)).astype(np.int64)
+            self.row_role = None
+            return
         all_atoms = sorted({int(a) for a in self.atoms.reshape(-1) if a >= 0})
         self.row_atom = np.asarray(all_atoms, dtype=np.int64)
         self.row_role = np.full((len(all_atoms), 2), -1, dtype=np.int64)
@@ -242,6 +341,156 @@ class Metadynamics(L.SideTerm, Control):
                 hit = np.nonzero(self.atoms[c] == a)[0]
                 if len(hit):
                     self.row_role[t, c] = hit[0]
+
+    # ------------------------------------------------------------------ CVs of groups
+    def _group(self, c, spec, weight_one=False):
+        """Add a group: a sequence of indices, or {"atoms": [...], "weights": [...]}; returns its index."""
+        weights = None
+        if isinstance(spec, dict):
+            unknown = sorted(set(spec) - {"atoms", "weights"})
+            if unknown or "atoms" not in spec:
+                raise ValueError(f'Metadynamics: CV {c}: a group is a list of indices or {{"atoms": [...], "weights": [...]}}')
+            spec, weights = spec["atoms"], spec.get("weights")
+        atoms = np.atleast_1d(np.asarray(spec))
+        if atoms.ndim != 1 or len(atoms) == 0:
+            raise ValueError(f"Metadynamics: CV {c}: an empty group (a group is a non-empty list of atom indices)")
+        if not np.issubdtype(atoms.dtype, np.integer) or np.any(atoms < 0):
+            raise ValueError(f"Metadynamics: CV {c}: a group needs non-negative whole atom indices")
+        if len(np.unique(atoms)) != len(atoms):
+            raise ValueError(f"Metadynamics: CV {c}: a group repeats an atom")
+        if weight_one:
+            weights = np.ones(len(atoms))
+        if weights is not None:
+            weights = np.array(weights, dtype=np.float64)
+            if weights.shape != atoms.shape or not np.all(np.isfinite(weights)) or np.any(~(weights > 0)):
+                raise ValueError(f"Metadynamics: CV {c}: weights must be [{len(atoms)}], finite and > 0")
+        for g, (at, w) in enumerate(zip(self.group_atoms, self.group_weights)):  # (the same group named again: one centre)
+            if np.array_equal(at, atoms) and ((w is None and weights is None) or (w is not None and weights is not None and np.array_equal(w, weights))):
+                return g
+        self.group_atoms.append(atoms.astype(np.int32))
+        self.group_weights.append(weights)
+        return len(self.group_atoms) - 1
+
+    def _add_group_cv(self, c, cv):
+        form = ('Metadynamics: a CV is (kind, groups) with kind group_distance, group_angle or group_dihedral, ("coordination", (A, B), '
+                '{"r0": ..., "n": 6, "d0": 0.0, "d_max": ...}), ("distance", (i, j)) or ("dihedral", (i, j, k, l))')
+        if not isinstance(cv, (tuple, list)) or len(cv) not in (2, 3) or not isinstance(cv[0], str):
+            raise ValueError(form)
+        kind = cv[0]
+        if kind not in KINDS and kind not in GROUP_KINDS:
+            raise ValueError(f"Metadynamics: unknown CV kind {kind!r} ({', '.join(list(KINDS) + list(GROUP_KINDS))})")
+        if kind == "coordination" and (len(cv) != 3 or not isinstance(cv[2], dict)):
+            raise ValueError('Metadynamics: a coordination CV takes {"r0": ..., "n": 6, "d0": 0.0, "d_max": ...}')
+        if len(cv) == 3 and kind != "coordination":
+            raise ValueError(form)
+        if kind in KINDS:  # served as single-atom groups of weight 1
+            at = np.asarray(cv[1])
+            want = 2 if kind == "distance" else 4
+            if at.shape != (want,) or not np.issubdtype(at.dtype, np.integer) or np.any(at < 0):
+                raise ValueError(f"Metadynamics: a {kind} needs {want} non-negative atom indices")
+            if len(np.unique(at)) != want:
+                raise ValueError(f"Metadynamics: CV {c} repeats an atom")
+            code, groups = (2 if kind == "distance" else 4), [self._group(c, [int(a)], weight_one=True) for a in at]
+        else:
+            code = GROUP_KINDS[kind]
+            try:
+                specs = list(cv[1])
+            except TypeError:
+                raise ValueError(form) from None
+            if len(specs) != GROUP_ARITY[code]:
+                raise ValueError(f"Metadynamics: a {kind} needs {GROUP_ARITY[code]} groups")
+            groups = [self._group(c, sp) for sp in specs]
+            if code != 5 and len(set(groups)) != len(groups):
+                raise ValueError(f"Metadynamics: CV {c}: a group is named twice")
+        if code == 5:
+            par = dict(cv[2]) if isinstance(cv[2], dict) else None
+            if par is None or "r0" not in par or set(par) - {"r0", "n", "d0", "d_max"}:
+                raise ValueError('Metadynamics: a coordination CV takes {"r0": ..., "n": 6, "d0": 0.0, "d_max": ...}')
+            r0, n, d0, d_max = par["r0"], par.get("n", 6), par.get("d0", 0.0), par.get("d_max")
+            if not np.isfinite(r0) or not r0 > 0:
+                raise ValueError(f"Metadynamics: CV {c}: r0 must be finite and positive")
+            if int(n) != n or not 2 <= n <= 24:
+                raise ValueError(f"Metadynamics: CV {c}: n must be a whole number in [2, 24]")
+            if not np.isfinite(d0) or d0 < 0:
+                raise ValueError(f"Metadynamics: CV {c}: d0 must be finite and >= 0")
+            if d_max is not None and (not np.isfinite(d_max) or not d0 < d_max):
+                raise ValueError(f"Metadynamics: CV {c}: d_max must lie above d0")
+            if len(self.group_atoms[groups[0]]) * len(self.group_atoms[groups[1]]) >= 2**31:
+                raise ValueError(f"Metadynamics: CV {c}: |A| |B| must stay below 2^31")
+            self.coord[c] = {"r0": float(r0), "n": int(n), "d0": float(d0), "d_max": None if d_max is None else float(d_max)}
+        self.kinds.append(kind)
+        self.cv_kind.append(code)
+        self.cv_groups.append(groups)
+
+    def raw_weights(self, g):
+        """The raw weights of group g: the explicit ones, or the masses a `Forces` handed over (`masses` may be set by hand)."""
+        if self.group_weights[g] is not None:
+            return self.group_weights[g]
+        if self.masses is None:
+            raise ValueError("Metadynamics: a group without explicit weights needs masses (pass the object to Forces, or set .masses)")
+        return np.asarray(self.masses, dtype=np.float64)[self.group_atoms[g]]
+
+    def _table_weights(self, g):
+        """What the library's table takes for group g: its raw weights; ones for a set of a coordination CV alone (not read)."""
+        centre = any(g in self.cv_groups[c] for c in range(self.ncv) if self.cv_kind[c] != 5)
+        if not centre and self.group_weights[g] is None and self.masses is None:
+            return np.ones(len(self.group_atoms[g]))
+        return self.raw_weights(g)
+
+    def weights(self, g):
+        """The normalised weights of group g, the sum taken in member order (as the library normalises)."""
+        W = self.raw_weights(g)
+        total = 0.0
+        for x in W:
+            total += float(x)
+        return W / total
+
+    def centres(self, pos, box):
+        """[G,3] of one replica: X_g = x_a0 + sum_a w_a mi(x_a - x_a0), the sum in the centre block's order (reduce.h)."""
+        from .group_restraints import fixed_order_sum
+
+        X = np.zeros((len(self.group_atoms), 3))
+        used = {g for c in range(self.ncv) if self.cv_kind[c] != 5 for g in self.cv_groups[c]}
+        for g, at in enumerate(self.group_atoms):
+            if g not in used:  # (the sets of a coordination CV: no centre is read)
+                continue
+            x0 = pos[at[0]]
+            X[g] = x0 + fixed_order_sum(self.weights(g)[:, None] * min_image(pos[at] - x0, box))
+        return X
+
+    def check_extent(self, pos, box):
+        """Whether the centres' precondition holds for `pos` [R,N,3] or [N,3] in `box`: every atom of a group of a centre CV
+        lies within half a box edge of the group's first atom along every periodic axis."""
+        if not self.grouped:
+            return True
+        pos = np.asarray(pos, dtype=np.float64)
+        if pos.ndim == 2:
+            pos = pos[None]
+        box = self._boxes(box, pos.shape[0])
+        used = {g for c in range(self.ncv) if self.cv_kind[c] != 5 for g in self.cv_groups[c]}
+        for g in sorted(used):
+            at = self.group_atoms[g]
+            for r in range(pos.shape[0]):
+                d, per = np.abs(min_image(pos[r, at] - pos[r, at[0]], box[r])), box[r] != 0  # (as GroupRestraints.check_extent)
+                if np.any(d[:, per] >= 0.5 * box[r][per] * (1.0 - 1e-12)):
+                    return False
+        return True
+
+    def check_box(self, box, R=None):
+        """What the library refuses of a coordination CV in a box (ValueError): with any non-zero edge `d_max` is required
+        and must not exceed half the shortest non-zero edge."""
+        if not self.grouped:
+            return
+        for b in self._boxes(box, self.nreplicas if R is None else R):
+            edges = b[b != 0]
+            for c in range(self.ncv):
+                if self.cv_kind[c] != 5 or not len(edges):
+                    continue
+                d_max = self.coord[c]["d_max"]
+                if d_max is None:
+                    raise ValueError(f"Metadynamics: CV {c}: a coordination CV in a periodic box needs d_max")
+                if d_max > 0.5 * edges.min():
+                    raise ValueError(f"Metadynamics: CV {c}: d_max must not exceed half the shortest non-zero box edge")
 
     def _per_cv(self, v, what, allow_none=False):
         if v is None:
@@ -261,9 +510,14 @@ class Metadynamics(L.SideTerm, Control):
         if at[-1] >= natoms:
             raise ValueError(f"Metadynamics: atom {at[-1]} is beyond the system's {natoms} atoms")
         if masses is not None:
-            m = np.asarray(masses, dtype=np.float64).reshape(-1)
+            m = np.array(masses, dtype=np.float64).reshape(-1)
             if np.any(~(m[at] > 0)):
                 raise ValueError(f"Metadynamics: atom {at[~(m[at] > 0)][0]} belongs to a CV and has no mass")
+            if self.grouped and (self.masses is None or not np.array_equal(self.masses, m)):
+                # the default weights: a context that holds older ones is set again, from the grid as it stands on the device
+                if self._eng is not None and self._eng.ctx:
+                    self._pull()
+                self.masses, self._eng, self._dev_dirty = m, None, False
         if virtual_sites is not None and getattr(virtual_sites, "nsites", 0):
             hit = np.intersect1d(at, np.asarray(virtual_sites.sites))
             if len(hit):
@@ -282,6 +536,8 @@ class Metadynamics(L.SideTerm, Control):
 
     def cv_values(self, pos, box):
         """(s [ncv], gradients [ncv,4,3]) of one replica: `pos` [N,3], `box` edge lengths [3]."""
+        if self.grouped:
+            return self.group_cv_values(pos, box)
         s, g = np.zeros(self.ncv), np.zeros((self.ncv, 4, 3))
         for c, kind in enumerate(self.kinds):
             if kind == "distance":
@@ -289,6 +545,32 @@ class Metadynamics(L.SideTerm, Control):
             else:
                 s[c], g[c] = cv_dihedral(pos[self.atoms[c]], box)
         return s, g
+
+    def group_cv_values(self, pos, box):
+        """(s [ncv], ds/dx as a list of [N,3] per CV) of one replica for a grouped bias, after cv_math.h and the scatter kernel
+        of metad_group.hip: a centre CV adds w_a ds/dX_g over its groups in ascending group order, a coordination CV what an
+        atom gathers as a member of A, then of B."""
+        pos = np.asarray(pos, dtype=np.float64)
+        box = np.asarray(box, dtype=np.float64).reshape(3)
+        s, grads = np.zeros(self.ncv), []
+        X = None
+        for c in range(self.ncv):
+            ds = np.zeros_like(pos)
+            if self.cv_kind[c] == 5:
+                A, B = (self.group_atoms[g] for g in self.cv_groups[c])
+                f, gd = coordination_pairs(pos, box, A, B, **self.coord[c])
+                # (the addends are the kernel's to the bit; their sums are taken exactly and rounded once, so that a comparison
+                #  carries the rounding of the device's order of summation alone)
+                s[c] = math.fsum(f.ravel())
+                ds[A] += np.array([[math.fsum(gd[i, :, k]) for k in range(3)] for i in range(len(A))]).reshape(len(A), 3)
+                ds[B] += -np.array([[math.fsum(gd[:, j, k]) for k in range(3)] for j in range(len(B))]).reshape(len(B), 3)
+            else:
+                X = self.centres(pos, box) if X is None else X
+                s[c], gC = cv_of_centres(self.cv_kind[c], X[self.cv_groups[c]], box)
+                for g, role in sorted((g, role) for role, g in enumerate(self.cv_groups[c])):
+                    ds[self.group_atoms[g]] += self.weights(g)[:, None] * gC[role]
+            grads.append(ds)
+        return s, grads
 
     def interp(self, grid, s):
         """(V, dV [ncv]) of the Hermite interpolant on one grid ([n0,2] or [n0,n1,4]) at CV values s [ncv]."""
@@ -338,6 +620,12 @@ class Metadynamics(L.SideTerm, Control):
             s, g = self.cv_values(pos[r], box[r])
             V, dV = self.interp(self._grid_of(grid, r), s)
             E[r], S[r] = V, s
+            if self.grouped:
+                f = np.zeros_like(pos[r])
+                for c in range(self.ncv):  # (CV order)
+                    f += -dV[c] * g[c]
+                F[r, self.row_atom] = f[self.row_atom]
+                continue
             for t, a in enumerate(self.row_atom):
                 f = np.zeros(3)
                 for c in range(self.ncv):  # (CV order: the order in which the kernel's thread adds)
@@ -400,6 +688,31 @@ class Metadynamics(L.SideTerm, Control):
         return [self.lo[c] + np.arange(int(self.nodes[c])) * self.h[c] for c in range(self.ncv)]
 
     # ------------------------------------------------------------------ the device side
+    def group_descriptor(self):
+        """(tmdhip_metad_group_desc, the arrays it points at) of a grouped bias."""
+        d = L.MetadGroupDesc()
+        d.struct_size = C.sizeof(L.MetadGroupDesc)
+        d.enable, d.nreplicas, d.ncv, d.ngroups = 1, self.nreplicas, self.ncv, len(self.group_atoms)
+        d.shared = 1 if self.walkers == "shared" else 0
+        for c in range(2):
+            for a in range(4):
+                d.groups[c][a] = -1
+        for c in range(self.ncv):
+            d.kind[c] = self.cv_kind[c]
+            for a, g in enumerate(self.cv_groups[c]):
+                d.groups[c][a] = g
+            d.bins[c] = int(self.bins[c])
+            d.grid_min[c], d.grid_max[c], d.sigma[c] = self.grid_min[c], self.grid_max[c], self.sigma[c]
+            if self.coord[c] is not None:
+                p = self.coord[c]
+                d.coord_n[c], d.coord_r0[c], d.coord_d0[c] = p["n"], p["r0"], p["d0"]
+                d.coord_dmax[c] = 0.0 if p["d_max"] is None else p["d_max"]
+        off = np.concatenate([[0], np.cumsum([len(a) for a in self.group_atoms])]).astype(np.int32)
+        keep = [np.ascontiguousarray(off), np.ascontiguousarray(np.concatenate(self.group_atoms).astype(np.int32)),
+                np.ascontiguousarray(np.concatenate([self._table_weights(g) for g in range(len(self.group_atoms))]).astype(np.float64))]
+        d.group_off_host, d.member_atom_host, d.member_weight_host = (a.ctypes.data_as(C.c_void_p) for a in keep)
+        return d, keep
+
     def descriptor(self):
         d = L.MetadDesc()
         d.struct_size = C.sizeof(L.MetadDesc)
@@ -444,8 +757,13 @@ class Metadynamics(L.SideTerm, Control):
             self._pull()
             if eng.nreplicas != self.nreplicas:
                 raise ValueError(f"the metadynamics bias was made for {self.nreplicas} replicas, the positions have {eng.nreplicas}")
-            d = self.descriptor()
-            L.check(eng.lib.tmdhip_set_metadynamics(eng.ctx, C.byref(d)), "tmdhip_set_metadynamics")
+            if self.grouped:
+                d, keep = self.group_descriptor()
+                L.check(eng.lib.tmdhip_set_metadynamics_groups(eng.ctx, C.byref(d)), "tmdhip_set_metadynamics_groups")
+                del keep
+            else:
+                d = self.descriptor()
+                L.check(eng.lib.tmdhip_set_metadynamics(eng.ctx, C.byref(d)), "tmdhip_set_metadynamics")
             self._eng, self._host_dirty = eng, True
         if self._host_dirty:
             g = np.ascontiguousarray(self._grid)
@@ -467,6 +785,9 @@ class Metadynamics(L.SideTerm, Control):
             raise RuntimeError("Metadynamics.deposit: give the object to a Forces(metadynamics=) first")
         pos = systems.pos
         eng = self._forces._engine(pos.detach())
+        boxes = self._forces._replica_boxes(systems.box, pos.shape[0])
+        if self.grouped:
+            self.check_box(boxes.reshape(-1, 3))
         with torch.cuda.device(pos.device):
             self.sync(eng)
             if self._log is None or self._log.device != pos.device:
@@ -478,7 +799,6 @@ class Metadynamics(L.SideTerm, Control):
                     self._log[:nh] = torch.as_tensor(self._log_host, device=pos.device)
             if self.nhills >= self._log.shape[0]:
                 self._log = torch.cat([self._log, torch.zeros_like(self._log)])
-            boxes = self._forces._replica_boxes(systems.box, pos.shape[0])
             row = self._log[self.nhills]
             plain = self.bias_factor is None
             L.check(eng.lib.tmdhip_metad_deposit(eng.ctx, C.c_void_p(pos.data_ptr()), boxes.ctypes.data_as(C.POINTER(C.c_double)),
@@ -525,10 +845,24 @@ class Metadynamics(L.SideTerm, Control):
         missing = [k for k in known[:5] if k not in conf]
         if missing:
             raise ValueError(f"metadynamics: missing keys {missing}")
+        def atom_list(v):  # a list of indices, or the name of a .npy file of indices
+            if isinstance(v, str):
+                v = np.load(v)
+            return [int(a) for a in np.asarray(v).reshape(-1)]
+
         try:
-            cvs = [(str(kind), tuple(int(a) for a in atoms)) for kind, atoms in conf.pop("cvs")]
-        except (TypeError, ValueError):
-            raise ValueError('metadynamics: cvs is a list of [kind, [atoms]] entries, e.g. [["dihedral", [4, 6, 8, 14]]]') from None
+            cvs = []
+            for entry in conf.pop("cvs"):
+                kind = str(entry[0])
+                if kind in GROUP_KINDS:
+                    groups = tuple(atom_list(g) for g in entry[1])
+                    cvs.append((kind, groups, dict(entry[2])) if kind == "coordination" else (kind, groups))
+                else:
+                    kind, atoms = entry
+                    cvs.append((kind, tuple(int(a) for a in atoms)))
+        except (TypeError, ValueError, IndexError, KeyError):
+            raise ValueError('metadynamics: cvs is a list of [kind, [atoms]] entries, e.g. [["dihedral", [4, 6, 8, 14]]], '
+                             '["group_distance", [[...], [...]]] or ["coordination", [[...], [...]], {r0: 3.5, n: 6, d_max: 9.0}]') from None
         return cls(cvs, nreplicas=nreplicas, **conf)
 
     # ------------------------------------------------------------------ restart

@@ -86,7 +86,7 @@ DEFAULTS = dict(
     hamiltonian_exchange=None,  # None or a mapping {frequency, seed, temperature, keep_matrices}: replicas trade couplings / windows: DESIGN §24
     restraints=None,  # None or an .npz file: harmonic position / distance restraints (pos_atom, pos_ref, pos_k, dist_pair, dist_r0, dist_k): DESIGN §17
     group_restraints=None,  # None or an .npz file: restraints between centres of groups of atoms (group_off, member_atom, kind, groups, target, k, flat): DESIGN §25
-    metadynamics=None,  # None or a mapping with the arguments of metadynamics.Metadynamics (cvs: [[kind, [atoms]], ...]): DESIGN §18
+    metadynamics=None,  # None or a mapping with the arguments of metadynamics.Metadynamics (cvs: [[kind, [atoms]], ...], ["group_distance", [[...], [...]]], ["coordination", [[...], [...]], {r0, n, d0, d_max}]; an atom list may be an .npy file): DESIGN §18, §26
     pressure=False,  # True: every monitor file gains a `pressure` column (bar): the instantaneous pressure from the molecular virial: DESIGN §19
     alchemical=None,  # None or a mapping with the arguments of alchemy.Alchemical (atoms, lambda_vdw, lambda_elec, alpha) and `states`: DESIGN §22
     implicit_solvent=None,  # None or "obc2": generalized-Born / surface-area implicit solvent, open boundaries only: DESIGN §21
@@ -348,6 +348,12 @@ def setup(args):
             system.pos.detach().cpu().numpy(), torch.diagonal(system.box, dim1=-2, dim2=-1).detach().cpu().numpy()):
         raise ValueError("group_restraints: an atom of a group lies half a box edge or more from the group's first atom "
                          "(make the groups whole before the run)")
+    if forces.metadynamics is not None and forces.metadynamics.grouped:
+        hbox = torch.diagonal(system.box, dim1=-2, dim2=-1).detach().cpu().numpy()
+        forces.metadynamics.check_box(hbox, R=hbox.shape[0])
+        if not forces.metadynamics.check_extent(system.pos.detach().cpu().numpy(), hbox):
+            raise ValueError("metadynamics: an atom of a group of a centre CV lies half a box edge or more from the group's first "
+                             "atom (make the groups whole before the run)")
     return mol, system, forces
 
 
